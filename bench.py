@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the A2C rollout+update hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload a3c|conv|gru|gru_bptt|fc] [--ingest ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload a3c|conv|gru|gru_bptt|fc] [--ingest ...] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: a rollout of n_envs x n_tsteps env-steps followed
 by one Updater.update_model (GAE/returns scan, forward, loss, backward, clip + optimiser).
@@ -226,6 +226,34 @@ def write_side_file(full, tag):
     except OSError as e:
         print(f"[bench] could not write the full report ({e})", file=sys.stderr)
         return None
+
+
+DUMP_CAP = 1 << 20           # --dump-outputs: elements per array; a larger output is written as a seeded sample of this many
+DUMP_MAX_BYTES = 60 * 2 ** 20      # the arrays' data: with the .npy headers and the losses, the dump stays under 64 MB
+
+
+def dump_outputs(b, out_dir):
+    """--dump-outputs: what the last timed step handed its caller, one <out_dir>/<name>.npy per array -- the rollout buffers
+    (rollout.<key>; the fp32 states rows are expanded from the single-frame store first), the update's losses (update.<key>)
+    and the net's parameters and buffers after that update (net.<name>).  Floating-point arrays as float32, the rest
+    (actions, counters) and the losses as float64.  An array of more than DUMP_CAP elements is written as its flattened
+    elements at DUMP_CAP positions drawn by numpy default_rng(0) without replacement, in ascending order."""
+    b.runner.materialize_states()
+    arrays = [("rollout." + k, v) for k, v in b.D.items()]
+    arrays += [("net." + n, t) for n, t in list(b.net.named_parameters()) + list(b.net.named_buffers())]
+    total = sum(min(t.numel(), DUMP_CAP) * (4 if t.is_floating_point() else 8) for _, t in arrays)
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays:
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_CAP, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        t = t.to(torch.float32 if t.is_floating_point() else torch.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    for k, v in (b.info or {}).items():
+        np.save(os.path.join(out_dir, f"update.{k}.npy"), np.asarray(v, dtype=np.float64))
 
 # ---------------------------------------------------------------- CPU baseline (oracle, host cores)
 def _cpu_rollout_worker(args):
@@ -825,8 +853,12 @@ def main():
                          "(configs[4]; the per-GPU shard leg of the default run sets it itself)")
     ap.add_argument("--env-workers", default="native", choices=["native", "process"])
     ap.add_argument("--n-workers", type=int, default=None, help="env worker threads/processes per rank")
-    ap.add_argument("--sustain-steps", type=int, default=200,
-                    help="if --steps is smaller, an additional region of this many steps is timed and reported")
+    ap.add_argument("--sustain-steps", type=int, default=0,
+                    help="if --steps is smaller, an additional region of this many steps is timed after it and reported "
+                         "as `sustained` (default 0: --steps is the one timed region of the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rollout buffers, losses, parameters) "
+                         "as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-update-graph", action="store_true", help="do not capture the update into a hipGraph")
     ap.add_argument("--frame-store", action="store_true",
                     help="force the single-frame uint8 rollout store + lazy fp32 states (SURVEY.md 8 row f4); it is the default "
@@ -894,6 +926,8 @@ def main():
     for _ in range(max(args.warmup - 1, 0)):
         b.step()
     elapsed, rollout_ms, update_ms = b.timed(args.steps, split=not args.no_kernel_timers)
+    if args.dump_outputs and shard.rank == 0:
+        dump_outputs(b, args.dump_outputs)
     sustained = None
     if args.steps < args.sustain_steps:
         e2, r2, u2 = b.timed(args.sustain_steps, split=not args.no_kernel_timers)

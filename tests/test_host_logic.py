@@ -63,7 +63,9 @@ def _free_port():
 
 def _worker(rank, world, port, q):
     import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    # gloo on any machine: with a GPU present Shard.from_env would pick nccl, which cannot reduce these CPU tensors
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                      A2C_DIST_BACKEND="gloo")
     from a2c_amd.parallel import Shard, moments_to_mean_std
     sh = Shard.from_env()
     assert sh.active and sh.world == world and sh.rank == rank
