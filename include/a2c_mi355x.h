@@ -19,6 +19,39 @@
  *     leading dimension / stride argument says otherwise; actions are int64;
  *   - return value: 0 = A2C_OK, negative = error (a2c_error_string()).
  */
+/*
+ * Environment switches
+ *
+ * The library reads these variables and no others (a2c_env_on / a2c_env_int in csrc/a2c_common.h;
+ * tests/test_abi.py checks this list against the sources).  "=1" means the first character is '1'.
+ * "per call": read on every call, so a process may flip it; "once": read at the first use.
+ * No switch changes a result except by choosing between two tested kernels (or two tested tilings
+ * of one kernel, which give bit-identical sums).
+ *
+ *   A2C_NO_STREAM=1          per call  conv forward / backward: no persistent streaming kernels (A3C conv1 / conv2 class)
+ *   A2C_BWD_X6=0             per call  A3C conv2 backward-data: fp32 MFMA streaming kernel instead of the bf16 x 6 one
+ *   A2C_WGRAD_X6=0           per call  A3C conv2 weight gradient (and the rank-n head path): fp32 MFMA kernel instead of x 6
+ *   A2C_WGRAD_F32=1          per call  conv1 weight gradient from the frame store: fp32 MFMAs instead of the bf16 pipe
+ *   A2C_WSB_NO_RING=1        per call  that bf16 kernel: every sample loaded whole (no frame ring in LDS)
+ *   A2C_NO_TUNE=1            per call  conv forward / band backward-data: rule-sized tiles, no timed tile search
+ *   A2C_BAND_TY=<n>          per call  band backward-data: tile height n (0 = the rule), no timed search
+ *   A2C_NO_BAND_GROUPS=1     per call  band backward-data: one workgroup for all channels
+ *   A2C_IGEMM_LDS_KB=<kb>    per call  conv forward: LDS budget of the generic kernel (default 64); set: no timed search
+ *   A2C_RUN3_LDS_KB=<kb>     per call  conv forward: LDS budget of the run3 kernel (default 80); set: no timed search
+ *   A2C_FUSE_W1=1            per call  a2c_conv2d_bwd_data_w1*: the fused band pass (measured slower) instead of two passes
+ *   A2C_C3W_D2=1             per call  3x3 weight gradient: round 3's tall-band instances (one chunk of lookahead)
+ *   A2C_NO_ODD_BS=1          per call  GRUModel conv4 / conv5 backward-data: the generic band kernel, not the odd-image one
+ *   A2C_NO_CHAIN=1           per call  a2c_conv2d_fwd_chain_supported answers 0 (separate launches)
+ *   A2C_NO_W1_FRAMES=1       once      a2c_conv2d_bwd_data_w1_frames_supported answers 0
+ *   A2C_GEMM_X9=0|1|2        per call  a2c_gemm_f32: 0 or 1 = fp32 MFMA kernels only; 2 = the x 6 kernel from M, N, K >= 256
+ *                                      and M N K >= 2.5e8 on; unset = from M, N, K >= 1024 and M N K >= 2e10 on
+ *   A2C_NO_GEMM_NT=1         per call  a2c_gemm_f32: not the A B^T split-K kernel
+ *   A2C_NO_SKINNY_STREAM=1   per call  a2c_gemm_f32: not the skinny streaming split-K kernel
+ *   A2C_GRU_K4=1             per call  GRU cell kernels: four-way K split (bit-identical to the launches they replace)
+ *   A2C_NO_RING=1            per call  a2c_a3c_rollout: the per-step body instead of the ring kernel
+ *   A2C_RING_BLOCKS=0        per call  a2c_a3c_rollout: no ring kernel when there are more envs than CUs
+ *   A2C_RING_F32=1           per call  ring kernel: conv1 on fp32 MFMAs instead of the bf16 pipe
+ */
 #ifndef A2C_MI355X_H
 #define A2C_MI355X_H
 
@@ -418,8 +451,7 @@ size_t a2c_gemm_ws_bytes(int64_t M, int64_t N, int splitk);
  * a = a0 + a1 + a2 (exact: 3 x 8 significant bits); the SIX piece products with qa + qb <= 2 are issued (each exact; the
  * three dropped ones are below 2^-24 of |a b|, under the rounding of the fp32 product itself) and every sum is the MFMA's
  * fp32 accumulator's -- nn.Linear's fp32 sum, re-associated, at 6/16 of the fp32 matrix time on paper and 1.7-1.9 x the
- * fp32 kernels measured (DESIGN.md section 4 "bf16 x 6").  A2C_GEMM_X9=0: fp32 MFMA kernels only; =1: all nine products
- * (gemm_x9_kernel; ties the fp32 kernels); =2: the six-product kernel from M, N, K >= 256 and M N K >= 2.5e8 on (tests).
+ * fp32 kernels measured (DESIGN.md section 4 "bf16 x 6").  A2C_GEMM_X9 moves the threshold (Environment switches).
  * 0: the product does not take that path.  Without the extra bytes a2c_gemm_f32 runs the fp32 MFMA kernels.            */
 size_t a2c_gemm_x9_ws_bytes(int64_t M, int64_t N, int64_t K);
 int a2c_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A,

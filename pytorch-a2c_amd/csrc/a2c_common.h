@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/a2c_mi355x.h"
 
 #define A2C_CHECK_LAUNCH()                                   \
@@ -10,6 +11,17 @@
   } while (0)
 
 static inline hipStream_t a2c_s(a2c_stream_t s) { return (hipStream_t)s; }
+
+// Environment switches: the only way the library reads its environment.  Every name, its values and when it is read are
+// listed in include/a2c_mi355x.h ("Environment switches"); tests/test_abi.py keeps that list and the sources in step.
+static inline bool a2c_env_on(const char* name) {            // set, first character '1'
+  const char* v = getenv(name);
+  return v != nullptr && v[0] == '1';
+}
+static inline int a2c_env_int(const char* name, int dflt) {  // unset or empty: dflt
+  const char* v = getenv(name);
+  return (v != nullptr && v[0] != '\0') ? atoi(v) : dflt;
+}
 
 // memory-bound elementwise kernels: cap the grid and grid-stride (guide G11)
 static inline int a2c_grid_1d(int64_t n, int block, int max_blocks = 2048) {

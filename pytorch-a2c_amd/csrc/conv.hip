@@ -66,13 +66,12 @@ struct BandKey {         // (layer, batch, flags) key of the tile-size tuners' c
   bool operator<(const BandKey& o) const { return std::lexicographical_compare(v, v + 9, o.v, o.v + 9); }
 };
 static int env_kb(const char* name, int dflt_kb) {
-  const char* v = getenv(name);
-  const int kb = v ? atoi(v) : 0;
+  const int kb = a2c_env_int(name, 0);
   return (kb > 0 ? kb : dflt_kb) * 1024;
 }
-// LDS per workgroup decides how many workgroups share a CU (160 KB): tunable for experiments
+// LDS per workgroup decides how many workgroups share a CU (160 KB)
 #define IGEMM_LDS_BUDGET env_kb("A2C_IGEMM_LDS_KB", 64)
-#define WGRAD_LDS_BUDGET env_kb("A2C_WGRAD_LDS_KB", 48)   // 3 workgroups per CU: the tiled kernels stage synchronously and rely on neighbours for overlap (76 KB: -10..25 % on the 3x3 layers)
+constexpr int WGRAD_LDS_BUDGET = 48 * 1024;   // 3 workgroups per CU: the tiled kernels stage synchronously and rely on neighbours for overlap (76 KB: -10..25 % on the 3x3 layers)
 constexpr int LDS_HARD_MAX = 160 * 1024;
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -545,13 +544,12 @@ struct StreamP {
   const float* wfrag; const float* bias;
   float* out; long out_bs;
   int B, H, W, OH, OW, Mch, relu, PLANE1, PLANEo;
-  int dbg;      // experiments (A2C_STREAM_DBG): 1 = no matrix phase, 2 = no input loads, 4 = no output stores
 };
 
 // one float4 slot of the sample: global -> register / register -> LDS.  Named scalars, not arrays:
 // the prefetch registers live across the persistent loop's back edge and must not end up in scratch.
 #define ST_LD(var, u, src) \
-  if (!(p.dbg & 2)) var = *reinterpret_cast<const float4*>((src) + (min(tid + (u) * ST_NT, tot4 - 1) << 2));
+  var = *reinterpret_cast<const float4*>((src) + (min(tid + (u) * ST_NT, tot4 - 1) << 2));
 #define ST_ST(var, u)                                                                          \
   {                                                                                            \
     const int idx_ = min(tid + (u) * ST_NT, tot4 - 1);                                          \
@@ -605,7 +603,7 @@ __global__ __launch_bounds__(ST_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     // compiler fall back to conservative vmcnt waits (measured 1.36 ms vs 1.23 ms); one burst before
     // the first tile costs 1.45 ms, one load per kernel row inside the tiles 1.50 ms.
 #define ST_TILE(T)                                                                                          \
-    if (!(p.dbg & 1) && (T) * (ST_NT / 64) + w < nfull) {                                                   \
+    if ((T) * (ST_NT / 64) + w < nfull) {                                                                   \
       const int idx = ((T) * (ST_NT / 64) + w) * 16 + j;                                                    \
       const bool ok = idx < NP;                                                                             \
       const int i = ok ? idx : 0;                                                                           \
@@ -638,7 +636,7 @@ __global__ __launch_bounds__(ST_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     ST_LD(v8, 8, nsrc) ST_LD(v9, 9, nsrc) ST_LD(v10, 10, nsrc) ST_LD(v11, 11, nsrc)
     ST_TILE(2)
     ST_LD(v12, 12, nsrc) ST_LD(v13, 13, nsrc)
-    if (!(p.dbg & 1) && nfull < ntile) {             // leftover tile: this wave's kernel row ky = w (8 of its 64 steps)
+    if (nfull < ntile) {                             // leftover tile: this wave's kernel row ky = w (8 of its 64 steps)
       const int idx = nfull * 16 + j;
       const int i = idx < NP ? idx : 0;
       const int r = i / p.OW, c = i - r * p.OW;
@@ -668,14 +666,14 @@ __global__ __launch_bounds__(ST_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
       for (int x = 1; x < ST_NT / 64; ++x) sum += q[x];
       sum += ob[co * p.PLANEo + NP];
       if (p.relu) sum = fmaxf(sum, 0.f);
-      if (!(p.dbg & 4)) dst[(long)co * NP + split0 + jx] = sum;
+      dst[(long)co * NP + split0 + jx] = sum;
     }
 #pragma unroll
     for (int u = 0; u < ST_FL; ++u) {                // outputs of the whole tiles of sample n: LDS -> HBM
       const int idx = min(tid + u * ST_NT, otot - 1);
       const int co = idx / out4, e = (idx - co * out4) << 2;
       const float4 t = *reinterpret_cast<const float4*>(ob + co * p.PLANEo + e);
-      if (!(p.dbg & 4)) *reinterpret_cast<float4*>(dst + (long)co * NP + e) = t;
+      *reinterpret_cast<float4*>(dst + (long)co * NP + e) = t;
     }
   }
 }
@@ -1063,7 +1061,7 @@ static void fill_stage(StageP& s, const SrcTile& t, const float* src, long bstri
            ((uintptr_t)src % 16 == 0);
   s.vec = stage_vec(src, bstride, t.IH, t.IW);
   s.flat = (t.tiles == 1 && t.sy0 <= 0 && t.TIH + t.sy0 >= t.IH && bstride % 4 == 0 && ((uintptr_t)src % 16 == 0) &&
-            ((long)t.Cp * t.IH * t.IW) % 4 == 0 && !getenv("A2C_NO_FLAT_STAGE")) ? 1 : 0;
+            ((long)t.Cp * t.IH * t.IW) % 4 == 0) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------ backward-weight
@@ -1613,40 +1611,8 @@ struct BstreamP {
     img[soff[2 * (u) + 1] & 0xffffu] = var.z; img[soff[2 * (u) + 1] >> 16] = var.w;             \
   }
 
-template <bool MASK>
-__global__ __launch_bounds__(BS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void bwd_stream_kernel(BstreamP p) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* __restrict__ img = lds;                              // dOut of the sample with a one-pixel zero halo
-  float* __restrict__ outb = lds + p.Cout * p.PLANE + 64;     // dX of the sample, [Cin][H*W]
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int g = lane >> 4, j = lane & 15;
-  const int WP = p.WP, PLANE = p.PLANE, HW = p.H * p.W;
-  const int ohw = p.OH * p.OW, nel4 = (p.Cout * ohw) >> 2, n4 = (p.Cin * HW) >> 2;
-  for (int i = tid; i < p.Cout * PLANE + 64; i += BS_NT) img[i] = 0.f;       // halo stays 0 forever
-  const BwdClass k = p.cls[w & 3];
-  const int half = w >> 2;
-  float af[32];
-#pragma unroll
-  for (int s = 0; s < 32; ++s) af[s] = p.wfrag[k.frag_off + s * 64 + lane];
-  const int NP = k.PH * k.PW, ntile = (NP + 15) >> 4;
-  float4 d0 = {}, d1 = {}, d2 = {}, d3 = {}, d4 = {}, d5 = {}, m0 = {}, m1 = {}, m2 = {}, m3 = {};
-  unsigned int soff[12];
-  BS_OFF(0) BS_OFF(1) BS_OFF(2) BS_OFF(3) BS_OFF(4) BS_OFF(5)
-  long b = blockIdx.x;
-  if (b >= p.B) return;
-  {
-    const float* __restrict__ src = p.dout + b * (long)p.Cout * ohw;
-    BS_LDD(d0, 0, src) BS_LDD(d1, 1, src) BS_LDD(d2, 2, src) BS_LDD(d3, 3, src) BS_LDD(d4, 4, src) BS_LDD(d5, 5, src)
-  }
-  for (; b < p.B; b += gridDim.x) {
-    const long nb = (b + gridDim.x < p.B) ? b + gridDim.x : b;          // past the end: re-read this sample (discarded)
-    const float* __restrict__ nsrc = p.dout + nb * (long)p.Cout * ohw;
-    const float* __restrict__ msrc = p.mask + b * (long)p.Cin * HW;
-    float* __restrict__ dst = p.din + b * (long)p.Cin * HW;
-    BS_STD(d0, 0) BS_STD(d1, 1) BS_STD(d2, 2) BS_STD(d3, 3) BS_STD(d4, 4) BS_STD(d5, 5)
-    __syncthreads();
-    /* two tiles of this wave at a time: two INDEPENDENT accumulator chains sharing the A fragments (a single chain issues */ \
-    /* one MFMA per 40-cycle dependent latency instead of one per 32); the second tile may not exist (wave-uniform)        */
+// two tiles of this wave at a time: two INDEPENDENT accumulator chains sharing the A fragments (a single chain issues
+// one MFMA per 40-cycle dependent latency instead of one per 32); the second tile may not exist (wave-uniform)
 #define BS_PAIR(TA)                                                                                         \
     {                                                                                                       \
       const int tA = (TA) * 2 + half, tB = tA + 2;                                                          \
@@ -1688,29 +1654,9 @@ __global__ __launch_bounds__(BS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         }                                                                                                   \
       }                                                                                                     \
     }
-    if (MASK) { BS_LDM(m0, 0, msrc) BS_LDM(m1, 1, msrc) BS_LDM(m2, 2, msrc) BS_LDM(m3, 3, msrc) }
-    BS_LDD(d0, 0, nsrc) BS_LDD(d1, 1, nsrc) BS_LDD(d2, 2, nsrc)
-    BS_PAIR(0)                                                  // tiles half, half + 2
-    BS_LDD(d3, 3, nsrc) BS_LDD(d4, 4, nsrc) BS_LDD(d5, 5, nsrc)
-    for (int tp = 2; tp * 2 + half < ntile; tp += 2) BS_PAIR(tp) // tiles half + 4, half + 6, ...
-    __syncthreads();                                            // every class has landed in outb
-#define BS_FLUSH(mv, u)                                                                         \
-    {                                                                                           \
-      const int i_ = min(tid + (u) * BS_NT, n4 - 1) << 2;                                        \
-      float4 v_ = *reinterpret_cast<const float4*>(outb + i_);                                  \
-      if (MASK) {                                                                               \
-        if (!(mv.x > 0.f)) v_.x = 0.f;                                                          \
-        if (!(mv.y > 0.f)) v_.y = 0.f;                                                          \
-        if (!(mv.z > 0.f)) v_.z = 0.f;                                                          \
-        if (!(mv.w > 0.f)) v_.w = 0.f;                                                          \
-      }                                                                                         \
-      *reinterpret_cast<float4*>(dst + i_) = v_;                                                \
-    }
-    BS_FLUSH(m0, 0) BS_FLUSH(m1, 1) BS_FLUSH(m2, 2) BS_FLUSH(m3, 3)
-  }
-}
 
-// bwd_stream_kernel, second form (round 6).  Two things the first form pays for per sample, measured: (1) the flush of the
+// bwd_stream2_kernel, the second form (round 6; the first form, bwd_stream_kernel, is at commit 15c35e9: every descriptor
+// that passes the streaming gate fits the second form's LDS).  Two things the first form paid for per sample, measured: (1) the flush of the
 // sample's dX (25.6 KB: LDS read, mask, global store) sits between two matrix phases with the matrix pipe idle, and the loop
 // top's wait for the next sample's dOut also waits for those fresh stores (loads and stores retire through one in-order
 // counter); (2) the ReLU mask is the fp32 activation itself, 25.6 KB per sample read for one bit per element (42 % of the
@@ -1728,7 +1674,6 @@ struct Bstream2P {
   BstreamP s;
   const unsigned long long* lmask;      // MODE 2: (B, lmw) 64-bit words
   int lmw;                              // words per sample = Cin * H * W / 64
-  int order;                            // third form: 0 = the two waves of a SIMD out of step, 1 = side work first, 2 = first tile pair first
   unsigned long long* dbg;              // second form: phase stamps of workgroup 0 (a2c_debug_bwd_stream_timing), [wave][8] shader clocks
 };
 template <int MODE, bool STAMP = false>
@@ -1835,101 +1780,6 @@ __global__ __launch_bounds__(BS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   if (stamp && lane == 0)
     for (int i = 0; i < 8; ++i) pp.dbg[w * 8 + i] = tsum[i];
 #undef BS2_TS
-}
-
-// Third form, OPT-IN (A2C_BWD_STREAM_FORM=3): built after the counters, measured, and slower -- 0.855 ms with the waves out of
-// step, 0.869 with the side work first on all waves, 0.913 with the first tile pair first, against 0.74 for the second form
-// (same box, alternating runs, tools/ab_bs3.sh).  Kept for the record and for the next look with a phase-stamp build.
-// (round 6, after the counters: MFMA pipe 54 % busy, the rest is time in which BOTH waves of a SIMD sit in the same
-// non-matrix phase -- staging, flush, the LDS reads at the head of a k block -- because two barriers per sample keep them in
-// step).  ONE barrier per sample: the dOut image is double buffered too (sample b + 1 is staged into the other image during
-// sample b's interval), and the two waves of a SIMD (class k, halves 0 and 1) run the interval's work in DIFFERENT orders --
-// half 0: first tile pair, flush, staging, loads, rest; half 1: flush, staging, loads, then its tiles -- so that one wave's
-// stores / LDS writes / address arithmetic run under the other's MFMAs.  Same sums in the same order: bit-identical dX.
-template <int MODE>
-__global__ __launch_bounds__(BS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void bwd_stream3_kernel(Bstream2P pp) {
-  const BstreamP& p = pp.s;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int g = lane >> 4, j = lane & 15;
-  const int WP = p.WP, PLANE = p.PLANE, HW = p.H * p.W;
-  const int obs = p.Cin * HW;                                 // floats per dX image
-  const int IMG = p.Cout * p.PLANE + 64;                      // floats per dOut image (one-pixel zero halo)
-  float* __restrict__ img0 = lds;                             // two dOut images
-  float* __restrict__ outb0 = lds + 2 * IMG;                  // two dX images, [Cin][H*W] each
-  const int ohw = p.OH * p.OW, nel4 = (p.Cout * ohw) >> 2, n4 = obs >> 2;
-  for (int i = tid; i < 2 * IMG; i += BS_NT) img0[i] = 0.f;   // halos stay 0 forever
-  const BwdClass k = p.cls[w & 3];
-  const int half = __builtin_amdgcn_readfirstlane(w >> 2);
-  float af[32];
-#pragma unroll
-  for (int s = 0; s < 32; ++s) af[s] = p.wfrag[k.frag_off + s * 64 + lane];
-  const int NP = k.PH * k.PW, ntile = (NP + 15) >> 4;
-  float4 d0 = {}, d1 = {}, d2 = {}, d3 = {}, d4 = {}, d5 = {}, m0 = {}, m1 = {}, m2 = {}, m3 = {};
-  unsigned int soff[12];
-  BS_OFF(0) BS_OFF(1) BS_OFF(2) BS_OFF(3) BS_OFF(4) BS_OFF(5)
-  long b = blockIdx.x;
-  if (b >= p.B) return;
-#define BS3_STD(var, u, base)                                                                   \
-  {                                                                                             \
-    (base)[soff[2 * (u)] & 0xffffu] = var.x; (base)[soff[2 * (u)] >> 16] = var.y;               \
-    (base)[soff[2 * (u) + 1] & 0xffffu] = var.z; (base)[soff[2 * (u) + 1] >> 16] = var.w;       \
-  }
-  __syncthreads();                                            // the zero fill, before anything is staged
-  {
-    const float* __restrict__ src = p.dout + b * (long)p.Cout * ohw;
-    BS_LDD(d0, 0, src) BS_LDD(d1, 1, src) BS_LDD(d2, 2, src) BS_LDD(d3, 3, src) BS_LDD(d4, 4, src) BS_LDD(d5, 5, src)
-    BS3_STD(d0, 0, img0) BS3_STD(d1, 1, img0) BS3_STD(d2, 2, img0) BS3_STD(d3, 3, img0) BS3_STD(d4, 4, img0) BS3_STD(d5, 5, img0)
-    const long b1 = (b + gridDim.x < p.B) ? b + gridDim.x : b;
-    const float* __restrict__ s1 = p.dout + b1 * (long)p.Cout * ohw;
-    BS_LDD(d0, 0, s1) BS_LDD(d1, 1, s1) BS_LDD(d2, 2, s1) BS_LDD(d3, 3, s1) BS_LDD(d4, 4, s1) BS_LDD(d5, 5, s1)
-  }
-  __syncthreads();
-  long pb = -1;
-  int cur = 0;
-  unsigned int lmb = 0;                                       // MODE 2: the mask bits of sample pb for this thread's four flush units
-  for (; b < p.B; b += gridDim.x) {
-    const long nb2 = (b + 2L * gridDim.x < p.B) ? b + 2L * gridDim.x : b;      // past the end: re-read this sample (discarded)
-    const float* __restrict__ nsrc = p.dout + nb2 * (long)p.Cout * ohw;
-    const float* __restrict__ msrc = p.mask + b * (long)obs;
-    const float* __restrict__ img = img0 + cur * IMG;         // this sample's dOut (staged during the previous interval)
-    float* __restrict__ imgn = img0 + (cur ^ 1) * IMG;        // the next sample's
-    float* __restrict__ outb = outb0 + cur * obs;             // this sample's dX
-    const float* __restrict__ ob = outb0 + (cur ^ 1) * obs;   // the previous sample's, flushed in this interval
-    unsigned int lb0 = 0, lb1 = 0, lb2 = 0, lb3 = 0;
-    // everything of the interval that is not this sample's matrix work
-#define BS3_SIDE                                                                                                   \
-    {                                                                                                              \
-      if (pb >= 0) { BS2_FLUSH(m0, 0, pb, ob) BS2_FLUSH(m1, 1, pb, ob) BS2_FLUSH(m2, 2, pb, ob) BS2_FLUSH(m3, 3, pb, ob) } \
-      BS3_STD(d0, 0, imgn) BS3_STD(d1, 1, imgn) BS3_STD(d2, 2, imgn) BS3_STD(d3, 3, imgn) BS3_STD(d4, 4, imgn) BS3_STD(d5, 5, imgn) \
-      if (MODE == 1) { BS_LDM(m0, 0, msrc) BS_LDM(m1, 1, msrc) BS_LDM(m2, 2, msrc) BS_LDM(m3, 3, msrc) }           \
-      if (MODE == 2) {                                                                                             \
-        const unsigned char* __restrict__ lmp = reinterpret_cast<const unsigned char*>(pp.lmask) + b * (long)pp.lmw * 8; \
-        const int nby = n4 >> 1;                                                                                   \
-        lb0 = lmp[min((tid + 0 * BS_NT) >> 1, nby - 1)]; lb1 = lmp[min((tid + 1 * BS_NT) >> 1, nby - 1)];          \
-        lb2 = lmp[min((tid + 2 * BS_NT) >> 1, nby - 1)]; lb3 = lmp[min((tid + 3 * BS_NT) >> 1, nby - 1)];          \
-      }                                                                                                            \
-      BS_LDD(d0, 0, nsrc) BS_LDD(d1, 1, nsrc) BS_LDD(d2, 2, nsrc) BS_LDD(d3, 3, nsrc) BS_LDD(d4, 4, nsrc) BS_LDD(d5, 5, nsrc) \
-    }
-    if (pp.order == 2 || (pp.order == 0 && half == 0)) {
-      BS_PAIR(0)
-      BS3_SIDE
-    } else {
-      BS3_SIDE
-      BS_PAIR(0)
-    }
-    for (int tp = 2; tp * 2 + half < ntile; tp += 2) BS_PAIR(tp) // tiles half + 4, half + 6, ...
-    if (MODE == 2) lmb = lb0 | (lb1 << 8) | (lb2 << 16) | (lb3 << 24);
-    __syncthreads();                                            // this sample's dX complete, the next sample's dOut staged
-    pb = b;
-    cur ^= 1;
-  }
-#undef BS3_SIDE
-  {
-    const float* __restrict__ ob = outb0 + (cur ^ 1) * obs;
-    BS2_FLUSH(m0, 0, pb, ob) BS2_FLUSH(m1, 1, pb, ob) BS2_FLUSH(m2, 2, pb, ob) BS2_FLUSH(m3, 3, pb, ob)
-  }
-#undef BS3_STD
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2947,7 +2797,7 @@ constexpr int A_0 = X2_0 + 3 * CQ, AQ = 6656, AROW = 208;
 constexpr int ZERO = A_0 + 3 * AQ, LDS_BYTES = ZERO + 32;
 }  // namespace wx
 struct WgradX6P {
-  const float* in; long in_bs; const float* dout; float* slab; int B; int dbg;
+  const float* in; long in_bs; const float* dout; float* slab; int B;
   // RANK (see BwdX6P): dOut formed in the kernel, written to the fp32 scratch in place of the DMA
   const float* dl; long ldl; int nlog; const float* Wc; const unsigned char* a2b; long a2b_row;
 };
@@ -3067,7 +2917,7 @@ __global__ __launch_bounds__(wx::NT) void wgrad_x6_kernel(WgradX6P p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                   // the sample's scratch has landed; the previous matrix phase is over
     // ---- conversion (waves 0-1: two half rows; 2-3: half row + dOut group; 4-7: half row, weight column, dOut group)
-    if (!(p.dbg & 1)) {
+    {
       half_row(tid);
       if (tid < 128) half_row(512 + tid);
       if (tid >= 256) {  // the column ox = 8 (rows oy 0..7) and the corner of weight column n
@@ -3084,7 +2934,7 @@ __global__ __launch_bounds__(wx::NT) void wgrad_x6_kernel(WgradX6P p) {
         }
       }
     }
-    if (!(p.dbg & 2) && tid >= 128 && tid < 480) {     // dOut group (co, gi): 0..8 rows, 9 the column, 10 the corner
+    if (tid >= 128 && tid < 480) {     // dOut group (co, gi): 0..8 rows, 9 the column, 10 the corner
       const int id = tid - 128, co = id / 11, gi = id - co * 11;
       const float* __restrict__ src = sdo + co * 81;
       float e[8];
@@ -3110,9 +2960,8 @@ __global__ __launch_bounds__(wx::NT) void wgrad_x6_kernel(WgradX6P p) {
       const long b2 = b + 2L * gridDim.x;
       raw(b2 < p.B ? b2 : b);                          // (and the small loads first: the loop top waits for the youngest)
     }
-    if (b + gridDim.x < p.B && !(p.dbg & 8)) dma(b + gridDim.x);
+    if (b + gridDim.x < p.B) dma(b + gridDim.x);
     // ---- matrix phase: three steps of 32 pixel slots; all twelve fragments of a step first, then its 24 MFMAs
-    if (!(p.dbg & 4))
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
       // The fragment reads go through inline asm: hipcc's waitcnt insertion treats every LDS access of a kernel that issues
@@ -3178,249 +3027,6 @@ __global__ __launch_bounds__(wx::NT) void wgrad_x6_kernel(WgradX6P p) {
   if (tid < 32) {
     float sdb = 0.f;
     for (int q = 0; q < 16; ++q) sdb += red[q * 32 + tid];
-    sl[32 * 256 + tid] = sdb;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// wgrad_x6p_kernel, OPT-IN (A2C_WGRAD_X6=2): built to run the conversion of sample n + 1 UNDER the matrix phase of sample n,
-// measured, and no faster -- 0.48-0.50 ms against 0.46 for wgrad_x6_kernel (same box, tools/wgrad_x6_timing.py): matrix phase
-// alone 0.31, conversion alone 0.21-0.25, together 0.48 whether the two waves of a SIMD run them in opposite order or in the
-// same order.  The phases do not compete for the matrix pipe and the vector ALU but for the LDS: ~390 ds_write_b32 / b16 per
-// sample at 4 cycles each on the store path beside ~650 fragment reads, 40 % of whose LDS cycles are bank conflicts.  Kept for
-// the record and for the next step there (wider stores, a conflict-free run pitch); dW is bit-identical to wgrad_x6_kernel.
-// wgrad_x6_kernel runs its two phases in sequence (conversion 0.22 ms + matrix phase 0.31 of its 0.47-0.51 ms): both waves of a
-// SIMD convert, then both multiply.  Here the piece images exist twice (two sets of 72 KB: phase runs at a 20-byte pitch --
-// fragments are four or five ds_read_b32 --, the corner cells as single dwords) and there is no fp32 scratch: a thread converts
-// straight from the float4s it prefetched (the next sample's, in registers during the whole interval).  Per sample ONE barrier;
-// between two barriers every wave multiplies sample n out of set n & 1 and converts sample n + 1 into the other set -- waves
-// 0-3 multiply first, waves 4-7 convert first, and waves w and w + 4 share a SIMD: its matrix pipe and its vector ALU work at
-// the same time.  Same MFMA order per accumulator as wgrad_x6_kernel: dW is bit-identical to it (db: sums in another order).
-namespace wxp {
-constexpr int NT = 512;
-constexpr int PQ = 12800, PRUN = 20, P0 = 0;                       // [q][run 640][10 el]
-constexpr int C2_0 = P0 + 3 * PQ, CQ = 4096;                       // [q][n 256][8 el]
-constexpr int X2_0 = C2_0 + 3 * CQ, XQ = 1024;                     // [q][n 256] one dword: the corner element, 0
-constexpr int A_0 = X2_0 + 3 * XQ, AQ = 6656, AROW = 208;          // [q][co 32][104 el]
-constexpr int SET = A_0 + 3 * AQ;                                  // 73,728
-constexpr int LDS_BYTES = 2 * SET;
-static_assert(SET == 73728 && SET % 16 == 0, "set");
-}  // namespace wxp
-template <bool RANK>
-__global__ __launch_bounds__(wxp::NT) void wgrad_x6p_kernel(WgradX6P p) {
-  using namespace wxp;
-  extern __shared__ __attribute__((aligned(16))) unsigned char ldsp[];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int l16 = lane & 15, g = lane >> 4;
-  const int wq = w & 3, th = w >> 2;                   // channel pair 2 wq + th; th also = "converts first"
-  for (int i = tid; i < LDS_BYTES / 16; i += NT) *reinterpret_cast<u32x4x*>(ldsp + i * 16) = (u32x4x){0u, 0u, 0u, 0u};
-  // ---- matrix-phase addresses of this lane (within a set)
-  int ncol[2];
-  const int ci_l = 2 * (2 * wq + th) + (l16 >> 3), ky_l = (l16 >> 1) & 3, kxl_l = l16 & 1;
-#pragma unroll
-  for (int tt = 0; tt < 2; ++tt) ncol[tt] = (ci_l * 4 + ky_l) * 4 + 2 * tt + kxl_l;
-  const int prow0 = P0 + ((ci_l * 20 + 2 * g + ky_l) * 2 + kxl_l) * PRUN;      // step 0: output row oy = g (step 1: + 16 runs)
-  const int prow8 = P0 + ((ci_l * 20 + 16 + ky_l) * 2 + kxl_l) * PRUN;         // step 2, g = 0: output row 8
-  const int aaddr = A_0 + l16 * AROW + g * 16;
-  f32x4 acc[2][2], acs[2][2];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) acc[mt][tt] = acs[mt][tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  // ---- conversion role: regular float4s r = tid + 512 j of the sample's a1 (columns 0..15 of every row: j < 3, the third only
-  // for tid < 256), edge float4s d = tid - 192 (columns 16..19 of row (ci, y) = (d / 20, d % 20): tid >= 192), dOut elements
-  // e = tid + 512 j (j < 6)
-  int rsrc[3], rdst[3];                                // float offset in the sample; byte offset of the par-0 dword in a set
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int r = min(tid + 512 * j, 1279), ci = r / 80, rem = r - ci * 80, y = rem >> 2, f = rem & 3;
-    rsrc[j] = (ci * 20 + y) * 20 + 4 * f;
-    rdst[j] = P0 + ((ci * 20 + y) * 2) * PRUN + 4 * f;
-  }
-  const bool edge = tid >= 192;
-  const int ed = edge ? tid - 192 : 0, eci = ed / 20, ey = ed - eci * 20;
-  const int esrc = (eci * 20 + ey) * 20 + 16, edst = P0 + ((eci * 20 + ey) * 2) * PRUN + 16;
-  f32x4 pa[3], pe;
-  float pd[6];
-  float wc[RANK ? 6 : 1][4], gl[4] = {0.f, 0.f, 0.f, 0.f};
-  unsigned int mbv[RANK ? 6 : 1];
-  float dbs[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (RANK) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j)
-#pragma unroll
-      for (int n = 0; n < 4; ++n) wc[RANK ? j : 0][n] = (tid + 512 * j < 2592 && n < p.nlog) ? p.Wc[(long)n * 2592 + tid + 512 * j] : 0.f;
-  }
-  auto load_raw = [&](long bn) {
-    const float* __restrict__ ga = p.in + bn * p.in_bs;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      if (j < 2 || tid < 256) pa[j] = *reinterpret_cast<const f32x4*>(ga + rsrc[j]);
-    if (edge) pe = *reinterpret_cast<const f32x4*>(ga + esrc);
-    if (RANK) {
-#pragma unroll
-      for (int n = 0; n < 4; ++n) gl[n] = n < p.nlog ? p.dl[bn * p.ldl + n] : 0.f;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) mbv[RANK ? j : 0] = p.a2b[bn * p.a2b_row + (min(tid + 512 * j, 2591) >> 3)];
-    } else {
-      const float* __restrict__ gd = p.dout + bn * 2592L;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) pd[j] = gd[min(tid + 512 * j, 2591)];
-    }
-  };
-  auto convert = [&](unsigned char* __restrict__ set) {
-    // a1: a float4 (x0 .. x0 + 3) is one dword of the parity-0 run (x0, x0 + 2) and one of the parity-1 run (x0 + 1, x0 + 3)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      if (j < 2 || tid < 256) {
-        unsigned int o0[3], o1[3];
-        wx_split2(pa[j][0], pa[j][2], o0);
-        wx_split2(pa[j][1], pa[j][3], o1);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          *reinterpret_cast<unsigned int*>(set + q * PQ + rdst[j]) = o0[q];
-          *reinterpret_cast<unsigned int*>(set + q * PQ + rdst[j] + PRUN) = o1[q];
-        }
-      }
-    }
-    if (edge) {      // columns 16..19 = taps kx 0..3 of the column ox = 8: also the column cells (oy <= 7) and the corner (oy = 8)
-      unsigned int o0[3], o1[3];
-      wx_split2(pe[0], pe[2], o0);
-      wx_split2(pe[1], pe[3], o1);
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        *reinterpret_cast<unsigned int*>(set + q * PQ + edst) = o0[q];
-        *reinterpret_cast<unsigned int*>(set + q * PQ + edst + PRUN) = o1[q];
-      }
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        const int ky = (ey & 1) + 2 * kh, dd = ey - ky, oy = dd >> 1;
-        if (dd >= 0 && oy <= 8) {
-          const int n0 = (eci * 4 + ky) * 4;
-#pragma unroll
-          for (int q = 0; q < 3; ++q) {
-            const unsigned short v0 = (unsigned short)(o0[q] & 0xffffu), v2 = (unsigned short)(o0[q] >> 16);
-            const unsigned short v1 = (unsigned short)(o1[q] & 0xffffu), v3 = (unsigned short)(o1[q] >> 16);
-            if (oy <= 7) {
-              unsigned short* c = reinterpret_cast<unsigned short*>(set + C2_0 + q * CQ + n0 * 16) + oy;
-              c[0] = v0; c[8] = v1; c[16] = v2; c[24] = v3;
-            } else {
-              unsigned short* x = reinterpret_cast<unsigned short*>(set + X2_0 + q * XQ + n0 * 4);
-              x[0] = v0; x[2] = v1; x[4] = v2; x[6] = v3;
-            }
-          }
-        }
-      }
-    }
-    // dOut: element e = (co, oy, ox) -> slot 8 oy + ox (ox < 8), 72 + oy (ox = 8, oy < 8), 80 (the corner)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const int e = tid + 512 * j;
-      float a;
-      if (RANK) {
-        a = 0.f;
-#pragma unroll
-        for (int n = 0; n < 4; ++n) a += gl[n] * wc[RANK ? j : 0][n];
-        if (!((mbv[RANK ? j : 0] >> (e & 7)) & 1u)) a = 0.f;
-      } else {
-        a = pd[j];
-      }
-      if (e < 2592) {
-        dbs[j] += a;
-        const int co = e / 81, px = e - co * 81, oy = px / 9, ox = px - oy * 9;
-        const int slot = ox < 8 ? 8 * oy + ox : (oy < 8 ? 72 + oy : 80);
-        const __bf16 h0 = (__bf16)a;
-        const float r1 = a - (float)h0;
-        const __bf16 h1 = (__bf16)r1;
-        const float r2 = r1 - (float)h1;
-        unsigned short* dst = reinterpret_cast<unsigned short*>(set + A_0 + co * AROW) + slot;
-        dst[0] = __builtin_bit_cast(unsigned short, h0);
-        dst[AQ / 2] = __builtin_bit_cast(unsigned short, h1);
-        dst[AQ] = __builtin_bit_cast(unsigned short, (__bf16)r2);
-      }
-    }
-  };
-  auto matrix = [&](const unsigned char* __restrict__ set) {
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      bf16x8x a[2][3], bf[2][3];
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-          a[mt][q] = *reinterpret_cast<const bf16x8x*>(set + aaddr + mt * 16 * AROW + s * 64 + q * AQ);
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          const unsigned int* pr = reinterpret_cast<const unsigned int*>(set + q * PQ + (s == 0 ? prow0 : s == 1 ? prow0 + 16 * PRUN : (g == 0 ? prow8 : prow0)));
-          const unsigned int d0 = pr[0], d1 = pr[1], d2 = pr[2], d3 = pr[3];
-          u32x4x v = (u32x4x){d0, d1, d2, d3};
-          if (tt == 1) {                                // kxh = 1: the run one element further
-            const unsigned int d4 = pr[4];
-            v = (u32x4x){__builtin_amdgcn_alignbit(d1, d0, 16), __builtin_amdgcn_alignbit(d2, d1, 16),
-                         __builtin_amdgcn_alignbit(d3, d2, 16), __builtin_amdgcn_alignbit(d4, d3, 16)};
-          }
-          if (s == 2) {                                 // lanes g = 1: the column cells, g = 2: the corner, g = 3: nothing
-            const u32x4x vc = *reinterpret_cast<const u32x4x*>(set + C2_0 + q * CQ + ncol[tt] * 16);
-            const unsigned int vx = *reinterpret_cast<const unsigned int*>(set + X2_0 + q * XQ + ncol[tt] * 4);
-            if (g == 1) v = vc;
-            else if (g == 2) v = (u32x4x){vx, 0u, 0u, 0u};
-            else if (g == 3) v = (u32x4x){0u, 0u, 0u, 0u};
-          }
-          bf[tt][q] = __builtin_bit_cast(bf16x8x, v);
-        }
-      }
-#define WXP_MM(AC, QA, QB)                                                                                              \
-      _Pragma("unroll") for (int mt = 0; mt < 2; ++mt)                                                                  \
-        _Pragma("unroll") for (int tt = 0; tt < 2; ++tt)                                                                \
-          AC[mt][tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mt][QA], bf[tt][QB], AC[mt][tt], 0, 0, 0);
-      WXP_MM(acs, 2, 0) WXP_MM(acs, 1, 1) WXP_MM(acs, 0, 2) WXP_MM(acs, 1, 0) WXP_MM(acs, 0, 1) WXP_MM(acc, 0, 0)
-#undef WXP_MM
-    }
-  };
-  long b = blockIdx.x;
-  if (b < p.B) {
-    __syncthreads();                                   // the zero fill
-    load_raw(b);
-    convert(ldsp);
-    if (b + gridDim.x < p.B) load_raw(b + gridDim.x);
-    __syncthreads();
-  }
-  int cur = 0;
-  for (; b < p.B; b += gridDim.x) {
-    const bool nxt = b + gridDim.x < p.B;
-    const long b2 = b + 2L * gridDim.x;
-    unsigned char* __restrict__ sc = ldsp + cur * SET;
-    unsigned char* __restrict__ sn = ldsp + (cur ^ 1) * SET;
-    const bool do_c = nxt && !(p.dbg & 1), do_l = b2 < p.B && !(p.dbg & 8), do_m = !(p.dbg & 4);
-    if (th == 0 || (p.dbg & 16)) {                     // (dbg 16: every wave multiplies first -- the in-phase order, for timing)
-      if (do_m) matrix(sc);
-      if (do_c) convert(sn);
-      if (nxt && do_l) load_raw(b2);
-    } else {
-      if (do_c) convert(sn);
-      if (nxt && do_l) load_raw(b2);
-      if (do_m) matrix(sc);
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  // partials: D row (co) = mt * 16 + 4 g + r, column = this lane's weight column of tile tt
-  float* sl = p.slab + (long)blockIdx.x * (32 * 256 + 32);
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sl[(mt * 16 + 4 * g + r) * 256 + ncol[tt]] = acc[mt][tt][r] + acs[mt][tt][r];
-  float* red = reinterpret_cast<float*>(ldsp);          // [e 3072]: this workgroup's sum over its samples of dOut element e
-#pragma unroll
-  for (int j = 0; j < 6; ++j) red[tid + 512 * j] = dbs[j];
-  __syncthreads();
-  if (tid < 32) {
-    float sdb = 0.f;
-    for (int i = 0; i < 81; ++i) sdb += red[tid * 81 + i];
     sl[32 * 256 + tid] = sdb;
   }
 }
@@ -3625,7 +3231,7 @@ __global__ __launch_bounds__(ST_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 //       group at tap column kx = 4 kxh + kxl are the 8 CONSECUTIVE elements m = c0 + kxh .. of one phase-plane row (two
 //       ds_read_b64 + one b32; kxh = 1 shifts by one element with v_alignbit) -- no gather, no conversion in the loop;
 //   wave (q, h): input plane ci = q (64 weight columns = 4 accumulator tiles kxl), K blocks of parity half h.
-struct WsbGeo { int NG, NGT, NB, PA, PP, PLS, SK, dbg; };      // PLS: elements per phase plane, SK: skew per 4 rows      // dbg (A2C_WSB_DBG, timing only): 1 = no matrix phase, 2 = no commit
+struct WsbGeo { int NG, NGT, NB, PA, PP, PLS, SK, no_ring; };  // PLS: elements per phase plane, SK: skew per 4 rows; no_ring: A2C_WSB_NO_RING
 //   wave w: K blocks {w, w + 8, ...} (a block = 4 pixel groups = 32 pixels) for ALL 256 weight columns -- 16 accumulator
 //   tiles, the block's three A fragments read once --; tile t = (ci, kxh, kp): lane j = (ky = j >> 1, kxl = 2 kp + (j & 1)),
 //   so kxh is uniform per tile and only the kxh = 1 tiles pay the one-element shift; the eight waves' partial tiles are
@@ -3708,13 +3314,11 @@ __global__ __launch_bounds__(ST_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   // Samples in CONTIGUOUS runs per workgroup (round 6; was n = blockIdx.x + k * gridDim.x): sample n + 1 of a slot shares
   // three of its four frames with sample n, so the workgroup that just fetched them finds them in its XCD's L2 -- with the
   // strided deal the four samples that share a frame ran on four different XCDs and every frame crossed the fabric four times
-  // (PMC: 1.77 GB per launch against 1.07 GB of frames + dOut).  A2C_WSB_STRIDED=1 (gq.dbg bit 2) keeps the strided deal.
-  const bool strided = (gq.dbg & 4) != 0;
-  const bool ring_off = strided || (gq.dbg & 8) != 0;          // A2C_WSB_NO_RING=1: every sample loaded and committed whole
+  // (PMC: 1.77 GB per launch against 1.07 GB of frames + dOut).  The strided deal was removed; it is at commit 15c35e9.
+  const bool ring_off = gq.no_ring != 0;                      // A2C_WSB_NO_RING=1: every sample loaded and committed whole
   const long chunk = (p.B + gridDim.x - 1) / gridDim.x;
-  const long nstep = strided ? (long)gridDim.x : 1L;
-  long n = strided ? (long)blockIdx.x : (long)blockIdx.x * chunk;
-  const long n_end = strided ? (long)p.B : (n + chunk < (long)p.B ? n + chunk : (long)p.B);
+  long n = (long)blockIdx.x * chunk;
+  const long n_end = n + chunk < (long)p.B ? n + chunk : (long)p.B;
 #define WSB_LDU(var, u, src)                                                                                   \
   {                                                                                                            \
     const unsigned int* s_ = reinterpret_cast<const unsigned int*>((src) + soff[u]);                            \
@@ -3722,7 +3326,7 @@ __global__ __launch_bounds__(ST_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     var.y = s_[(smask[u] >> 8) ? 1 : 0];                                                                       \
   }
   // dOut rows are prefetched TWO samples ahead (two register sets d / e, the loop unrolled twice), the frames one: stamps of
-  // the one-deep version (A2C_WSB_DBG=1/2/3, tools/a3c_wgrad_bench.py) -- loads alone 0.27 ms, + matrix 0.18, + commit 0.15 =
+  // the one-deep version (phases switched off one at a time, timing builds only) -- loads alone 0.27 ms, + matrix 0.18, + commit 0.15 =
   // the whole kernel: a load issued at the head of a 1.4 us matrix phase comes back after ~3.5 us under this kernel's own
   // bursts, so every sample waited ~2 us for its dOut.  (The frames of sample n + 1 are mostly L2 hits since the contiguous
   // deal: one sample of lookahead covers them.)
@@ -3785,7 +3389,7 @@ __global__ __launch_bounds__(ST_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     d_[3 * ps_] = __builtin_amdgcn_perm(__float_as_uint((float)(x1_ >> 24)), __float_as_uint((float)(x0_ >> 24)), 0x07060302u); \
   }
   auto matrix = [&]() {
-    for (int b = (gq.dbg & 1) ? NB : w; b < NB; b += ST_NT / 64) {
+    for (int b = w; b < NB; b += ST_NT / 64) {
       const int grp = 4 * b + g;
       const unsigned short* __restrict__ ap = A + j * PA + grp * 8;
       const bf16x8w ah = *reinterpret_cast<const bf16x8w*>(ap);
@@ -3838,18 +3442,16 @@ __global__ __launch_bounds__(ST_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   // the sample two steps on into the set just freed and the frames of the next sample; past the end: re-read this sample
 #define WSB_ITER(N_, D0, D1, D2, D3)                                                                           \
   {                                                                                                            \
-    const long n2_ = ((N_) + 2 * nstep < n_end) ? (N_) + 2 * nstep : (N_);                                     \
-    const long n1_ = ((N_) + nstep < n_end) ? (N_) + nstep : (N_);                                             \
+    const long n2_ = ((N_) + 2 < n_end) ? (N_) + 2 : (N_);                                                     \
+    const long n1_ = ((N_) + 1 < n_end) ? (N_) + 1 : (N_);                                                     \
     __syncthreads();                                 /* everyone is done with the previous sample (and the zero fill) */ \
     if (inc_cur) rot = (rot + 1) & 3; else rot = 0;                                                            \
     pofs0 = rot * 4 * PLS; pofs1 = ((rot + 1) & 3) * 4 * PLS; pofs2 = ((rot + 2) & 3) * 4 * PLS; pofs3 = ((rot + 3) & 3) * 4 * PLS; \
-    if (!(gq.dbg & 2)) {                                                                                       \
-      WSB_STD(D0, 0) WSB_STD(D1, 1) WSB_STD(D2, 2) WSB_STD(D3, 3)                                              \
-      if (inc_cur) {                                                                                           \
-        WSB_STU2(g0, 0, pofs3) WSB_STU2(g1, 1, pofs3)                                                          \
-      } else {                                                                                                 \
-        WSB_STU(g0, 0) WSB_STU(g1, 1) WSB_STU(g2, 2) WSB_STU(g3, 3) WSB_STU(g4, 4) WSB_STU(g5, 5) WSB_STU(g6, 6) WSB_STU(g7, 7) \
-      }                                                                                                        \
+    WSB_STD(D0, 0) WSB_STD(D1, 1) WSB_STD(D2, 2) WSB_STD(D3, 3)                                                \
+    if (inc_cur) {                                                                                             \
+      WSB_STU2(g0, 0, pofs3) WSB_STU2(g1, 1, pofs3)                                                            \
+    } else {                                                                                                   \
+      WSB_STU(g0, 0) WSB_STU(g1, 1) WSB_STU(g2, 2) WSB_STU(g3, 3) WSB_STU(g4, 4) WSB_STU(g5, 5) WSB_STU(g6, 6) WSB_STU(g7, 7) \
     }                                                                                                          \
     __syncthreads();                                                                                           \
     /* frames FIRST: loads retire in order, and the next commit needs them before this dOut */                 \
@@ -3864,16 +3466,16 @@ __global__ __launch_bounds__(ST_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
   bool inc_cur = false;                              // the sample about to be committed continues the one in LDS
   int nv1 = 4;
   if (n < n_end) {
-    const long n1 = (n + nstep < n_end) ? n + nstep : n;
+    const long n1 = (n + 1 < n_end) ? n + 1 : n;
     WSB_LOADD(n, d0, d1, d2, d3)
     nv = p.nvalid[n];
     WSB_LOADG(n, false)
     nv1 = p.nvalid[n1];
     WSB_LOADD(n1, e0, e1, e2, e3)
   }
-  for (; n < n_end; n += 2 * nstep) {
+  for (; n < n_end; n += 2) {
     WSB_ITER(n, d0, d1, d2, d3)
-    if (n + nstep < n_end) WSB_ITER(n + nstep, e0, e1, e2, e3)
+    if (n + 1 < n_end) WSB_ITER(n + 1, e0, e1, e2, e3)
   }
 #undef WSB_ITER
 #undef WSB_STU2
@@ -3920,9 +3522,7 @@ __global__ __launch_bounds__(ST_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 
 static bool plan_wstream_bf16(const a2c_conv_desc* d, const WstreamP& p, WsbGeo& gq, size_t& lds) {
   gq.NG = (d->OW + 7) / 8;
-  gq.dbg = getenv("A2C_WSB_DBG") ? atoi(getenv("A2C_WSB_DBG")) & 3 : 0;
-  { const char* sd = getenv("A2C_WSB_STRIDED"); if (sd && sd[0] == '1') gq.dbg |= 4; }
-  { const char* sd = getenv("A2C_WSB_NO_RING"); if (sd && sd[0] == '1') gq.dbg |= 8; }
+  gq.no_ring = a2c_env_on("A2C_WSB_NO_RING");
   gq.NGT = d->OH * gq.NG;
   gq.NB = (gq.NGT + 3) / 4;
   const int need_dw = gq.NB * 16;                      // dwords of one channel's groups (8 bf16 = 4 dwords each)
@@ -4009,7 +3609,7 @@ static const void* wgrad_fn(const WgradPlan& pl) {
 
 // which wgrad_run_kernel instantiation (if any) fits the layer: 1 = <1,4,1,5>, 2 = <2,2,2,3>
 static int wgrad_run_variant(const a2c_conv_desc* d) {
-  if (!run_layout(d) || getenv("A2C_NO_PF")) return 0;
+  if (!run_layout(d)) return 0;
   const int mt = ceil_div(d->Cout, 16), c4n = ceil_div(d->OW, 4), rgs = d->Cin * d->ks * 2 / 16;
   if (d->stride == 4 && mt == 1 && rgs == 4 && c4n == 5) return 1;
   if (d->stride == 2 && mt == 2 && rgs == 8 && c4n == 3) return 2;
@@ -4054,9 +3654,8 @@ static bool plan_wgrad(const a2c_conv_desc* d, int B, WgradPlan& pl, bool allow_
   const int nkt = ceil_div(d->Cin * d->ks * d->ks, 16);
   const int ktw = ceil_div(nkt, 4);
   pl.rs = 0;
-  const bool rs_ok = !getenv("A2C_NO_WGRAD_RS");
-  if (rs_ok && mt == 1 && nkt == 3) { pl.MT = 1; pl.KTW = 3; pl.rs = 1; }          // exact: every k-tile is real
-  else if (rs_ok && mt == 2 && nkt == 9) { pl.MT = 2; pl.KTW = 9; pl.rs = 1; }
+  if (mt == 1 && nkt == 3) { pl.MT = 1; pl.KTW = 3; pl.rs = 1; }          // exact: every k-tile is real
+  else if (mt == 2 && nkt == 9) { pl.MT = 2; pl.KTW = 9; pl.rs = 1; }
   else if (mt == 1 && ktw <= 1) { pl.MT = 1; pl.KTW = 1; }
   else if (mt == 1 && ktw <= 4) { pl.MT = 1; pl.KTW = 4; }
   else if (mt <= 2 && ktw <= 4) { pl.MT = 2; pl.KTW = 4; }
@@ -4066,16 +3665,16 @@ static bool plan_wgrad(const a2c_conv_desc* d, int B, WgradPlan& pl, bool allow_
   pl.ex = (ktw == pl.KTW) ? 1 : 0;
   // dOut tile floats per pixel row: MT*16 planes * OWp (+ plane padding, fixed)
   plan_src(t, pl.MT * 16 * pl.OWp, pl.MT * 16 * 34, WGRAD_LDS_BUDGET);
-  if (t.tiles > 1 && !getenv("A2C_WGRAD_LDS_KB")) {     // a small plane: the whole sample as ONE tile beats two uneven ones
+  if (t.tiles > 1) {     // a small plane: the whole sample as ONE tile beats two uneven ones
     SrcTile t1 = t;
     plan_src(t1, pl.MT * 16 * pl.OWp, pl.MT * 16 * 34, 128 * 1024);     // (whole samples are staged as float4 runs)
     if (t1.tiles == 1) t = t1;
   }
   pl.pf = 0;
-  if (allow_run && !getenv("A2C_NO_WGRAD_PF") && d->W % 4 == 0 && d->OW % 2 == 0) {
+  if (allow_run && d->W % 4 == 0 && d->OW % 2 == 0) {
     const int ni = (pl.rs && pl.KTW == 3) ? 4 : (pl.rs && pl.KTW == 9) ? 8 : (!pl.rs && pl.MT == 2 && pl.KTW == 4 && pl.ex) ? 12 : 0;
     const int nd = (pl.rs && pl.KTW == 3) ? 16 : 8;
-    const long budget = env_kb("A2C_WGRAD_PF_LDS_KB", 64);
+    const long budget = 64 * 1024;
     int tph = 0;
     for (int c = 1; c <= d->OH && ni; ++c) {      // largest band whose loads fit the prefetch registers
       const int tih = (c - 1) * d->stride + d->ks;
@@ -4090,10 +3689,10 @@ static bool plan_wgrad(const a2c_conv_desc* d, int B, WgradPlan& pl, bool allow_
       t.tiles = ceil_div(t.PH, t.TPH);
     }
   }
-  if (!pl.pf && allow_run && !getenv("A2C_NO_WGRAD_PF") && !getenv("A2C_NO_WGRAD_PF2") && d->W % 4 && d->W % 2 == 0 && pl.ex &&
+  if (!pl.pf && allow_run && d->W % 4 && d->W % 2 == 0 && pl.ex &&
       !pl.rs && pl.MT == 2 && pl.KTW == 4) {
     // narrow layers: 8-B input slots, 4-B dOut slots (WGRAD_PF_D / _E)
-    const long budget = env_kb("A2C_WGRAD_PF_LDS_KB", 64);
+    const long budget = 64 * 1024;
     int tph = 0;
     for (int c = 1; c <= d->OH; ++c) {
       const int tih = (c - 1) * d->stride + d->ks;
@@ -4173,8 +3772,7 @@ static int conv_fwd_impl(const a2c_conv_desc* d, const float* in, int64_t in_bst
   SrcTile t;
   t.Cp = d->Cin; t.IH = d->H; t.IW = d->W; t.SY = d->stride; t.SX = d->stride;
   t.sy0 = -d->pad; t.sx0 = -d->pad; t.span_y = d->ks; t.span_x = d->ks; t.PH = d->OH; t.PW = d->OW;
-  const bool staged_out = !getenv("A2C_NO_OUT_STAGE");
-  plan_src(t, staged_out ? d->Cout * d->OW : 0, 16, fwd_kb > 0 ? fwd_kb * 1024 : IGEMM_LDS_BUDGET);
+  plan_src(t, d->Cout * d->OW, 16, fwd_kb > 0 ? fwd_kb * 1024 : IGEMM_LDS_BUDGET);
   IgemmP p;
   fill_stage(p.st, t, in, in_bstride);
   p.out_stage = 0; p.out_vec = 0;
@@ -4191,11 +3789,10 @@ static int conv_fwd_impl(const a2c_conv_desc* d, const float* in, int64_t in_bst
   {  // streaming kernel: A3C conv1 class at large batch
     StreamP sp;
     const int n_cu = stream_grid();
-    if (B >= 8 * n_cu && !getenv("A2C_NO_STREAM") && !getenv("A2C_NO_PF") && in_bstride % 4 == 0 && out_bstride % 4 == 0 &&
+    if (B >= 8 * n_cu && !a2c_env_on("A2C_NO_STREAM") && in_bstride % 4 == 0 && out_bstride % 4 == 0 &&
         ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0) && plan_stream(d, sp)) {
       sp.in = in; sp.in_bs = in_bstride; sp.wfrag = wprep_fwd; sp.bias = bias; sp.out = out; sp.out_bs = out_bstride;
       sp.B = B; sp.relu = relu;
-      { const char* e = getenv("A2C_STREAM_DBG"); sp.dbg = e ? atoi(e) : 0; }
       const size_t lds = stream_lds(sp);
       static bool attr = false;
       if (!attr) {
@@ -4210,7 +3807,7 @@ static int conv_fwd_impl(const a2c_conv_desc* d, const float* in, int64_t in_bst
   }
   {  // streaming kernel: A3C conv2 class at large batch
     Stream2P sp;
-    if (B >= 16 * stream_grid() && !getenv("A2C_NO_STREAM") && !getenv("A2C_NO_PF") && in_bstride % 4 == 0 && out_bstride % 4 == 0 &&
+    if (B >= 16 * stream_grid() && !a2c_env_on("A2C_NO_STREAM") && in_bstride % 4 == 0 && out_bstride % 4 == 0 &&
         ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0) && plan_stream2(d, sp)) {
       sp.in = in; sp.in_bs = in_bstride; sp.wfrag = wprep_fwd; sp.bias = bias; sp.out = out; sp.out_bs = out_bstride;
       sp.B = B; sp.relu = relu;
@@ -4223,7 +3820,7 @@ static int conv_fwd_impl(const a2c_conv_desc* d, const float* in, int64_t in_bst
     }
   }
   const bool run = run_layout(d);
-  if (run && in_bstride % 4 == 0 && ((uintptr_t)in % 16 == 0) && nfrag * 4 <= 32 * 1024 && !getenv("A2C_NO_PF")) {
+  if (run && in_bstride % 4 == 0 && ((uintptr_t)in % 16 == 0) && nfrag * 4 <= 32 * 1024) {
     // largest band whose image fits the prefetch registers; prefer bands whose pixel count fills
     // whole 32-pixel pairs
     int tph = 0;
@@ -4262,7 +3859,7 @@ static int conv_fwd_impl(const a2c_conv_desc* d, const float* in, int64_t in_bst
     }
   }
   const bool run3 = run3_layout(d);
-  if (run3 && in_bstride % 4 == 0 && ((uintptr_t)in % 16 == 0) && !getenv("A2C_NO_PF") && !getenv("A2C_NO_RUN3")) {
+  if (run3 && in_bstride % 4 == 0 && ((uintptr_t)in % 16 == 0)) {
     const int S = d->stride;
     const bool ovec = (d->OW % 4 == 0) && (out_bstride % 4 == 0) && (((long)d->OH * d->OW) % 4 == 0) && ((uintptr_t)out % 16 == 0);
     const long budget = fwd_kb > 0 ? fwd_kb * 1024L : (long)env_kb("A2C_RUN3_LDS_KB", 80);
@@ -4304,11 +3901,11 @@ static int conv_fwd_impl(const a2c_conv_desc* d, const float* in, int64_t in_bst
       return A2C_OK;
     }
   }
-  if (staged_out) {            // generic kernel: output tile assembled in LDS, flushed coalesced
+  {                            // generic kernel: output tile assembled in LDS, flushed coalesced
     p.out_stage = t.Cp * t.PLANE + 64;
     p.out_vec = (d->OW % 4 == 0) && (out_bstride % 4 == 0) && (((long)d->OH * d->OW) % 4 == 0) && ((uintptr_t)out % 16 == 0);
     if (!p.out_vec && t.tiles == 1 && t.TPH == d->OH && out_bstride % 4 == 0 && ((long)d->Cout * d->OH * d->OW) % 4 == 0 &&
-        ((uintptr_t)out % 16 == 0) && (p.out_stage % 4 == 0) && !getenv("A2C_NO_FLAT_STAGE"))
+        ((uintptr_t)out % 16 == 0) && (p.out_stage % 4 == 0))
       p.out_vec = 2;
   }
   if (run || run3) {   // generic kernel on a run-ordered layer: steps walk (c4, ky, kx)
@@ -4329,7 +3926,7 @@ static int conv_fwd_tuned(const a2c_conv_desc* d, const float* in, int64_t in_bs
   static std::mutex mu;
   static std::map<BandKey, int> cache;
   const long work = (long)B * d->Cout * d->OH * d->OW;
-  if (getenv("A2C_NO_TUNE") || getenv("A2C_IGEMM_LDS_KB") || getenv("A2C_RUN3_LDS_KB") || work < (1L << 16))
+  if (a2c_env_on("A2C_NO_TUNE") || env_kb("A2C_IGEMM_LDS_KB", 0) || env_kb("A2C_RUN3_LDS_KB", 0) || work < (1L << 16))
     return conv_fwd_impl(d, in, in_bstride, wprep_fwd, bias, relu, out, out_bstride, B, 0, stream);
   const BandKey key = {{d->Cin, d->H, d->W, d->Cout, d->ks, d->stride, d->pad, B, (int)(in_bstride % 4 == 0) | ((int)(out_bstride % 4 == 0) << 1)}};
   hipStream_t st = a2c_s(stream);
@@ -4353,7 +3950,6 @@ static int conv_fwd_tuned(const a2c_conv_desc* d, const float* in, int64_t in_bs
     (void)hipEventRecord(e1, st);
     float ms = 0.f;
     if (rc != A2C_OK || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) continue;
-    if (getenv("A2C_TUNE_LOG")) fprintf(stderr, "a2c fwd tune (%d,%d,%d)->%d s%d B=%d: budget %d KB %.4f ms\n", d->Cin, d->H, d->W, d->Cout, d->stride, B, c, ms / reps);
     if (best_ms < 0.f || ms < 0.97f * best_ms) { best = c; best_ms = ms; }      // later candidates must win by 3 %
   }
   (void)hipEventDestroy(e0);
@@ -4466,7 +4062,7 @@ static bool band_setup(const a2c_conv_desc* d, const float* dout, const float* w
   q.st.TIH = TIH; q.st.WP = WPo; q.st.PLANE = PLANEo; q.st.sx0 = ox_lo; q.st.fast = 0;
   // one band = the whole sample (TY == H): dOut is staged and dX flushed as contiguous float4 runs (bwd_band_kernel)
   q.st.flat = (TY == d->H && q.st.vec != 4 && ((long)d->Cout * d->OH * d->OW) % 4 == 0 && ((long)d->Cin * d->H * d->W) % 4 == 0 &&
-               ((uintptr_t)dout % 16 == 0) && !getenv("A2C_NO_FLAT_STAGE")) ? 1 : 0;
+               ((uintptr_t)dout % 16 == 0)) ? 1 : 0;
   q.st.vec = stage_vec(dout, q.st.bstride, d->OH, d->OW);
   for (int cls = 0; cls < S * S; ++cls) {
     const int ry = cls / S, rx = cls % S;
@@ -4499,7 +4095,7 @@ static int launch_bwd_band(const a2c_conv_desc* d, const float* dout, const floa
     const int vecs = q.st.vec;
     const long tot_v = (long)d->Cout * TIH * (d->OW / vecs);
     const size_t lds2 = 4 * (nfrag + (size_t)q.out_floats + (size_t)d->Cout * PLANEo + 64);
-    if (!getenv("A2C_NO_BAND2") && nfrag * 4 <= 64 * 1024 && d->OW % vecs == 0 && tot_v <= 256L * PFB2_MAX && MTb == 1 &&
+    if (nfrag * 4 <= 64 * 1024 && d->OW % vecs == 0 && tot_v <= 256L * PFB2_MAX && MTb == 1 &&
         c4n % 2 == 0 && lds2 <= LDS_HARD_MAX) {      // MTb > 1 measured slower: fragments + band leave one workgroup per CU
       BwdBand2P q2;
       q2.b = q; q2.nfrag = (int)nfrag;
@@ -4526,7 +4122,7 @@ static int launch_bwd_band(const a2c_conv_desc* d, const float* dout, const floa
   // whole-sample bands that leave ONE workgroup per CU: the input channels in groups of 16, one workgroup each, when two
   // of those fit a CU (GRUModel conv4 backward-data, 32 <- 48 @21: 96 KB -> 2 x 68 KB)
   if (q.st.flat && q.bands == 1 && MTb >= 2 && MTb <= 4 && lds > 80 * 1024 && d->Cin % 16 == 0 && (16 * d->H * d->W) % 4 == 0 &&
-      !getenv("A2C_NO_BAND_GROUPS")) {
+      !a2c_env_on("A2C_NO_BAND_GROUPS")) {
     const size_t lds1 = 4 * ((size_t)16 * TY * d->W + (size_t)d->Cout * PLANEo + 64);
     if (lds1 <= 80 * 1024) {
       q.mgroups = MTb; MTk = 1; q.out_floats = 16 * TY * d->W; lds = lds1;
@@ -4561,8 +4157,7 @@ static bool plan_band_w1(const a2c_conv_desc* d2, const a2c_conv_desc* d1, int B
   // N = 32 768: 21.7 vs 11.4 + 6.9 ms; ConvModel at N = 2 048: 3.0-4.1 vs 2.35 + 0.47 ms) although it moves 43 % fewer
   // bytes: with the input-row prefetch, the k offsets and the extra accumulators it needs 250-300 VGPRs (one workgroup
   // per CU), and the extra per-band phases (mask in place, barrier, bias partials, 3-MFMA steps) are latency-bound.
-  const char* on = getenv("A2C_FUSE_W1");
-  if (!on || on[0] != '1' || !desc_ok(d2) || !desc_ok(d1) || getenv("A2C_NO_BAND2")) return false;
+  if (!a2c_env_on("A2C_FUSE_W1") || !desc_ok(d2) || !desc_ok(d1)) return false;
   if (d1->ks != 3 || d1->stride != 1 || d1->pad != 1 || d1->Cout != d2->Cin || d1->OH != d2->H || d1->OW != d2->W) return false;
   if (d2->Cin > 16 || d1->Cin * 9 > 48 || d2->W % 4 || d2->stride * d2->stride > MAX_CLS || (d2->Cout / 4) % 2) return false;
   const size_t nfrag = a2c_conv2d_prep_floats(d2, 1);
@@ -4580,7 +4175,7 @@ static bool plan_band_w1(const a2c_conv_desc* d2, const a2c_conv_desc* d1, int B
     const long planex = ((tihx * wpx + 31) / 32) * 32 + 16;
     const long lds = 4L * ((long)nfrag + q.out_floats + (long)d2->Cout * PLANEo + 64 + d1->Cin * planex + 64);
     if (tot_v > 256L * PFB2_MAX || (long)d2->Cin * ty * d2->W > 256L * PFM2_W1 * 4 ||
-        (long)d1->Cin * tihx * (d2->W / 4) > 256L * NIX || tihx > 255 || lds > env_kb("A2C_W1_LDS_KB", 80)) break;
+        (long)d1->Cin * tihx * (d2->W / 4) > 256L * NIX || tihx > 255 || lds > 80 * 1024) break;
     best = ty;
   }
   if (!best) return false;
@@ -4623,9 +4218,10 @@ static int bwd_band_tuned(const a2c_conv_desc* d, const float* dout, const float
                           float* din, int B, a2c_stream_t stream) {
   static std::mutex mu;
   static std::map<BandKey, int> cache;
-  if (getenv("A2C_BAND_TY")) return launch_bwd_band(d, dout, wprep_bwd, mask, din, B, atoi(getenv("A2C_BAND_TY")), stream);
+  const int ty_env = a2c_env_int("A2C_BAND_TY", -1);
+  if (ty_env >= 0) return launch_bwd_band(d, dout, wprep_bwd, mask, din, B, ty_env, stream);
   const long work = (long)B * d->Cin * d->H * d->W;
-  if (getenv("A2C_NO_TUNE") || work < (1L << 24)) return launch_bwd_band(d, dout, wprep_bwd, mask, din, B, 0, stream);
+  if (a2c_env_on("A2C_NO_TUNE") || work < (1L << 24)) return launch_bwd_band(d, dout, wprep_bwd, mask, din, B, 0, stream);
   const BandKey key = {{d->Cin, d->H, d->W, d->Cout, d->ks, d->stride, d->pad, B, mask ? 1 : 0}};
   hipStream_t st = a2c_s(stream);
   {
@@ -4649,7 +4245,6 @@ static int bwd_band_tuned(const a2c_conv_desc* d, const float* dout, const float
       (void)hipEventRecord(e1, st);
       float ms = 0.f;
       if (rc != A2C_OK || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) continue;
-      if (getenv("A2C_TUNE_LOG")) fprintf(stderr, "a2c band tune (%d,%d,%d)<-%d s%d B=%d: TY %d %.3f ms\n", d->Cin, d->H, d->W, d->Cout, S, B, ty, ms);
       if (best == 0 || ms < best_ms) { best = ty; best_ms = ms; }
     }
     (void)hipEventDestroy(e0);
@@ -4713,7 +4308,7 @@ int a2c_conv2d_bwd_data_lanemask(const a2c_conv_desc* d, const float* dout, cons
 /* include/a2c_mi355x.h: the two backward passes of the layer below a rank-n_logits head with dOut formed in the kernels */
 int a2c_conv2d_bwd_rank_supported(const a2c_conv_desc* d, int n_logits, int B) {
   if (!desc_ok(d) || B < 1 || n_logits < 1 || n_logits > 4 || (d->Cin * d->H * d->W) % 256 || c3_supported(d, 1)) return 0;
-  { const char* e = getenv("A2C_WGRAD_X6"); if (e && e[0] == '0') return 0; }
+  if (a2c_env_int("A2C_WGRAD_X6", 1) == 0) return 0;
   static const unsigned long long probe = 0;
   static const RankSrc rprobe = {(const float*)16, 4, 1, (const float*)16, (const unsigned char*)16, 324};
   if (conv_bwd_data_generic(d, (const float*)16, (const float*)16, nullptr, (float*)16, B, nullptr, &probe, true, &rprobe) != A2C_OK) return 0;
@@ -4775,7 +4370,7 @@ int conv_bwd_data_generic(const a2c_conv_desc* d, const float* dout, const float
     const int nel = d->Cout * d->OH * d->OW;
     if (run_layout(d) && S * S <= MAX_CLS && MTb <= 2 && nel <= 256 * 4 * PF_B && (4 * c4n) % CH == 0 &&
         nfrag * 4 <= 48 * 1024 && ((uintptr_t)dout % 16 == 0) && ((uintptr_t)din % 16 == 0) &&
-        (!mask || (uintptr_t)mask % 16 == 0) && (d->H * d->W) % 4 == 0 && !getenv("A2C_NO_PF")) {
+        (!mask || (uintptr_t)mask % 16 == 0) && (d->H * d->W) % 4 == 0) {
       BwdFusedP q;
       q.dout = dout; q.din = din; q.mask = mask; q.wfrag = wprep_bwd;
       q.Cout = d->Cout; q.OH = d->OH; q.OW = d->OW; q.Cin = d->Cin; q.H = d->H; q.W = d->W; q.S = S; q.B = B;
@@ -4792,23 +4387,21 @@ int conv_bwd_data_generic(const a2c_conv_desc* d, const float* dout, const float
         q.cls[cls].oy_add = ry; q.cls[cls].ox_add = rx;
       }
       if (S == 2 && d->ks == 4 && MTb == 1 && c4n == 8 && nel % 4 == 0 && nel <= BS_PD * BS_NT * 4 &&
-          d->Cin * d->H * d->W <= BS_PM * BS_NT * 4 && B >= 8 * stream_grid() && !getenv("A2C_NO_STREAM")) {
+          d->Cin * d->H * d->W <= BS_PM * BS_NT * 4 && B >= 8 * stream_grid() && !a2c_env_on("A2C_NO_STREAM")) {
         BstreamP sp;
         sp.dout = dout; sp.din = din; sp.mask = mask; sp.wfrag = wprep_bwd;
         sp.Cout = d->Cout; sp.OH = d->OH; sp.OW = d->OW; sp.Cin = d->Cin; sp.H = d->H; sp.W = d->W; sp.B = B;
         sp.WP = q.WP; sp.PLANE = q.PLANE; sp.off0 = q.off0; sp.step_a = q.step_a; sp.step_b = q.step_b; sp.step_c = q.step_c;
         for (int cls = 0; cls < 4; ++cls) sp.cls[cls] = q.cls[cls];
         const int n4 = d->Cin * d->H * d->W / 4;
-        // second form (two dX images, flush under the next sample's matrix phase, lane masks): A2C_BWD_STREAM_V1=1 keeps the first
+        // bwd_stream2_kernel (two dX images, flush under the next sample's matrix phase, lane masks).  The gate above bounds its
+        // LDS: nel <= 3072 and Cin * H * W <= 8192 floats give at most 107 KB.
         const size_t slds2 = 4 * ((size_t)d->Cout * q.PLANE + 64 + 2 * (size_t)d->Cin * d->H * d->W);
-        const char* v1 = getenv("A2C_BWD_STREAM_V1");
-        const bool form2 = slds2 <= LDS_HARD_MAX && !(v1 && v1[0] == '1') && (!lmask || n4 % 64 == 0);
-        if (lmask && !form2) return A2C_ERR_ARG;
+        if (slds2 > LDS_HARD_MAX || (lmask && n4 % 64)) return A2C_ERR_ARG;
         if (probe_only && !rank) return A2C_OK;
         {  // the bf16 x 6 form (bwd_x6_kernel): exactly A3CModel's conv2, mask as bits or none; A2C_BWD_X6=0 keeps the fp32 MFMA kernels
-          const char* x6 = getenv("A2C_BWD_X6");
           if (d->Cout == 32 && d->Cin == 16 && d->OH == 9 && d->OW == 9 && d->H == 20 && d->W == 20 && P == 0 && (lmask || !mask) &&
-              !(x6 && x6[0] == '0')) {
+              a2c_env_int("A2C_BWD_X6", 1) != 0) {
             if (probe_only) return A2C_OK;
             BwdX6P xp;
             xp.dout = dout; xp.din = din; xp.wfrag = wprep_bwd; xp.lmask = lmask; xp.lmw = n4 / 64 * 4; xp.B = B;
@@ -4827,42 +4420,15 @@ int conv_bwd_data_generic(const a2c_conv_desc* d, const float* dout, const float
           }
         }
         if (rank) return A2C_ERR_ARG;
-        // third form (one barrier per sample, both images double buffered, the two waves of a SIMD out of step): A2C_BWD_STREAM_FORM=3
-        const size_t slds3 = 4 * (2 * ((size_t)d->Cout * q.PLANE + 64) + 2 * (size_t)d->Cin * d->H * d->W);
-        const char* fm = getenv("A2C_BWD_STREAM_FORM");
-        if (form2 && slds3 <= LDS_HARD_MAX && fm && fm[0] == '3') {        // OPT-IN: measured slower (0.855-0.913 vs 0.74 ms)
-          Bstream2P s3;
-          s3.s = sp; s3.lmask = lmask; s3.lmw = n4 / 64 * 4;
-          { const char* o = getenv("A2C_BS3_ORDER"); s3.order = o ? atoi(o) : 0; }
-          s3.dbg = nullptr;
-          const void* sk = lmask ? (const void*)bwd_stream3_kernel<2> : mask ? (const void*)bwd_stream3_kernel<1> : (const void*)bwd_stream3_kernel<0>;
-          if (slds3 > 64 * 1024) (void)hipFuncSetAttribute(sk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds3);
-          const int sgrid = resident_grid(sk, slds3, B, BS_NT);
-          if (lmask) hipLaunchKernelGGL(bwd_stream3_kernel<2>, dim3(sgrid), dim3(BS_NT), slds3, a2c_s(stream), s3);
-          else if (mask) hipLaunchKernelGGL(bwd_stream3_kernel<1>, dim3(sgrid), dim3(BS_NT), slds3, a2c_s(stream), s3);
-          else hipLaunchKernelGGL(bwd_stream3_kernel<0>, dim3(sgrid), dim3(BS_NT), slds3, a2c_s(stream), s3);
-          A2C_CHECK_LAUNCH();
-          return A2C_OK;
-        }
-        if (form2) {
-          Bstream2P s2;
-          s2.s = sp; s2.lmask = lmask; s2.lmw = n4 / 64 * 4; s2.order = 0; s2.dbg = g_bs2_dbg;
-          const void* sk = lmask ? (const void*)bwd_stream2_kernel<2> : mask ? (const void*)bwd_stream2_kernel<1> : (const void*)bwd_stream2_kernel<0>;
-          if (slds2 > 64 * 1024) (void)hipFuncSetAttribute(sk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds2);
-          const int sgrid = resident_grid(sk, slds2, B, BS_NT);
-          if (lmask && s2.dbg) hipLaunchKernelGGL((bwd_stream2_kernel<2, true>), dim3(sgrid), dim3(BS_NT), slds2, a2c_s(stream), s2);
-          else if (lmask) hipLaunchKernelGGL(bwd_stream2_kernel<2>, dim3(sgrid), dim3(BS_NT), slds2, a2c_s(stream), s2);
-          else if (mask) hipLaunchKernelGGL(bwd_stream2_kernel<1>, dim3(sgrid), dim3(BS_NT), slds2, a2c_s(stream), s2);
-          else hipLaunchKernelGGL(bwd_stream2_kernel<0>, dim3(sgrid), dim3(BS_NT), slds2, a2c_s(stream), s2);
-          A2C_CHECK_LAUNCH();
-          return A2C_OK;
-        }
-        const size_t slds = 4 * ((size_t)d->Cout * q.PLANE + 64 + (size_t)d->Cin * d->H * d->W);
-        const void* sk = mask ? (const void*)bwd_stream_kernel<true> : (const void*)bwd_stream_kernel<false>;
-        if (slds > 64 * 1024) (void)hipFuncSetAttribute(sk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds);
-        const int sgrid = resident_grid(sk, slds, B, BS_NT);
-        if (mask) hipLaunchKernelGGL(bwd_stream_kernel<true>, dim3(sgrid), dim3(BS_NT), slds, a2c_s(stream), sp);
-        else hipLaunchKernelGGL(bwd_stream_kernel<false>, dim3(sgrid), dim3(BS_NT), slds, a2c_s(stream), sp);
+        Bstream2P s2;
+        s2.s = sp; s2.lmask = lmask; s2.lmw = n4 / 64 * 4; s2.dbg = g_bs2_dbg;
+        const void* sk = lmask ? (const void*)bwd_stream2_kernel<2> : mask ? (const void*)bwd_stream2_kernel<1> : (const void*)bwd_stream2_kernel<0>;
+        if (slds2 > 64 * 1024) (void)hipFuncSetAttribute(sk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds2);
+        const int sgrid = resident_grid(sk, slds2, B, BS_NT);
+        if (lmask && s2.dbg) hipLaunchKernelGGL((bwd_stream2_kernel<2, true>), dim3(sgrid), dim3(BS_NT), slds2, a2c_s(stream), s2);
+        else if (lmask) hipLaunchKernelGGL(bwd_stream2_kernel<2>, dim3(sgrid), dim3(BS_NT), slds2, a2c_s(stream), s2);
+        else if (mask) hipLaunchKernelGGL(bwd_stream2_kernel<1>, dim3(sgrid), dim3(BS_NT), slds2, a2c_s(stream), s2);
+        else hipLaunchKernelGGL(bwd_stream2_kernel<0>, dim3(sgrid), dim3(BS_NT), slds2, a2c_s(stream), s2);
         A2C_CHECK_LAUNCH();
         return A2C_OK;
       }
@@ -4879,7 +4445,7 @@ int conv_bwd_data_generic(const a2c_conv_desc* d, const float* dout, const float
     }
   }
   if (lmask) return A2C_ERR_ARG;           // only the streaming kernel reads lane masks
-  if (S * S <= MAX_CLS && !getenv("A2C_NO_BAND") && ((uintptr_t)din % 16 == 0) && (!mask || (uintptr_t)mask % 16 == 0)) {
+  if (S * S <= MAX_CLS && ((uintptr_t)din % 16 == 0) && (!mask || (uintptr_t)mask % 16 == 0)) {
     const int rc = bwd_band_tuned(d, dout, wprep_bwd, mask, din, B, stream);
     if (rc != BAND_NA) return rc;
   }
@@ -4988,10 +4554,9 @@ int a2c_conv2d_bwd_weight_frames(const a2c_conv_desc* d, const uint8_t* fstore, 
   wp.in = nullptr; wp.in_bs = 0; wp.dout = dout; wp.slab = (float*)ws; wp.B = B;
   wp.fstore = fstore; wp.fs_slot_stride = (long)slot_stride; wp.T = (int)T; wp.nvalid = nvalid;
   {  // the bf16-pipe form (exact 3-way split of dOut; uint8 pixels are exact in bf16); A2C_WGRAD_F32=1: the fp32 MFMAs below
-    const char* e32 = getenv("A2C_WGRAD_F32");       // (read per call: A/B runs, tests)
     WsbGeo gq;
     size_t ldsb = 0;
-    if (!(e32 != nullptr && e32[0] == '1') && plan_wstream_bf16(d, wp, gq, ldsb)) {
+    if (!a2c_env_on("A2C_WGRAD_F32") && plan_wstream_bf16(d, wp, gq, ldsb)) {
       static bool attrb = false;
       if (!attrb) {
         if (hipFuncSetAttribute((const void*)wgrad_stream_bf16_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
@@ -5042,18 +4607,8 @@ int a2c_conv2d_bwd_weight_rank(const a2c_conv_desc* d, const float* in, int64_t 
     attrr = true;
   }
   WgradX6P xp;
-  xp.in = in; xp.in_bs = (long)in_bstride; xp.dout = nullptr; xp.slab = (float*)ws; xp.B = B; xp.dbg = 0;
+  xp.in = in; xp.in_bs = (long)in_bstride; xp.dout = nullptr; xp.slab = (float*)ws; xp.B = B;
   xp.dl = dl; xp.ldl = (long)ld_dl; xp.nlog = n_logits; xp.Wc = Wc; xp.a2b = maskbits; xp.a2b_row = (long)mask_row_bytes;
-  const char* x6 = getenv("A2C_WGRAD_X6");
-  if (x6 && x6[0] == '2') {
-    static bool attrq = false;
-    if (!attrq) {
-      if (hipFuncSetAttribute((const void*)wgrad_x6p_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wxp::LDS_BYTES) != hipSuccess)
-        return A2C_ERR_LAUNCH;
-      attrq = true;
-    }
-    hipLaunchKernelGGL(wgrad_x6p_kernel<true>, dim3(grid), dim3(wxp::NT), wxp::LDS_BYTES, st, xp);
-  } else
   hipLaunchKernelGGL(wgrad_x6_kernel<true>, dim3(grid), dim3(wx::NT), wx::LDS_BYTES, st, xp);
   A2C_CHECK_LAUNCH();
   const long nWx = 32L * 256, perx = nWx + 32;
@@ -5075,7 +4630,7 @@ int a2c_conv2d_bwd_weight(const a2c_conv_desc* d, const float* in, int64_t in_bs
   {  // streaming kernel: A3C conv1 class at large batch
     WstreamP wp;
     const int grid = stream_grid();
-    if (aligned && B >= 8 * grid && ((uintptr_t)dout % 16 == 0) && !getenv("A2C_NO_STREAM") && !getenv("A2C_NO_PF") &&
+    if (aligned && B >= 8 * grid && ((uintptr_t)dout % 16 == 0) && !a2c_env_on("A2C_NO_STREAM") &&
         plan_wstream(d, wp)) {
       wp.in = in; wp.in_bs = in_bstride; wp.dout = dout; wp.slab = (float*)ws; wp.B = B;
       wp.fstore = nullptr; wp.fs_slot_stride = 0; wp.T = 1; wp.nvalid = nullptr;
@@ -5096,10 +4651,9 @@ int a2c_conv2d_bwd_weight(const a2c_conv_desc* d, const float* in, int64_t in_bs
     }
   }
   {  // the bf16 x 6 form (wgrad_x6_kernel): exactly A3CModel's conv2 at streaming batch; A2C_WGRAD_X6=0 keeps the fp32 MFMA kernel
-    const char* x6 = getenv("A2C_WGRAD_X6");
     const int grid = stream_grid() < pl.grid ? stream_grid() : pl.grid;
     if (pl.run == 2 && d->Cin == 16 && d->Cout == 32 && d->H == 20 && d->W == 20 && d->ks == 4 && d->stride == 2 && d->pad == 0 &&
-        aligned && ((uintptr_t)dout % 16 == 0) && B >= 8 * grid && !(x6 && x6[0] == '0')) {
+        aligned && ((uintptr_t)dout % 16 == 0) && B >= 8 * grid && a2c_env_int("A2C_WGRAD_X6", 1) != 0) {
       static bool attrx = false;
       if (!attrx) {
         if (hipFuncSetAttribute((const void*)wgrad_x6_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wx::LDS_BYTES) != hipSuccess ||
@@ -5110,16 +4664,6 @@ int a2c_conv2d_bwd_weight(const a2c_conv_desc* d, const float* in, int64_t in_bs
       WgradX6P xp;
       xp.in = in; xp.in_bs = (long)in_bstride; xp.dout = dout; xp.slab = (float*)ws; xp.B = B;
       xp.dl = nullptr; xp.ldl = 0; xp.nlog = 0; xp.Wc = nullptr; xp.a2b = nullptr; xp.a2b_row = 0;
-      { const char* dg = getenv("A2C_WGRAD_X6_DBG"); xp.dbg = dg ? atoi(dg) : 0; }      // timing experiments only (wrong sums)
-      if (x6 && x6[0] == '2') {              // OPT-IN (A2C_WGRAD_X6=2): conversion under the matrix phase -- measured slower, see the kernel
-        static bool attrp = false;
-        if (!attrp) {
-          if (hipFuncSetAttribute((const void*)wgrad_x6p_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wxp::LDS_BYTES) != hipSuccess)
-            return A2C_ERR_LAUNCH;
-          attrp = true;
-        }
-        hipLaunchKernelGGL(wgrad_x6p_kernel<false>, dim3(grid), dim3(wxp::NT), wxp::LDS_BYTES, st, xp);
-      } else
       hipLaunchKernelGGL(wgrad_x6_kernel<false>, dim3(grid), dim3(wx::NT), wx::LDS_BYTES, st, xp);
       A2C_CHECK_LAUNCH();
       const long nWx = 32L * 256, perx = nWx + 32;
@@ -5150,8 +4694,7 @@ int a2c_conv2d_bwd_weight(const a2c_conv_desc* d, const float* in, int64_t in_bs
   p.S = d->stride; p.sy0 = pl.t.sy0; p.TPH = pl.t.TPH; p.tiles = pl.t.tiles; p.B = B;
   p.PLANEo = pl.PLANEo; p.nkt = ceil_div(p.K, 16);
   p.dvec = ((d->OW % 4 == 0) && ((uintptr_t)dout % 16 == 0)) ? 4 : ((d->OW % 2 == 0) && ((uintptr_t)dout % 8 == 0)) ? 2 : 0;
-  p.dflat = (pl.t.tiles == 1 && ((long)d->Cout * d->OH * d->OW) % 4 == 0 && ((uintptr_t)dout % 16 == 0) &&
-             !getenv("A2C_NO_FLAT_STAGE")) ? 1 : 0;
+  p.dflat = (pl.t.tiles == 1 && ((long)d->Cout * d->OH * d->OW) % 4 == 0 && ((uintptr_t)dout % 16 == 0)) ? 1 : 0;
 #define WGRAD_LAUNCH(...) launch_wgrad_t<__VA_ARGS__>(p, pl.grid, pl.lds, st)
   WGRAD_VARIANTS(WGRAD_LAUNCH)
 #undef WGRAD_LAUNCH

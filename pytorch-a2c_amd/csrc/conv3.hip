@@ -208,12 +208,10 @@ struct C3P {
   const unsigned* sg_in;              // backward-data: the ReLU mask of the layer below as sign words, or nullptr
   long sg_bs;                         // sample stride of the sign words (in words)
   C3U8 u8;                            // first layers: uint8 frame-store source instead of src (u8.f != nullptr)
-  int prio;                           // loader waves at raised priority
   float* w1_slab;                     // c3bs_kernel<..., W1>: per (workgroup, w1 wave) partial [16 x 36 | 16] of the FIRST layer's gradient
 };
-// (loader waves issue a few hundred instructions per chunk between the computing waves' MFMA streams: at equal priority they
-// were the critical path of the weight-gradient kernels; A2C_C3_PRIO=0 = round 3's schedule, for A/B runs)
-static int c3_prio() { static const int v = getenv("A2C_C3_PRIO") ? atoi(getenv("A2C_C3_PRIO")) : 1; return v; }
+// (loader waves run at raised priority: they issue a few hundred instructions per chunk between the computing waves' MFMA
+// streams, and at equal priority they were the critical path of the weight-gradient kernels)
 
 template <int CS, int CD, int H, int W, int S, int R, int KCO = 0, int NLO = 0>
 struct C3Geo {
@@ -375,7 +373,7 @@ __device__ __forceinline__ void c3_body(const C3P& p, float* __restrict__ lds, c
   if (w >= G::NW) {
     // ------------------------------------------------------------------ loader waves (planes / fragment pieces dealt round robin)
     const int lw = w - G::NW;
-    if (p.prio) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     int roff[G::NQ], rrow[G::NQ];                 // this lane's piece of DMA instruction q: source offset / image row
 #pragma unroll
     for (int q = 0; q < G::NQ; ++q) {
@@ -679,7 +677,7 @@ __global__ __launch_bounds__(640) void c3b_kernel(C3P p) {
   if (w >= G::NW) {
     // ------------------------------------------------------------------ loader waves
     const int lw = w - G::NW;
-    if (p.prio) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     int roff[G::NQ], rrow[G::NQ];
 #pragma unroll
     for (int q = 0; q < G::NQ; ++q) {
@@ -1111,7 +1109,7 @@ __global__ __launch_bounds__((C3SGeo<CS, CD, H, W, S, R, DS>::NTHR)) void c3s_ke
   if (w >= G::NW) {
     // ------------------------------------------------------------------ loader waves
     const int lw = w - G::NW;
-    if (p.prio) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     int roff[G::NQ], rrow[G::NQ];
 #pragma unroll
     for (int q = 0; q < G::NQ; ++q) {
@@ -1422,7 +1420,7 @@ __global__ __launch_bounds__((C3BSGeo<CO, CI, HO, WO, RQ, KC, D, FRES, ODD, MS, 
     typedef __bf16 bf16x8s __attribute__((ext_vector_type(8)));
     typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
     if constexpr (W1) {
-      if (p.prio) __builtin_amdgcn_s_setprio(2);              // (the band waits for them at X: 7.01 -> 6.87 ms at N = 32,768)
+      __builtin_amdgcn_s_setprio(2);              // (the band waits for them at X: 7.01 -> 6.87 ms at N = 32,768)
     }
     f32x4 wacc0 = {0.f, 0.f, 0.f, 0.f}, wacc1 = wacc0, wacc2 = wacc0;
     float wdb = 0.f;
@@ -1563,7 +1561,7 @@ __global__ __launch_bounds__((C3BSGeo<CO, CI, HO, WO, RQ, KC, D, FRES, ODD, MS, 
   if (w >= G::NW) {
     // ------------------------------------------------------------------ loader waves
     const int lw = w - G::NW;
-    if (p.prio) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     int roff[G::NQ], rrow[G::NQ];
 #pragma unroll
     for (int q = 0; q < G::NQ; ++q) {
@@ -1974,8 +1972,6 @@ struct C3WP {
   const float* zero;
   int B;
   C3U8 u8;                            // first layer: uint8 frame-store source instead of x (u8.f != nullptr)
-  int nodma;                          // timing experiment (A2C_C3W_NODMA=1: wrong sums): only the first band is loaded
-  int prio;                           // loader waves at raised priority
 };
 
 __global__ __launch_bounds__(256) void c3w_reduce_kernel(const float* __restrict__ slab, int nslab, long per, long nW,
@@ -2022,7 +2018,7 @@ __global__ __launch_bounds__((C3WGeo<CS, CD, H, W, S, R, KC, NCG, D>::NTHR)) voi
       rrow[q] = (pi < G::PP) ? (i == 0 ? -100000 : r) : -200000;
       roff[q] = r * W + G::PB * (i - 1);
     }
-    if (p.prio) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     int doff[G::DNQ], drow[G::DNQ];                   // dOut pieces: band row and source offset of this lane's piece
 #pragma unroll
     for (int q = 0; q < G::DNQ; ++q) {
@@ -2126,7 +2122,7 @@ __global__ __launch_bounds__((C3WGeo<CS, CD, H, W, S, R, KC, NCG, D>::NTHR)) voi
     // smaller immediate only waits longer.)
     auto wait_for = [&](long k1) {
       constexpr int CA = G::NIX > 63 ? 63 : G::NIX, CB = G::NIX + G::NID > 63 ? 63 : G::NIX + G::NID;
-      if (G::LOOK >= 2 && k1 + 1 < nwork && !p.nodma) {
+      if (G::LOOK >= 2 && k1 + 1 < nwork) {
         if ((int)((unsigned)(k1 + 1) % (unsigned)G::NCH) == 0) c3_wait_vm<CB>();
         else c3_wait_vm<CA>();
       } else {
@@ -2138,7 +2134,7 @@ __global__ __launch_bounds__((C3WGeo<CS, CD, H, W, S, R, KC, NCG, D>::NTHR)) voi
     wait_for(0);
     c3_bar();                                 // (raw s_barrier: __syncthreads() would drain vmcnt to 0)
     for (long k = 0; k < nwork; ++k) {
-      if (k + G::LOOK < nwork && !p.nodma) dma(k + G::LOOK);          // into the image chunk k - 1 left
+      if (k + G::LOOK < nwork) dma(k + G::LOOK);          // into the image chunk k - 1 left
       wait_for(k + 1);
       c3_bar();
     }
@@ -2316,17 +2312,14 @@ bool c3_supported(const a2c_conv_desc* d, int kind);
 // stride-2 backward-data onto an ODD image (GRUModel conv4: 32 <- 48, 21 x 21 <- 11 x 11; conv5: 48 <- 64, 11 x 11 <- 6 x 6): the
 // staged sign-word kernel only (c3bs_kernel<..., ODD>); A2C_NO_ODD_BS=1 leaves the layers on conv.hip's generic band kernel
 static bool c3bs_odd_shape(const a2c_conv_desc* d) {
-  const char* e = getenv("A2C_NO_ODD_BS");             // (read per call: tests compare the two kernels)
-  const bool off = e != nullptr && e[0] == '1';
-  if (off || d->ks != 3 || d->pad != 1 || d->stride != 2 || d->H != d->W) return false;
+  if (a2c_env_on("A2C_NO_ODD_BS")) return false;       // (read per call: tests compare the two kernels)
+  if (d->ks != 3 || d->pad != 1 || d->stride != 2 || d->H != d->W) return false;
   return (d->H == 21 && d->Cin == 32 && d->Cout == 48) ||          // GRUModel conv4: 21 x 21 <- 11 x 11
          (d->H == 11 && d->Cin == 48 && d->Cout == 64);            // GRUModel conv5: 11 x 11 <- 6 x 6
 }
 // backward-data with the FLOAT activation as the mask has a kernel of this family (the odd-image instance reads sign words only)
 bool c3_bwd_mask_supported(const a2c_conv_desc* d) { return c3_supported(d, 1) && !c3bs_odd_shape(d); }
 bool c3_supported(const a2c_conv_desc* d, int kind) {
-  static const bool off = getenv("A2C_NO_C3") != nullptr && getenv("A2C_NO_C3")[0] == '1';
-  if (off) return false;
   if (kind == 1 && d->stride == 2) return c3b_shape(d) || c3bs_odd_shape(d);
   if (d->ks != 3 || d->pad != 1) return false;
   if (kind == 0 && d->stride == 2 && d->H == 42 && d->W == 42) return (d->Cin == 32 && d->Cout == 64) || (d->Cin == 24 && d->Cout == 32);
@@ -2390,7 +2383,6 @@ int c3_fwd(const a2c_conv_desc* d, const float* in, long in_bs, const float* fra
            long out_bs, unsigned* signs, long signs_bs, int B, hipStream_t st) {
   C3P p{in, in_bs, frag, bias, nullptr, out, out_bs, zero_page(), B, relu, g_c3_dbg, signs, nullptr, signs_bs};
   if (!p.zero) return A2C_ERR_LAUNCH;
-  p.prio = c3_prio();
   if (signs != nullptr && B > 64) {   // the direct-store kernels with the sign-word writer wave, where they have one (two chunks or more)
     if (d->stride == 1 && d->H == 84 && d->Cin == 16) return c3_launch<16, 24, 84, 84, 1, 12, false, 0, true>(p, st);
     if (d->stride == 2 && d->H == 84 && d->Cin == 24) return c3_launch<24, 32, 84, 84, 2, 6, false, 0, true>(p, st);
@@ -2430,9 +2422,7 @@ int c3_fwd(const a2c_conv_desc* d, const float* in, long in_bs, const float* fra
 
 // rollout-step chain: GRUModel conv2 .. conv5 (16 -> 24 @84, 24 -> 32 @42, 32 -> 48 @21, 48 -> 64 @11, all 3x3 / stride 2 / pad 1)
 bool c3_chain_supported(const a2c_conv_desc* d, int n) {
-  static const bool off = getenv("A2C_NO_C3") != nullptr && getenv("A2C_NO_C3")[0] == '1';
-  const char* nc = getenv("A2C_NO_CHAIN");        // (read per call: tests compare the chain with the four launches)
-  if (off || (nc != nullptr && nc[0] == '1') || n != 4) return false;
+  if (a2c_env_on("A2C_NO_CHAIN") || n != 4) return false;      // (read per call: tests compare the chain with the four launches)
   static const int cin[4] = {16, 24, 32, 48}, cout[4] = {24, 32, 48, 64}, hw[4] = {84, 42, 21, 11};
   for (int i = 0; i < 4; ++i)
     if (d[i].ks != 3 || d[i].pad != 1 || d[i].stride != 2 || d[i].Cin != cin[i] || d[i].Cout != cout[i] || d[i].H != hw[i] || d[i].W != hw[i])
@@ -2452,7 +2442,6 @@ int c3_chain_fwd(const a2c_conv_desc* d, int n, const float* in, long in_bs, con
   for (int i = 0; i < 4; ++i) {
     cp.l[i] = C3P{i == 0 ? in : out[i - 1], i == 0 ? in_bs : out_bs[i - 1], frag[i], bias[i], nullptr, out[i], out_bs[i], zp, B, relu,
                   nullptr, signs[i], nullptr, signs[i] ? signs_bs[i] : 0};
-    cp.l[i].prio = c3_prio();
   }
   using G2 = C3Geo<16, 24, 84, 84, 2, 6, 0, 4>;
   using G3 = C3Geo<24, 32, 42, 42, 2, 11, 0, 4>;
@@ -2493,11 +2482,9 @@ int c3_fwd_frames(const a2c_conv_desc* d, const unsigned char* f, long bs, long 
   if (!c3_fwd_frames_supported(d)) return A2C_ERR_ARG;
   C3P p{nullptr, 0, frag, bias, nullptr, out, out_bs, zero_page(), B, relu, g_c3_dbg, signs, nullptr, signs_bs, C3U8{f, bs, nv, nv_s, T}};
   if (!p.zero) return A2C_ERR_LAUNCH;
-  p.prio = c3_prio();
-  // 256 envs: 7-row bands, two output images, four storers (49.0 -> 43.7 us; 6-row bands 45.5, 8-row 44.8); A2C_C3S_DS=0: one image
-  static const bool ds = !(getenv("A2C_C3S_DS") && getenv("A2C_C3S_DS")[0] == '0');
-  if (B > 64 && ds) return c3s_launch<4, 16, 84, 84, 1, 7, false, true>(p, st);      // (32 envs: 224 twelve-row bands are one per CU)
-  if (signs != nullptr || B > 64) return c3s_launch<4, 16, 84, 84, 1, 12, false>(p, st);
+  // 256 envs: 7-row bands, two output images, four storers (49.0 -> 43.7 us; 6-row bands 45.5, 8-row 44.8)
+  if (B > 64) return c3s_launch<4, 16, 84, 84, 1, 7, false, true>(p, st);      // (32 envs: 224 twelve-row bands are one per CU)
+  if (signs != nullptr) return c3s_launch<4, 16, 84, 84, 1, 12, false>(p, st);
   return c3_launch<4, 16, 84, 84, 1, 6, false>(p, st);
 }
 
@@ -2507,7 +2494,6 @@ int c3_bwd_data(const a2c_conv_desc* d, const float* dout, const float* frag, co
   C3P p{dout, (long)d->Cout * d->OH * d->OW, frag, nullptr, mask, din, (long)d->Cin * d->H * d->W, zero_page(), B, 0, g_c3_dbg,
         nullptr, signs, signs_bs};
   if (!p.zero) return A2C_ERR_LAUNCH;
-  p.prio = c3_prio();
   if (mask != nullptr) {
     if (d->stride == 1 && d->Cin == 16 && d->Cout == 24) return c3_launch<24, 16, 84, 84, 1, 12, true>(p, st);
     if (d->stride == 2 && d->H == 84 && d->Cin == 24) return c3b_launch<32, 24, 42, 42, 6, 8>(p, st);
@@ -2531,7 +2517,7 @@ int c3_bwd_data(const a2c_conv_desc* d, const float* dout, const float* frag, co
 // layer 2's backward-data (sign-word mask) + the first layer's weight gradient from the uint8 frame store, in one pass:
 // GRUModel's conv2 (16 <- 24, 84 x 84 <- 42 x 42, stride 2) over conv1 (4 -> 16, 3 x 3, stride 1, pad 1)
 bool c3_bwd_data_w1_frames_supported(const a2c_conv_desc* d2, const a2c_conv_desc* d1) {
-  static const bool off = getenv("A2C_NO_W1_FRAMES") && getenv("A2C_NO_W1_FRAMES")[0] == '1';
+  static const bool off = a2c_env_on("A2C_NO_W1_FRAMES");
   return !off && c3_supported(d2, 1) && d2->stride == 2 && d2->H == 84 && d2->W == 84 && d2->Cin == 16 && d2->Cout == 24 &&
          d1->Cin == 4 && d1->Cout == 16 && d1->H == 84 && d1->W == 84 && d1->ks == 3 && d1->stride == 1 && d1->pad == 1;
 }
@@ -2546,7 +2532,6 @@ int c3_bwd_data_w1_frames(const a2c_conv_desc* d2, const a2c_conv_desc* d1, cons
   C3P p{dout, (long)d2->Cout * d2->OH * d2->OW, frag, nullptr, nullptr, nullptr, 0, zero_page(), B, 0, g_c3_dbg,
         nullptr, signs, signs_bs, C3U8{f, bs, nv, 1, T}};
   if (!p.zero) return A2C_ERR_LAUNCH;
-  p.prio = c3_prio();
   return c3bs_w1_launch<24, 16, 42, 42, 6, 8, 4, true>(p, dW1, db1, ws, ws_bytes, st);
 }
 
@@ -2571,17 +2556,13 @@ int c3_bwd_data_w1_frames(const a2c_conv_desc* d2, const a2c_conv_desc* d1, cons
   X(32, 64, 42, 42, 2, 7, 8, 4, 2)
 
 bool c3w_supported(const a2c_conv_desc* d) {
-  static const bool off = (getenv("A2C_NO_C3") != nullptr && getenv("A2C_NO_C3")[0] == '1') ||
-                          (getenv("A2C_NO_C3W") != nullptr && getenv("A2C_NO_C3W")[0] == '1');
-  static const bool all = !(getenv("A2C_C3W_ALL") != nullptr && getenv("A2C_C3W_ALL")[0] == '0');
-  if (off || d->ks != 3 || d->pad != 1) return false;
+  if (d->ks != 3 || d->pad != 1) return false;
   // Measured against conv.hip's wgrad_kernel at N = 4096 (tools/conv3_check.py): this kernel wins on the first layer
   // (4 -> 16: 0.92 vs 1.01 ms) and on ConvModel's conv4 (32 -> 64 @42: 1.29 vs 1.55 ms), ties on the 84-wide
   // 16 -> 24 layers (2.87-2.95 vs 3.00 ms, 1.15 vs 1.11 ms: matrix-bound in both, 67 TF with a quarter of the 24-channel
   // tiles empty -- and the generic instance for them spilled registers), and lost on the 24 -> 32 layers until the loader
   // waves got their priority, the flat dOut bands and four waves for dword rows (round 4; N = 32,768: 11.2 vs 12.0 ms
-  // at 84, 3.30 vs 3.56 at 42).  A2C_C3W_ALL=0 keeps those two on the generic kernel.
-  if (!all && d->Cin == 24) return false;
+  // at 84, 3.30 vs 3.56 at 42).
 #define C3W_MATCH(cs, cd, h, w_, s_, r, kc, ncg, dd) if (d->Cin == cs && d->Cout == cd && d->H == h && d->W == w_ && d->stride == s_) return true;
   C3W_CASES(C3W_MATCH)
 #undef C3W_MATCH
@@ -2589,8 +2570,7 @@ bool c3w_supported(const a2c_conv_desc* d) {
 }
 
 static int c3w_dispatch(const a2c_conv_desc* d, const C3WP& p, float* dW, float* db, size_t ws_bytes, hipStream_t st, size_t* need) {
-  const char* e_old = getenv("A2C_C3W_D2");       // (read per call: tests switch it)
-  const bool old = e_old != nullptr && e_old[0] == '1';
+  const bool old = a2c_env_on("A2C_C3W_D2");       // (read per call: tests switch it)
 #define C3W_RUN(cs, cd, h, w_, s_, r, kc, ncg, dd) \
   if (d->Cin == cs && d->Cout == cd && d->H == h && d->W == w_ && d->stride == s_) return c3w_launch<cs, cd, h, w_, s_, r, kc, ncg, dd>(p, dW, db, ws_bytes, st, need);
   if (old) { C3W_OLD_CASES(C3W_RUN) }
@@ -2610,9 +2590,6 @@ size_t c3w_ws_bytes(const a2c_conv_desc* d) {
 int c3w_bwd_weight(const a2c_conv_desc* d, const float* in, long in_bs, const float* dout, float* dW, float* db, int B, void* ws,
                    size_t ws_bytes, hipStream_t st) {
   C3WP p{in, in_bs, dout, (float*)ws, zero_page(), B};
-  static const int nodma = getenv("A2C_C3W_NODMA") != nullptr && getenv("A2C_C3W_NODMA")[0] == '1';
-  p.nodma = nodma;
-  p.prio = c3_prio();
   if (!p.zero) return A2C_ERR_LAUNCH;
   return c3w_dispatch(d, p, dW, db, ws_bytes, st, nullptr);
 }
@@ -2622,6 +2599,5 @@ int c3w_bwd_weight_frames(const a2c_conv_desc* d, const unsigned char* f, long b
   if (!(c3w_supported(d) && d->Cin == 4)) return A2C_ERR_ARG;
   C3WP p{nullptr, 0, dout, (float*)ws, zero_page(), B, C3U8{f, bs, nv, 1, T}};
   if (!p.zero) return A2C_ERR_LAUNCH;
-  p.prio = c3_prio();
   return c3w_dispatch(d, p, dW, db, ws_bytes, st, nullptr);
 }

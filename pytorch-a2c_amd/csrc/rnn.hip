@@ -394,10 +394,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
 }  // namespace
 
 // A2C_GRU_K4=1 (read per call): the cell kernels with a four-way K split, bit-identical to the launch sequences they replace
-static bool gru_k4() {
-  const char* e = getenv("A2C_GRU_K4");
-  return e != nullptr && e[0] == '1';
-}
+static bool gru_k4() { return a2c_env_on("A2C_GRU_K4"); }
 
 extern "C" {
 int a2c_gru_gates(const float* gx, const float* gh, const float* b, const float* h, float* z, float* r, float* rh,

@@ -70,7 +70,7 @@ struct RolloutX {              // what a2c_a3c_rollout adds to the per-step argu
   int frame_bits;                                  // the pool publishes one bit per pixel (A2C_FRAME_BITS)
   unsigned long long* dbg;                         // phase stamps of workgroup 0 (a2c_debug_ring_timing), or nullptr
   int poll_gap;                                    // 64-cycle sleeps between two polls of the rec granule
-  int early_poll;                                  // ring kernel: first poll behind plane 0 (A2C_RING_EARLY=0: behind plane 1 only)
+  int early_poll;                                  // ring kernel: first poll behind plane 0 (0: behind plane 1 only)
   int bstride, boff;                               // ring kernel: workgroup i plays env b = i * bstride + boff (blocks of a larger launch)
 };
 
@@ -1297,10 +1297,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 }
 
 // conv1 of the ring kernel on the bf16 pipe (exact 3-way split of the weights, see a3c_ring_kernel); A2C_RING_F32=1: fp32 MFMAs
-static bool ring_bf16() {
-  const char* e = getenv("A2C_RING_F32");       // (read per call: A/B runs)
-  return !(e != nullptr && e[0] == '1');
-}
+static bool ring_bf16() { return !a2c_env_on("A2C_RING_F32"); }      // (read per call: A/B runs)
 static size_t ring_lds(const StepP& p, int hnt) {
   const int ntile2 = (p.OH2 * p.OW2 + 15) / 16;
   const size_t part = (size_t)ntile2 * 1024 > (size_t)hnt * NT ? (size_t)ntile2 * 1024 : (size_t)hnt * NT;
@@ -1363,10 +1360,8 @@ static bool set_lds_attr() {
  * a2c_a3c_ring_supported answers the same question for the caller that wants to leave the fp32 state rows out
  * (states_lazy).  The environment switches are read per call (tests and A/B scripts flip them). */
 static bool ring_applies(const StepP& p, int B, int cus, int hnt, const float* conv1_weight) {
-  const char* nr = getenv("A2C_NO_RING");
-  if (nr != nullptr && nr[0] == '1') return false;
-  const char* rb = getenv("A2C_RING_BLOCKS");
-  const bool ring_blocks = !(rb != nullptr && rb[0] == '0');
+  if (a2c_env_on("A2C_NO_RING")) return false;
+  const bool ring_blocks = a2c_env_int("A2C_RING_BLOCKS", 1) != 0;
   return conv1_weight != nullptr && ((uintptr_t)conv1_weight % 4) == 0 && (B <= cus || ring_blocks) &&
          ring_lds(p, hnt) <= 160 * 1024 && (p.OH1 * p.OW1 + 15) / 16 <= 32;
 }
@@ -1462,8 +1457,7 @@ int a2c_a3c_rollout(const a2c_a3c_rollout_args* r, a2c_stream_t stream) {
   p.x.nvalid = r->nvalid_rows; p.x.nvalid_carry = r->nvalid_carry;
   p.x.states_lazy = (r->states_lazy && r->frame_store) ? 1 : 0;
   {
-    static const bool no_tag = getenv("A2C_NO_TAGGED") != nullptr && getenv("A2C_NO_TAGGED")[0] == '1';
-    const bool ok = r->tagged && r->frame_bits && !no_tag && r->tagged_chunks >= 2 && r->tagged_chunks <= 64 &&
+    const bool ok = r->tagged && r->frame_bits && r->tagged_chunks >= 2 && r->tagged_chunks <= 64 &&
                     r->tagged_stride >= 16 * (int64_t)r->tagged_chunks && r->tagged_stride % 16 == 0 && ((uintptr_t)r->tagged % 16) == 0 &&
                     (r->tagged_chunks - 1) * 112 >= r->H * r->W;
     p.x.tagged = ok ? r->tagged : nullptr;
@@ -1472,12 +1466,8 @@ int a2c_a3c_rollout(const a2c_a3c_rollout_args* r, a2c_stream_t stream) {
   }
   p.x.frame_bits = r->frame_bits ? 1 : 0;
   p.x.dbg = g_ring_dbg;
-  {
-    static const int gap = getenv("A2C_RING_POLL") ? atoi(getenv("A2C_RING_POLL")) : 4;
-    p.x.poll_gap = gap > 0 ? gap : 1;
-    static const int early = getenv("A2C_RING_EARLY") ? atoi(getenv("A2C_RING_EARLY")) : 1;
-    p.x.early_poll = early;
-  }
+  p.x.poll_gap = 4;
+  p.x.early_poll = 1;
   if (r->frame_store && (!r->nvalid_rows || !r->nvalid_carry || r->T < 4 || ((uintptr_t)r->frame_store % 16) ||
                          r->frame_store_slot_stride % 16 || r->frame_store_slot_stride < (r->T + 4) * (int64_t)r->H * r->W))
     return A2C_ERR_ARG;

@@ -23,6 +23,24 @@ def test_header_lists_the_path_functions():
         assert n in names
 
 
+def test_environment_switches_are_the_ones_the_header_lists():
+    """every A2C_* name the kernel sources read (through a2c_env_on / a2c_env_int / env_kb, the only readers) is listed in
+    include/a2c_mi355x.h's "Environment switches" section, and every listed name is read"""
+    csrc = os.path.join(ROOT, "pytorch-a2c_amd", "csrc")
+    read = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith(".hip"):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        assert "getenv(" not in src, f + ": read the environment through a2c_env_on / a2c_env_int"
+        read |= set(re.findall(r"\b(?:a2c_env_on|a2c_env_int|env_kb)\(\s*\"(A2C_[A-Z0-9_]+)\"", src))
+        read |= set(re.findall(r"\bgetenv\(\s*\"(A2C_[A-Z0-9_]+)\"", src))
+    hdr = open(os.path.join(ROOT, "include", "a2c_mi355x.h")).read()
+    m = re.search(r"/\*\s*\n \* Environment switches\n(.*?)\*/", hdr, flags=re.S)
+    assert m, "include/a2c_mi355x.h: no Environment switches section"
+    listed = set(re.findall(r"^ \*   (A2C_[A-Z0-9_]+)[=<]", m.group(1), flags=re.M))
+    assert read and read == listed, (sorted(read - listed), sorted(listed - read))
+
 def test_library_exports_every_declared_symbol():
     from a2c_amd import _lib
     lib = _lib.load()                      # raises if the .so is missing or a symbol is absent

@@ -850,11 +850,10 @@ def _lanemask_ref(act):
 
 
 @pytest.mark.parametrize("B", [2048 + 55, 4096])
-def test_conv2d_streaming_backward_data_with_lane_masks(monkeypatch, B):
+def test_conv2d_streaming_backward_data_lane_masks_equal_the_float_mask(monkeypatch, B):
     """round 6: the streaming backward-data kernel of A3CModel's conv2 takes its ReLU mask as LANE MASKS (800 B per sample
     instead of the 25.6 KB activation row): a2c_lanemask_from_act == the layout's definition, and the masked dX equals the
-    float-mask call bit for bit -- on the second form of the kernel (two dX images, default) and against the first
-    (A2C_BWD_STREAM_V1=1)."""
+    float-mask call bit for bit (bwd_stream2_kernel: two dX images)."""
     ops = _ops()
     monkeypatch.setenv("A2C_BWD_X6", "0")                    # (the fp32 MFMA kernels; the bf16 x 6 form has its own test below)
     d = ops.conv_desc(16, 20, 20, 32, 4, 2, 0)
@@ -875,23 +874,8 @@ def test_conv2d_streaming_backward_data_with_lane_masks(monkeypatch, B):
     ops.conv_bwd_data_lanemask(d, dout, wb, lm, got, B)
     want = torch.full((B, 16, 20, 20), float("nan"), device=DEV)
     ops.conv_bwd_data(d, dout, wb, actd, want, B)
-    for order in ("0", "1", "2"):                            # the opt-in third form (one barrier per sample), its three schedules
-        monkeypatch.setenv("A2C_BWD_STREAM_FORM", "3")
-        monkeypatch.setenv("A2C_BS3_ORDER", order)
-        f3 = torch.full((B, 16, 20, 20), float("nan"), device=DEV)
-        ops.conv_bwd_data_lanemask(d, dout, wb, lm, f3, B)
-        torch.cuda.synchronize()
-        assert torch.equal(got, f3), order
-    monkeypatch.delenv("A2C_BWD_STREAM_FORM")
-    monkeypatch.delenv("A2C_BS3_ORDER")
-    monkeypatch.setenv("A2C_BWD_STREAM_V1", "1")
-    old = torch.full((B, 16, 20, 20), float("nan"), device=DEV)
-    ops.conv_bwd_data(d, dout, wb, actd, old, B)
-    with pytest.raises(RuntimeError):
-        ops.conv_bwd_data_lanemask(d, dout, wb, lm, got.clone(), B)            # the first form does not read lane masks
-    monkeypatch.delenv("A2C_BWD_STREAM_V1")
     torch.cuda.synchronize()
-    assert torch.equal(got, want) and torch.equal(want, old)
+    assert torch.equal(got, want)
     assert not bool(torch.isnan(got).any())
 
 
@@ -961,12 +945,6 @@ def test_conv2d_weight_gradient_on_the_bf16_pipe_is_the_fp32_sum(monkeypatch, B,
         assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
         res[x6] = (outs[0][0].double().reshape(32, 256), outs[0][1].double())
     assert not torch.equal(res["1"][0], res["0"][0])                          # (the bf16 kernel did run)
-    monkeypatch.setenv("A2C_WGRAD_X6", "2")               # the opt-in form with the conversion under the matrix phase: the same dW
-    dW2, db2 = torch.full((32, 16, 4, 4), float("nan"), device=DEV), torch.full((32,), float("nan"), device=DEV)
-    ops.conv_bwd_weight(d, a1.data_ptr(), 6400 + pad, dout, dW2, db2, B, ws)
-    torch.cuda.synchronize()
-    assert torch.equal(dW2.double().reshape(32, 256), res["1"][0])
-    close("db, pipelined form", db2, res["1"][1], 1e-5 * float(res["1"][1].abs().max()) + 1e-4, 1e-5)
     x = a1[:, :6400].reshape(B, 16, 20, 20).double()
     ref = torch.zeros(32, 256, dtype=torch.float64, device=DEV)
     for i in range(0, B, 512):
@@ -1476,11 +1454,11 @@ def test_gemm_x6_from_prebuilt_images(M, N, K, sk, kc):
         ops.gemm_x6_images(M, N, K, ia, ib, c32.data_ptr(), N, splitk=2, ws=None)
 
 
-@pytest.mark.parametrize("mode", ["1", "2"])
+@pytest.mark.parametrize("mode", ["2"])
 @pytest.mark.parametrize("tA,tB,M,N,K", [(0, 1, 1280, 1100, 2000), (0, 0, 1152, 900, 1000), (1, 0, 520, 1030, 777)])
 def test_gemm_bf16_x9_path_is_the_fp32_product(tA, tB, M, N, K, mode, monkeypatch):
-    """A2C_GEMM_X9=1 (opt-in): both operands split into three bf16 pieces (exact), nine exact piece products per element
-    pair, fp32 accumulation -- against fp64 no less accurate than the fp32 MFMA kernels (1.5 x + 1e-7 of the rms), for every
+    """A2C_GEMM_X9=2 (the x 6 kernel from the small threshold on): both operands split into three bf16 pieces (exact), the
+    six piece products with qa + qb <= 2 per element pair, fp32 accumulation -- against fp64 no less accurate than the fp32 MFMA kernels (1.5 x + 1e-7 of the rms), for every
     operand orientation, ragged sizes, bias + ReLU + mask in the epilogue; without the extra workspace the call falls back."""
     ops = _ops()
     a = rnd((K, M) if tA else (M, K), 31).to(DEV)
@@ -1502,7 +1480,7 @@ def test_gemm_bf16_x9_path_is_the_fp32_product(tA, tB, M, N, K, mode, monkeypatc
     rms = float(want.pow(2).mean().sqrt())
     e9, e32 = (float((res[k] - want).pow(2).mean().sqrt()) / rms for k in (mode, "0"))
     assert e9 <= 1.5 * e32 + 1e-7, (e9, e32)
-    assert not torch.equal(res[mode], res["0"])          # (the x 9 kernel did run)
+    assert not torch.equal(res[mode], res["0"])          # (the x 6 kernel did run)
     monkeypatch.setenv("A2C_GEMM_X9", mode)              # no room for the images: the fp32 kernel, bit for bit
     c = torch.empty(M, N, device=DEV)
     ops.gemm(tA, tB, M, N, K, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), c.data_ptr(), N, bias=bias, relu=True,

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """A3CModel conv1 (8x8 / stride 4) weight gradient from the single-frame uint8 store at update batch, through the C ABI:
-HIP-event time per launch.   python tools/a3c_wgrad_bench.py [N]      (A2C_WGRAD_F32=1: the fp32 MFMA kernel;
-A2C_WSB_DBG=1 / 2 / 3: timing-only variants of the bf16-pipe kernel without its matrix phase / commit phase / both)"""
+HIP-event time per launch.   python tools/a3c_wgrad_bench.py [N]      (A2C_WGRAD_F32=1: the fp32 MFMA kernel)"""
 import os
 import sys
 
@@ -31,4 +30,4 @@ e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 10
 fl = 2.0 * N * 16 * 400 * 256
-print(f"N={N} F32={os.environ.get('A2C_WGRAD_F32', '0')} DBG={os.environ.get('A2C_WSB_DBG', '0')}: {ms:.3f} ms  {fl / ms / 1e9:.1f} TF (fp32-equivalent)")
+print(f"N={N} F32={os.environ.get('A2C_WGRAD_F32', '0')}: {ms:.3f} ms  {fl / ms / 1e9:.1f} TF (fp32-equivalent)")

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """3x3 conv layers of ConvModel / GRUModel through the C ABI: max error against torch (CPU, fp32) at a small batch and
-HIP-event timings at rollout / update batch sizes.  Run twice to compare the kernel families:
-    python tools/conv3_check.py            # shape-specialised streaming kernels (conv3.hip) where they apply
-    A2C_NO_C3=1 python tools/conv3_check.py    # conv.hip's generic kernels"""
+HIP-event timings at rollout / update batch sizes (shape-specialised streaming kernels of conv3.hip where they apply):
+    python tools/conv3_check.py [layer ...]"""
 import os
 import sys
 
@@ -17,8 +16,6 @@ LAYERS = [  # Cin, H, W, Cout, stride, has bwd-data
     (16, 84, 84, 24, 2, True), (24, 42, 42, 32, 2, True), (32, 21, 21, 48, 2, True), (48, 11, 11, 64, 2, True)]
 dev = torch.device("cuda")
 only = [int(a) for a in sys.argv[1:]]
-tag = "generic (A2C_NO_C3=1)" if os.environ.get("A2C_NO_C3") == "1" else "conv3 where supported"
-print("kernels:", tag)
 
 
 def timeit(fn, reps):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-role timeline of workgroup 0 of conv1's staged forward (c3s_kernel, uint8 frames in, sign words out) at 256 samples:
 needs a build with the stamps compiled in (make -C pytorch-a2c_amd/csrc EXTRA=-DA2C_C3_STAMPS after a `make clean`).  Times in us
-relative to the first stamp; A2C_C3S_DS=0 selects the single-image kernel.   python tools/dbg/c3s_stamps.py"""
+relative to the first stamp.   python tools/dbg/c3s_stamps.py"""
 import ctypes
 import os
 import sys
