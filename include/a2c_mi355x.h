@@ -433,6 +433,36 @@ int a2c_loss_fwd_bwd(const float *logits, int64_t ld_logits, const float *vals, 
                      float *dvals, int64_t dval_stride, double *loss_sums, double *reduce_scratch,
                      a2c_stream_t stream);
 
+/* ------------------------------------------------------------------ a5c: continuous (Gaussian) actions
+ * FCModel / GRUFCModel with is_discrete=False (models.py:396-405, 514-524): the heads rows are
+ * [mu (n) | raw (n) | value] and sigma = softplus(raw) + 1e-4 (torch threshold 20: raw > 20 gives raw).
+ * n (the action dimension) is 1 .. A2C_GAUSS_MAX_N.                                      */
+#define A2C_GAUSS_MAX_N 64
+/* sigma[b*ld_sigma + j] = sigma (may be NULL); if actions != NULL, actions[b*ld_act + j] = mu + sigma*eps[b*ld_eps + j]
+ * rounded like torch's two ops (runner.py:98-104).  B rows of heads with row stride ld_heads (>= 2n).                 */
+int a2c_gauss_head(const float *heads, int64_t ld_heads, const float *eps, int64_t ld_eps, float *sigma,
+                   int64_t ld_sigma, float *actions, int64_t ld_act, int64_t B, int n, a2c_stream_t stream);
+/* The reference's Gaussian loss (updater.py:108-117), first of two launches.  With d = mu - a, c = clamp(sigma^2, 1e-3),
+ * l = log(clamp(sqrt(2 pi) sigma, 1e-3)) and adv the (optionally normalised, as in a2c_loss_fwd_bwd) advantage:
+ * sums[0..5] (double) = sum d^2, sum w/(2c), sum w*l, sum l, sum adv, sum (V-R)^2 over the local rows, where
+ * w = adv for n >= 2 and w = 1 for n == 1 (sum adv is only accumulated for n == 1, else 0).  Deterministic (fixed-order
+ * grid reduction in reduce_scratch).  When the batch is sharded the six sums are all-reduced before the second launch. */
+int a2c_gauss_loss_sums(const float *heads, int64_t ld_heads, const float *vals, int64_t val_stride,
+                        const float *actions, int64_t ld_act, const float *advs, const float *returns,
+                        const double *adv_sums, int64_t n_local, int64_t n_global, int n, double *sums,
+                        double *reduce_scratch, a2c_stream_t stream);
+/* Second launch: from the GLOBAL sums (M = n_global*n, mse = sums[0]/M, K and P = sums[1], sums[2], times mean(adv) for
+ * n == 1 -- the reference broadcasts (N,1)*(N,) to an N x N product there), writes
+ *   dheads[i*ldd + j] = dL/dmu,  dheads[i*ldd + n + j] = dL/draw,  dvals[i*dval_stride] = dL/dV,
+ *   loss_sums[0..2] = (-(mse*K + P)/n, sum (V-R)^2, sums[3]/n) * n_local/n_global,
+ * so that Updater's host finishing (sum / n_global, summed over the ranks) gives the reference's
+ * Pi_Loss = pi_coef*(mse*K + P)/M, ValLoss and Entropy = -entr_coef*sums[3]/M.                                          */
+int a2c_gauss_loss_fwd_bwd(const float *heads, int64_t ld_heads, const float *vals, int64_t val_stride,
+                           const float *actions, int64_t ld_act, const float *advs, const float *returns,
+                           const double *adv_sums, const double *sums, int64_t n_local, int64_t n_global, int n,
+                           float pi_coef, float val_coef, float entr_coef, float *dheads, int64_t ldd, float *dvals,
+                           int64_t dval_stride, double *loss_sums, a2c_stream_t stream);
+
 /* ------------------------------------------------------------------ a6: dense layers
  * C[M,N] = (accumulate ? C : 0) + opA(A)[M,K] * opB(B)[K,N] (+ bias[N]) ; then optional ReLU ; then optional
  * multiply by (mask[m*ldmask+n] > 0) (the ReLU derivative of the layer below, fused into

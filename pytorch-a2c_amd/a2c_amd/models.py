@@ -15,7 +15,9 @@ Quirks of the reference that change results and are reproduced (SURVEY.md sectio
   * GRU cell: h = z*h_old + (1-z)*tanh(x Wx2 + (r*h_old) Wh2 + b2), weights (3,in,h) used as
     ``x.mm(W)`` (models.py:472-475).
   * FCModel / GRUFCModel value head = LayerNorm -> Linear(h,1) -> Linear(1,1) (models.py:392-394).
-Out of scope: ``bnorm=True`` paths, continuous actions, the unused noise helpers.
+Continuous (Gaussian) actions (``is_discrete=False``) are available on FCModel and GRUFCModel: ``action_out`` is 2n
+wide, the heads rows are [mu | raw | value] and sigma = softplus(raw) + 1e-4 comes from a2c_gauss_head (csrc/gauss.hip).
+Out of scope: ``bnorm=True`` paths, continuous actions on the pixel models, the unused noise helpers.
 """
 import os
 
@@ -54,6 +56,11 @@ class _HipNet(nn.Module):
 
     def _arena_order(self):
         return [n for n, _ in self.named_parameters()]
+
+    @property
+    def _n_pi(self):
+        """columns of the policy head: the logits, or [mu | raw] of a Gaussian policy"""
+        return self.output_space if self.is_discrete else 2 * self.output_space
 
     def _ensure_device(self):
         if self._arena is not None:
@@ -181,10 +188,16 @@ class _HipNet(nn.Module):
             raise TypeError("recurrent model: forward(x, old_h)")
         if not need_grad:
             out = self._run_forward(xd, hd, "pub", save=False)
-            return tuple(o.clone() for o in out)
+            return self._pack(tuple(o.clone() for o in out))
         params = [p for n, p in self.named_parameters() if n not in self._unused_params]
         h_arg = old_h if (self.is_recurrent and torch.is_tensor(old_h) and old_h.requires_grad) else None
-        return _NetFunction.apply(self, xd, hd, h_arg, *params)
+        return self._pack(_NetFunction.apply(self, xd, hd, h_arg, *params))
+
+    def _pack(self, out):
+        """flat (val, mu, sigma[, h]) of a Gaussian policy -> the reference's (val, (mu, sigma)[, h])"""
+        if self.is_discrete:
+            return out
+        return (out[0], (out[1], out[2])) + tuple(out[3:])
 
     def _run_forward(self, xd, hd, tag, save):
         B = xd.shape[0]
@@ -193,18 +206,28 @@ class _HipNet(nn.Module):
         bstride = xd[0].numel()
         if self.is_recurrent:
             o = self._fwd(xd.data_ptr(), bstride, B, tag, st, save, h_in=hd)
-            return o["vals"].view(B, 1), o["logits"], o["h"]
+            return (o["vals"].view(B, 1),) + self._policy_out(o["logits"], tag, B, st) + (o["h"],)
         o = self._fwd(xd.data_ptr(), bstride, B, tag, st, save)
-        return o["vals"].view(B, 1), o["logits"]
+        return (o["vals"].view(B, 1),) + self._policy_out(o["logits"], tag, B, st)
+
+    def _policy_out(self, logits, tag, B, st):
+        """(logits,) or (mu, sigma) of a Gaussian policy (sigma from a2c_gauss_head into the workspace)"""
+        if self.is_discrete:
+            return (logits,)
+        n = self.output_space
+        sigma = self.ws(tag).get("sigma", (B, n))
+        ops.gauss_head(logits, n, B, sigma=sigma, st=st)
+        return logits[:, :n], sigma
 
     # heads buffer: (B, A+1) = [logits | value]; gradient buffer has the same layout
+    # (a Gaussian policy: [mu | raw | value], 2n + 1 columns)
     def _heads(self, tag, B):
-        A = self.output_space
+        A = self._n_pi
         hb = self.ws(tag).get("heads", (B, A + 1))
         return hb, hb[:, :A], hb[:, A]
 
     def dheads(self, tag, B):
-        A = self.output_space
+        A = self._n_pi
         db = self.ws(tag).get("dheads", (B, A + 1))
         return db, db[:, :A], db[:, A]
 
@@ -224,16 +247,26 @@ class _NetFunction(torch.autograd.Function):
         net, xd = ctx.net, ctx.xd
         B = xd.shape[0]
         st = ops.stream()
-        A = net.output_space
         db, dl, dv = net.dheads("ag", B)
         db.zero_()
-        if gouts[1] is not None:
-            dl.copy_(gouts[1])
+        if net.is_discrete:
+            if gouts[1] is not None:
+                dl.copy_(gouts[1])
+            n_pol = 1
+        else:       # (val, mu, sigma[, h]): sigma = softplus(raw) + 1e-4, torch's softplus backward (threshold 20)
+            n = net.output_space
+            if gouts[1] is not None:
+                dl[:, :n].copy_(gouts[1])
+            if gouts[2] is not None:
+                raw = net._heads("ag", B)[1][:, n:]
+                z = torch.exp(raw)
+                dl[:, n:].copy_(torch.where(raw > 20, gouts[2], gouts[2] * z / (z + 1)))
+            n_pol = 2
         if gouts[0] is not None:
             dv.copy_(gouts[0].reshape(B))
         dh_next = None
-        if net.is_recurrent and len(gouts) > 2 and gouts[2] is not None:
-            dh_next = gouts[2].contiguous()
+        if net.is_recurrent and len(gouts) > 1 + n_pol and gouts[1 + n_pol] is not None:
+            dh_next = gouts[1 + n_pol].contiguous()
         dh_in = net._bwd(xd.data_ptr(), xd[0].numel(), B, "ag", st, dh_next=dh_next) if net.is_recurrent else \
             net._bwd(xd.data_ptr(), xd[0].numel(), B, "ag", st)
         grads = [net.G(n).clone() for n, _ in net.named_parameters() if n not in net._unused_params]
@@ -250,7 +283,8 @@ class A3CModel(_HipNet):
     def __init__(self, input_space, output_space, h_size=256, bnorm=False, is_discrete=True, **kwargs):
         super().__init__()
         if bnorm or not is_discrete:
-            raise NotImplementedError("a2c_amd: bnorm / continuous actions are out of scope (see DESIGN.md)")
+            raise NotImplementedError("a2c_amd: bnorm is out of scope, and continuous actions (is_discrete=False) are "
+                                      "available on FCModel and GRUFCModel only (see DESIGN.md)")
         self.is_recurrent = False
         self.input_space, self.output_space, self.h_size, self.is_discrete = input_space, output_space, h_size, True
         C, H, W = input_space[-3:]
@@ -745,7 +779,8 @@ class ConvModel(_ConvStackNet):
     def __init__(self, input_space, output_space, h_size=288, bnorm=False, is_discrete=True, **kwargs):
         super().__init__()
         if bnorm or not is_discrete:
-            raise NotImplementedError("a2c_amd: bnorm / continuous actions are out of scope (see DESIGN.md)")
+            raise NotImplementedError("a2c_amd: bnorm is out of scope, and continuous actions (is_discrete=False) are "
+                                      "available on FCModel and GRUFCModel only (see DESIGN.md)")
         self.is_recurrent = False
         self.input_space, self.output_space, self.h_size = input_space, output_space, h_size
         self.bnorm, self.is_discrete = False, True
@@ -1108,7 +1143,8 @@ class GRUModel(_ConvStackNet, _GruMixin):
     def __init__(self, input_space, output_space, h_size=288, bnorm=False, is_discrete=True, **kwargs):
         super().__init__()
         if bnorm or not is_discrete:
-            raise NotImplementedError("a2c_amd: bnorm / continuous actions are out of scope (see DESIGN.md)")
+            raise NotImplementedError("a2c_amd: bnorm is out of scope, and continuous actions (is_discrete=False) are "
+                                      "available on FCModel and GRUFCModel only (see DESIGN.md)")
         self.is_recurrent = True
         self.input_space, self.output_space, self.h_size = input_space, output_space, h_size
         self.bnorm, self.is_discrete = False, True
@@ -1288,7 +1324,7 @@ class _FCBase(_HipNet, _LNValueMixin):
         self.base = nn.Sequential(nn.Linear(self.flat_size, h_size), nn.ReLU(), nn.Linear(h_size, h_size))
 
     def _build_heads(self, output_space, h_size):
-        self.action_out = nn.Linear(h_size, output_space)
+        self.action_out = nn.Linear(h_size, self._n_pi)
         self.value_out = nn.Sequential(nn.LayerNorm(h_size), nn.Linear(h_size, 1), nn.Linear(1, 1))
 
     def _base_fwd(self, x_ptr, bstride, B, ws, st):
@@ -1312,9 +1348,9 @@ class FCModel(_FCBase):
 
     def __init__(self, input_shape, output_space, h_size=200, bnorm=False, is_discrete=True, **kwargs):
         super().__init__()
-        if bnorm or not is_discrete:
-            raise NotImplementedError("a2c_amd: bnorm / continuous actions are out of scope (see DESIGN.md)")
-        self.is_discrete, self.is_recurrent = True, False
+        if bnorm:
+            raise NotImplementedError("a2c_amd: bnorm is out of scope (see DESIGN.md)")
+        self.is_discrete, self.is_recurrent = bool(is_discrete), False
         self._build_base(input_shape, output_space, h_size)
         self._build_heads(output_space, h_size)
         self._post_init()
@@ -1324,11 +1360,11 @@ class FCModel(_FCBase):
         fx = self._base_fwd(x_ptr, bstride, B, ws, st)
         hb, logits, vals = self._heads(tag, B)
         linear_fwd(ws, fx.data_ptr(), h, P("action_out.weight"), P("action_out.bias"), logits, B, st)
-        self._value_fwd(ws, fx, B, st, hb[:, self.output_space:])
+        self._value_fwd(ws, fx, B, st, hb[:, self._n_pi:])
         return dict(logits=logits, vals=vals)
 
     def _bwd(self, x_ptr, bstride, B, tag, st):
-        ws, P, G, h, A = self.ws(tag), self.P, self.G, self.h_size, self.output_space
+        ws, P, G, h, A = self.ws(tag), self.P, self.G, self.h_size, self._n_pi
         fx = ws.get("fx", (B, h))
         db, dl, dv = self.dheads(tag, B)
         dfx = ws.get("dfx", (B, h))
@@ -1347,22 +1383,22 @@ class GRUFCModel(_FCBase, _GruMixin):
 
     def __init__(self, input_shape, output_space, h_size=200, bnorm=False, is_discrete=True, **kwargs):
         super().__init__()
-        if bnorm or not is_discrete:
-            raise NotImplementedError("a2c_amd: bnorm / continuous actions are out of scope (see DESIGN.md)")
-        self.is_discrete, self.is_recurrent = True, True
+        if bnorm:
+            raise NotImplementedError("a2c_amd: bnorm is out of scope (see DESIGN.md)")
+        self.is_discrete, self.is_recurrent = bool(is_discrete), True
         self._build_base(input_shape, output_space, h_size)
         self.gru = GRU(x_size=h_size, h_size=h_size)
         self._build_heads(output_space, h_size)
         self._post_init()
 
     def _heads_fwd(self, ws, hn, B, hb, st):
-        A = self.output_space
+        A = self._n_pi
         linear_fwd(ws, hn.data_ptr(), self.h_size, self.P("action_out.weight"), self.P("action_out.bias"), hb[:, :A], B,
                    st)
         self._value_fwd(ws, hn, B, st, hb[:, A:])
 
     def _heads_bwd(self, ws, hn, B, db, dhn, st):
-        A, h = self.output_space, self.h_size
+        A, h = self._n_pi, self.h_size
         self._value_bwd(ws, hn, db[:, A:], dhn, B, st)
         dl = db[:, :A]
         linear_bwd_weight(ws, dl, hn.data_ptr(), h, self.G("action_out.weight"), self.G("action_out.bias"), B, st)
@@ -1396,7 +1432,7 @@ class GRUFCModel(_FCBase, _GruMixin):
 
     # BPTT (updater.py:139-169): base MLP batched rollout-major, GRU cells + heads time-major
     def bptt_forward(self, states, h_states, dones, R, T, tag, st):
-        ws, h, A = self.ws(tag), self.h_size, self.output_space
+        ws, h, A = self.ws(tag), self.h_size, self._n_pi
         N = R * T
         self._refresh(st)
         fx = self._base_fwd(states.data_ptr(), states[0].numel(), N, ws, st)
@@ -1410,7 +1446,7 @@ class GRUFCModel(_FCBase, _GruMixin):
         return vals, logits
 
     def bptt_backward(self, states, dones, R, T, tag, st):
-        ws, h, A = self.ws(tag), self.h_size, self.output_space
+        ws, h, A = self.ws(tag), self.h_size, self._n_pi
         N = R * T
         fx_tm = ws.get("fx_tm", (T, R, h))
         hn_tm = ws.get("tm_hn", (T, R, h))

@@ -699,6 +699,40 @@ def loss_fwd_bwd(logits, vals, actions, advs, returns, adv_sums, n_global, pi_co
           "a2c_loss_fwd_bwd")
 
 
+# ---------------------------------------------------------------- continuous (Gaussian) actions
+def gauss_head(heads, n, B, sigma=None, eps=None, actions_ptr=0, act_ld=0, st=None):
+    """heads rows [mu (n) | raw (n) | ...] (only stride(0) is used) -> sigma (B, n) (optional) and, with eps (B, n),
+    actions rows mu + sigma*eps at actions_ptr (row stride act_ld floats)"""
+    _chk(heads, "heads", contig=False); _chk(sigma, "sigma", contig=False); _chk(eps, "eps", contig=False)
+    check(lib().a2c_gauss_head(_p(heads), heads.stride(0), _p(eps), eps.stride(0) if eps is not None else 0, _p(sigma),
+                               sigma.stride(0) if sigma is not None else 0, actions_ptr or None, act_ld, B, n,
+                               st if st is not None else stream()), "a2c_gauss_head")
+
+
+def gauss_loss_sums(heads, vals, actions, advs, returns, adv_sums, n_global, n, sums, st=None, scratch=None):
+    """first half of the Gaussian loss: sums (6,) float64 of the local rows (a2c_gauss_loss_sums)"""
+    _chk(heads, "heads", contig=False); _chk(vals, "vals", contig=False); _chk(actions, "actions", contig=False)
+    _chk(advs, "advs"); _chk(returns, "returns"); _chk(sums, "sums", torch.float64)
+    st = st if st is not None else stream()
+    check(lib().a2c_gauss_loss_sums(_p(heads), heads.stride(0), _p(vals), vals.stride(0), _p(actions), actions.stride(0),
+                                    _p(advs), _p(returns), _p(adv_sums), heads.shape[0], n_global, n, _p(sums),
+                                    _p(scratch if scratch is not None else reduce_scratch(heads.device, st)), st),
+          "a2c_gauss_loss_sums")
+
+
+def gauss_loss_fwd_bwd(heads, vals, actions, advs, returns, adv_sums, sums, n_global, n, pi_coef, val_coef, entr_coef,
+                       dheads, dvals, loss_sums, st=None):
+    """second half: dheads rows [dmu | draw], dvals and the three loss sums from the global sums"""
+    _chk(heads, "heads", contig=False); _chk(vals, "vals", contig=False); _chk(actions, "actions", contig=False)
+    _chk(advs, "advs"); _chk(returns, "returns"); _chk(sums, "sums", torch.float64)
+    _chk(dheads, "dheads", contig=False); _chk(dvals, "dvals", contig=False); _chk(loss_sums, "loss_sums", torch.float64)
+    check(lib().a2c_gauss_loss_fwd_bwd(_p(heads), heads.stride(0), _p(vals), vals.stride(0), _p(actions), actions.stride(0),
+                                       _p(advs), _p(returns), _p(adv_sums), _p(sums), heads.shape[0], n_global, n,
+                                       float(pi_coef), float(val_coef), float(entr_coef), _p(dheads), dheads.stride(0),
+                                       _p(dvals), dvals.stride(0), _p(loss_sums), st if st is not None else stream()),
+          "a2c_gauss_loss_fwd_bwd")
+
+
 # ---------------------------------------------------------------- dense
 def pick_splitk(M, N, K, target_wgs=512, min_k=32):
     min_k = int(os.environ.get("A2C_SPLITK_MIN_K", min_k))

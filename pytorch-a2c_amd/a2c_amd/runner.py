@@ -72,12 +72,20 @@ class SequentialEnvironment:
     def render(self):
         return self.env.render()
 
-    def get_action(self, preds, rand_nums=None):
-        """softmax + inverse-CDF sample of one (or a batch of) logits rows (runner.py:94-97)."""
-        if not (self.is_gym and self.is_discrete):
+    def get_action(self, preds, rand_nums=None, noise=None):
+        """softmax + inverse-CDF sample of one (or a batch of) logits rows (runner.py:94-97); a continuous env takes the
+        ``(mu, sigma)`` tuple and samples mu + sigma*noise (``noise`` default: torch.randn_like(sigma), runner.py:98-104),
+        returned as a float32 vector of shape (n,)."""
+        if not self.is_gym:
             raise NotImplementedError
-        probs = F.softmax(preds.detach(), dim=-1)
-        return int(sample_action(probs, rand_nums).item())
+        if self.is_discrete:
+            probs = F.softmax(preds.detach(), dim=-1)
+            return int(sample_action(probs, rand_nums).item())
+        mus, sigmas = preds
+        if noise is None:
+            noise = torch.randn_like(sigmas)
+        actions = (mus.detach() + sigmas.detach() * noise.to(sigmas.device)).cpu().squeeze().numpy().astype(np.float32)
+        return actions.reshape(1) if actions.ndim == 0 else actions
 
 
 class HostEnvPool:
@@ -118,12 +126,13 @@ class Runner:
     runner.py:110).  ``datas`` tensors should live on the device (``cuda_if`` them like
     training.py:94-101); ``actions`` may stay a host LongTensor like the reference's."""
 
-    def __init__(self, datas, hyps, gate_q, stop_q, rew_q, env_pool=None, uniform_fn=None, ingest=None):
+    def __init__(self, datas, hyps, gate_q, stop_q, rew_q, env_pool=None, uniform_fn=None, ingest=None, normal_fn=None):
         self.hyps, self.datas = hyps, datas
         self.gate_q, self.stop_q, self.rew_q = gate_q, stop_q, rew_q
         self.obs_deque = deque(maxlen=hyps["n_frame_stack"])     # kept for API parity (single-env helpers)
         self.env_pool = env_pool
         self.uniform_fn = uniform_fn          # (t, B) -> device tensor (B,) of uniforms; default torch.rand
+        self.normal_fn = normal_fn            # continuous nets: (t, B, env0) -> device tensor (B, n) of N(0,1); default torch.randn
         self.ingest = ingest or try_key(hyps, "ingest", None)     # None: zero-copy when it applies, else memcpy
         self._ready = False
         self.error = None                     # exception that ended run() (training.train re-raises it)
@@ -174,11 +183,17 @@ class Runner:
         self.S = C * self.HW
         self.device_pool = hasattr(pool, "device_step")
         self.proc_pool = hasattr(pool, "post_actions")
+        # continuous nets (is_discrete=False): actions are float rows of n, sampled by a2c_gauss_head
+        self.cont = not getattr(net, "is_discrete", True)
+        if self.cont and self.proc_pool:
+            raise ValueError("a2c_amd.Runner: a continuous-action net needs an in-process (HostEnvPool) or device env pool; "
+                             "the process / thread env pools carry int32 actions")
+        self.n_act = int(net.output_space)
         f32 = dict(dtype=torch.float32, device=dev)
         self.bookmark = torch.zeros((B, self.S), **f32)                  # state_bookmark of every env
         self.val_prev = torch.zeros(B, **f32)
         self.done_eff = torch.zeros(B, **f32)
-        self.act_dev = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.act_dev = torch.zeros((B, self.n_act), **f32) if self.cont else torch.zeros(B, dtype=torch.int64, device=dev)
         self.h = torch.zeros((B, net.h_size), **f32) if net.is_recurrent else None   # h_bookmark
         self.ep_rew = np.zeros(B)
         pin = torch.cuda.is_available()
@@ -218,7 +233,7 @@ class Runner:
             torch.cuda.current_stream().synchronize()
         elif not self.device_pool:
             self.h_frames, self.h_rew, self.h_done, self.h_reset = mk(B, self.HW), mk(B), mk(B), mk(B)
-            self.h_act = mk(B, dt=torch.int64)
+            self.h_act = mk(B, self.n_act) if self.cont else mk(B, dt=torch.int64)
             self.np_frames, self.np_rew, self.np_done, self.np_act = (x.numpy() for x in (self.h_frames, self.h_rew,
                                                                                              self.h_done, self.h_act))
             self.d_frames = torch.zeros((B, self.HW), **f32)
@@ -389,6 +404,31 @@ class Runner:
             return self.uniform_fn(t, B, env0)
         return torch.rand(B, device=self.net._dev, dtype=torch.float32)
 
+    def _normals(self, t, B, env0):
+        if self.normal_fn is not None:
+            return self.normal_fn(t, B, env0).reshape(B, self.n_act)
+        return torch.randn((B, self.n_act), device=self.net._dev, dtype=torch.float32)
+
+    def _act_row(self, slot0, T, t):
+        """(address, element stride) of datas['actions'][slot0*T + t] for B slots T rows apart (int64 or float rows of n)"""
+        if self.cont:
+            n = self.n_act
+            return self.datas["actions"].data_ptr() + 4 * n * (slot0 * T + t), T * n
+        return self.datas["actions"].data_ptr() + 8 * (slot0 * T + t), T
+
+    def _sample(self, net, logits, u, eps, a_ptr, a_stride, B, st):
+        """actions of the step from the policy heads: softmax sampling, or mu + sigma*eps (a2c_gauss_head)"""
+        if self.cont:
+            ops.gauss_head(logits, self.n_act, B, eps=eps, actions_ptr=a_ptr, act_ld=a_stride, st=st)
+        else:
+            ops.softmax_sample(logits, u, a_ptr, a_stride, B, net.output_space, st=st)
+
+    def _env_action(self, na_j, shift):
+        """what env.step receives: int(action) + shift, or the float32 (n,) vector + shift"""
+        if self.cont:
+            return na_j + np.float32(shift)
+        return int(na_j) + shift
+
     def _forward(self, net, x_ptr, bstride, B, env0, st, sampler=None, stash=None):
         """stash = (bufs, row0, row_stride): conv-stack nets write this step's activations into the update's buffers"""
         kw = dict(stash=stash) if (stash is not None and isinstance(stash[0], list)) else {}
@@ -452,16 +492,17 @@ class Runner:
                 hs = D["h_states"]
                 ops.copy_rows(h.data_ptr(), h.shape[1], hs.data_ptr() + 4 * (slot0 * T + t) * h.shape[1],
                               T * h.shape[1], B, h.shape[1], st)
-            u = self._uniforms(t, B, env0)
+            u = self._uniforms(t, B, env0) if not self.cont else None
+            eps = self._normals(t, B, env0) if self.cont else None
             act = self.act_dev[env0:env0 + B]
             if acts_host_out is None:      # device-resident actions buffer: write it in place
-                a_ptr, a_stride = D["actions"].data_ptr() + 8 * (slot0 * T + t), T
+                a_ptr, a_stride = self._act_row(slot0, T, t)
             else:
-                a_ptr, a_stride = act.data_ptr(), 1
-            out = self._forward(net, sp(t), T * S, B, env0, st, sampler=(u, a_ptr, a_stride))
+                a_ptr, a_stride = act.data_ptr(), (self.n_act if self.cont else 1)
+            out = self._forward(net, sp(t), T * S, B, env0, st, sampler=None if self.cont else (u, a_ptr, a_stride))
             logits, vals = out["logits"], out["vals"]
             if not out.get("sampled", False):
-                ops.softmax_sample(logits, u, a_ptr, a_stride, B, net.output_space, st=st)
+                self._sample(net, logits, u, eps, a_ptr, a_stride, B, st)
             if h is not None and out["h"].data_ptr() != h.data_ptr():      # (the GRU models update h in place)
                 ops.copy_rows(out["h"].data_ptr(), h.shape[1], h.data_ptr(), h.shape[1], B, h.shape[1], st)
             fr, rew, done, reset = self._env_step(pool, act, a_ptr, a_stride, env0, B, t, slot0, T, shift, acts_host_out, pong)
@@ -557,7 +598,13 @@ class Runner:
         if getattr(self, "_u_buf", None) is None or self._u_buf.shape != (T, self.B):
             self._u_buf = torch.zeros((T, self.B), dtype=torch.float32, device=dev)
         ub = self._u_buf
-        if self.uniform_fn is not None:
+        if self.cont:       # continuous nets: the slot's N(0,1) noise, one persistent (T, B, n) buffer likewise
+            n = self.n_act
+            if getattr(self, "_e_buf", None) is None or self._e_buf.shape != (T, self.B, n):
+                self._e_buf = torch.zeros((T, self.B, n), dtype=torch.float32, device=dev)
+            for t in range(T):
+                self._e_buf[t, env0:env0 + B].copy_(self._normals(t, B, env0))
+        elif self.uniform_fn is not None:
             for t in range(T):
                 ub[t, env0:env0 + B].copy_(self.uniform_fn(t, B, env0).reshape(B))
         else:
@@ -735,9 +782,9 @@ class Runner:
                 fr = _Frames(ptr32=df.data_ptr())
         act = self.act_dev[env0:env0 + B]
         if c["acts_host_out"] is None:
-            a_ptr, a_stride = D["actions"].data_ptr() + 8 * (slot0 * T + min(k, T - 1)), T
+            a_ptr, a_stride = self._act_row(slot0, T, min(k, T - 1))
         else:
-            a_ptr, a_stride = act.data_ptr(), 1
+            a_ptr, a_stride = act.data_ptr(), (self.n_act if self.cont else 1)
         if c["fused"]:      # a2c_a3c_step: record(k-1) + frame stack + forward + sample (+ bootstrap) in ONE launch
             kw = dict(val_prev=val_prev.data_ptr(), rewards=rewards.data_ptr(), dones=dones.data_ptr(), deltas=deltas.data_ptr(),
                       T=T, slot0=slot0, gamma=float(gamma), pong=int(pong))
@@ -839,7 +886,8 @@ class Runner:
             finally:
                 net._frames_src = None
             if not out.get("sampled", False):
-                ops.softmax_sample(out["logits"], u, a_ptr, a_stride, B, net.output_space, st=st)
+                self._sample(net, out["logits"], u, self._e_buf[k, env0:env0 + B] if self.cont else None, a_ptr, a_stride,
+                             B, st)
             if out.get("h_next_src") is not None:      # cell stash: the next segment's post kernel reads h_new from there
                 pass
             elif h is not None and out["h"].data_ptr() != h.data_ptr():    # (the GRU models update h in place)
@@ -851,11 +899,11 @@ class Runner:
             return
         # the sampled actions go to the host (pinned staging) at the tail of the segment
         ha = self.h_act[env0:env0 + B]
-        if a_stride == 1:
+        if (a_ptr == act.data_ptr()) if self.cont else a_stride == 1:
             ha.copy_(act, non_blocking=True)
         else:
             if getattr(self, "_act_gather", None) is None:
-                self._act_gather = torch.zeros(self.B, dtype=torch.int64, device=net._dev)
+                self._act_gather = torch.zeros_like(self.act_dev)
             ag = self._act_gather[env0:env0 + B]
             ag.copy_(D["actions"][slot0 * T + k::T][:B])
             ha.copy_(ag, non_blocking=True)
@@ -874,7 +922,7 @@ class Runner:
             return
         nf, nr, nd = (x[env0:env0 + B] for x in (self.np_frames, self.np_rew, self.np_done))
         for j in range(B):
-            obs, rew, done = pool.step(env0 + j, int(na[j]) + shift)
+            obs, rew, done = pool.step(env0 + j, self._env_action(na[j], shift))
             self.ep_rew[env0 + j] += rew
             reset = done
             if pong and rew != 0:
@@ -1003,7 +1051,7 @@ class Runner:
 
     def _actions_to_host(self, act, a_stride, env0, B, t, slot0, T):
         ha = self.h_act[env0:env0 + B]
-        if a_stride == 1:
+        if (not self.datas["actions"].is_cuda) if self.cont else a_stride == 1:
             ha.copy_(act, non_blocking=True)
         else:
             ha.copy_(self.datas["actions"][slot0 * T + t::T][:B], non_blocking=True)
@@ -1063,8 +1111,7 @@ class Runner:
         na = self.np_act[env0:env0 + B]
         nf, nr, nd = (x[env0:env0 + B] for x in (self.np_frames, self.np_rew, self.np_done))
         for j in range(B):
-            a = int(na[j])
-            obs, rew, done = pool.step(env0 + j, a + shift)
+            obs, rew, done = pool.step(env0 + j, self._env_action(na[j], shift))
             self.ep_rew[env0 + j] += rew
             reset = done
             if pong and rew != 0:
@@ -1108,10 +1155,11 @@ class StatsRunner:
     estimator over the same number of episodes.  ``StatsRunner(hyps, env=one_env)`` keeps the reference's serial
     loop (same episodes in the same order as the reference) for callers that own a single env object."""
 
-    def __init__(self, hyps, env=None, envs=None, uniform_fn=None):
+    def __init__(self, hyps, env=None, envs=None, uniform_fn=None, normal_fn=None):
         self.hyps = hyps
         self.n_episodes = try_key(hyps, "n_test_eps", 15)
         self.uniform_fn = uniform_fn              # (t, E) -> (E,) device uniforms; default torch.rand
+        self.normal_fn = normal_fn                # continuous nets: (t, E, 0) -> (E, n) device N(0,1); default torch.randn
         self.obs_deque = deque(maxlen=hyps["n_frame_stack"])
         self.envs = list(envs) if envs is not None else None
         self.env = env
@@ -1148,7 +1196,8 @@ class StatsRunner:
         d_frames = torch.zeros(E, HW, **f32)
         cur, nxt = torch.zeros(E, S, **f32), torch.zeros(E, S, **f32)
         ones, zeros = torch.ones(E, **f32), torch.zeros(E, **f32)
-        act_dev = torch.zeros(E, dtype=torch.int64, device=dev)
+        cont, n = not getattr(net, "is_discrete", True), int(net.output_space)
+        act_dev = torch.zeros((E, n), **f32) if cont else torch.zeros(E, dtype=torch.int64, device=dev)
         h = torch.zeros(E, net.h_size, **f32) if net.is_recurrent else None
         d_frames.copy_(h_frames, non_blocking=True)
         ops.frame_stack_push(d_frames, ones, cur.data_ptr(), S, cur.data_ptr(), S, E, C, HW, st)      # [0,..,0, env.reset()]
@@ -1158,7 +1207,10 @@ class StatsRunner:
         t = 0
         max_steps = max_steps or int(try_key(hyps, "max_eval_steps", 10 ** 6))
         while active.any() and t < max_steps:
-            u = self.uniform_fn(t, E) if self.uniform_fn is not None else torch.rand(E, **f32)
+            if cont:
+                eps = self.normal_fn(t, E, 0).reshape(E, n) if self.normal_fn is not None else torch.randn((E, n), **f32)
+            else:
+                u = self.uniform_fn(t, E) if self.uniform_fn is not None else torch.rand(E, **f32)
             if fused:       # state t = push(state t-1, frame) + forward + sample in ONE launch
                 kw = dict(prev=cur.data_ptr(), prev_stride=S) if t == 0 else \
                     dict(prev=cur.data_ptr(), prev_stride=S, frame_new=d_frames.data_ptr(), reset_mask=zeros.data_ptr(),
@@ -1175,13 +1227,15 @@ class StatsRunner:
                 else:
                     out = net._fwd(cur.data_ptr(), S, E, "eval", st, False, sampler=(u, act_dev.data_ptr(), 1)) \
                         if getattr(net, "_fused_sampling", False) else net._fwd(cur.data_ptr(), S, E, "eval", st, False)
-                if not out.get("sampled", False):
+                if cont:
+                    ops.gauss_head(out["logits"], n, E, eps=eps, actions_ptr=act_dev.data_ptr(), act_ld=n, st=st)
+                elif not out.get("sampled", False):
                     ops.softmax_sample(out["logits"], u, act_dev.data_ptr(), 1, E, net.output_space, st=st)
                 if net.is_recurrent:
                     h.copy_(out["h"])
             acts = act_dev.cpu().numpy()                       # the one host round trip of the step
             for j in np.nonzero(active)[0]:
-                obs, rew, done, _ = envs[j].step(int(acts[j]) + shift)
+                obs, rew, done, _ = envs[j].step(acts[j] + np.float32(shift) if cont else int(acts[j]) + shift)
                 ep_rew[j] += rew
                 if pong and rew != 0:
                     done = True

@@ -82,10 +82,20 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
 
     # environments
     serial = try_key(hyps, "env_pool", "process") == "serial"
+    probe = None
     if env_fn is None:
         hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
         probe = eval_env or SequentialEnvironment(**hyps)             # the probe for shapes (training.py:60-65)
         hyps["is_discrete"], n_act = probe.is_discrete, probe.n
+    else:
+        hyps["is_discrete"] = bool(try_key(hyps, "is_discrete", True))
+    if not hyps["is_discrete"]:
+        # float actions do not fit the process pool's int32 command words: continuous envs step in this process
+        if "env_pool" in hyps and hyps["env_pool"] == "process":
+            raise ValueError("a2c_amd: continuous action spaces need env_pool='serial' (the process env pool carries "
+                             "int32 actions)")
+        serial = True
+    if env_fn is None:
         kws = [dict({k: v for k, v in hyps.items() if k != "seed"}, seed=hyps["seed"] + j) for j in range(hyps["n_envs"])]
         if serial:
             envs = [SequentialEnvironment(**kw) for kw in kws]
@@ -108,7 +118,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                                   n_workers=try_key(hyps, "n_env_workers", None), pong="Pong" in hyps["env_type"],
                                   action_shift=1 if hyps["env_type"] == "Pong-v0" else try_key(hyps, "action_shift", 0),
                                   probe_reset=True, frame_bits=bool(try_key(hyps, "frame_bits", False)))
-        hyps["is_discrete"], n_act = True, hyps["action_size"]
+        n_act = hyps["action_size"]
     hyps["state_shape"] = [hyps["n_frame_stack"]] + list(pool.frame_shape[1:])
     if hyps["env_type"] == "Pong-v0":
         action_size, hyps["action_shift"] = 3, 1                      # training.py:67-69
@@ -129,7 +139,10 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                    "deltas": cuda_if(torch.zeros(shared_len)), "rewards": cuda_if(torch.zeros(shared_len)),
                    # (the reference keeps `actions` on the host, training.py:90,97; device resident here so that the
                    # rollout's device relay can write it -- nothing outside this function sees the dict)
-                   "actions": cuda_if(torch.zeros(shared_len).long()), "dones": cuda_if(torch.zeros(shared_len))}
+                   # (continuous actions: one float row of n per sample, training.py:89-92)
+                   "actions": cuda_if(torch.zeros(shared_len).long() if hyps["is_discrete"] else
+                                      torch.zeros((shared_len, action_size))),
+                   "dones": cuda_if(torch.zeros(shared_len))}
     if net.is_recurrent:
         shared_data["h_states"] = cuda_if(torch.zeros(shared_len, net.h_size))
     n_rollouts = hyps["n_rollouts"]

@@ -6,7 +6,8 @@ is_discrete ret_mean ret_std`` (updater.py:9-229).
 One ``update_model`` call enqueues, on one HIP stream and without host round trips until the
 final read-back of five scalars:
   fused GAE + returns scan -> model forward (N = n_rollouts*n_tsteps samples, or the BPTT unroll)
-  -> advantage statistics -> fused loss forward+backward -> model backward into the flat gradient
+  -> advantage statistics -> fused loss forward+backward (continuous actions: Gaussian loss sums [-> all-reduce] ->
+  Gaussian loss forward+backward) -> model backward into the flat gradient
   arena -> [RCCL all-reduce when sharded] -> grad-norm reduction -> fused clip + RMSprop/Adam.
 """
 import torch
@@ -125,8 +126,8 @@ class Updater:
         self.net = net
         self.hyps = hyps
         self.is_discrete = hyps["is_discrete"]
-        if not self.is_discrete:
-            raise NotImplementedError("a2c_amd: continuous action spaces are out of scope (see DESIGN.md)")
+        if bool(self.is_discrete) != bool(getattr(net, "is_discrete", True)):
+            raise ValueError("a2c_amd: hyps['is_discrete'] does not match the net's is_discrete")
         self.shard = shard if shard is not None else Shard()
         self.optim = self.new_optim(hyps["lr"])
         self.info = {}
@@ -155,6 +156,8 @@ class Updater:
                      err=torch.zeros(1, dtype=torch.int32, device=dev),
                      out5=torch.zeros(5, dtype=torch.float64, device=dev),
                      host=torch.zeros(8, dtype=torch.float64).pin_memory() if torch.cuda.is_available() else None)
+            if not self.is_discrete:    # the six Gaussian loss sums (a2c_gauss_loss_sums), all-reduced when sharded
+                b["gsums"] = torch.zeros(6, dtype=torch.float64, device=dev)
             self._bufs = b
         return b
 
@@ -174,8 +177,11 @@ class Updater:
         rewards = self._dev(shared_data["rewards"]).reshape(-1)
         dones = self._dev(shared_data["dones"]).reshape(-1)
         deltas = self._dev(shared_data["deltas"]).reshape(-1)
-        actions = self._dev(shared_data["actions"], torch.int64).reshape(-1)
         N = states.shape[0]
+        if self.is_discrete:
+            actions = self._dev(shared_data["actions"], torch.int64).reshape(-1)
+        else:       # (N, n) float rows (training.py:89-92)
+            actions = self._dev(shared_data["actions"]).reshape(N, net.output_space)
         T = int(hyps["n_tsteps"])
         if N % T:
             raise ValueError("len(states) is not a multiple of n_tsteps")
@@ -228,8 +234,17 @@ class Updater:
             sh.allreduce_(adv_sums)
 
         db, dl, dv = net.dheads("train", N)
-        ops.loss_fwd_bwd(logits, vals, actions, advs, rets, adv_sums, n_global, try_key(hyps, "pi_coef", 1.0), hyps["val_coef"],
-                         hyps["entr_coef"], dl, dv, stats[2:5], st, scratch=b["scratch"])
+        if self.is_discrete:
+            ops.loss_fwd_bwd(logits, vals, actions, advs, rets, adv_sums, n_global, try_key(hyps, "pi_coef", 1.0),
+                             hyps["val_coef"], hyps["entr_coef"], dl, dv, stats[2:5], st, scratch=b["scratch"])
+        else:
+            # the Gaussian loss needs batch-wide sums before any gradient (mse and K of the mu gradient): two launches,
+            # the sums all-reduced in between when sharded (a capture is cut there, like at the advantage moments)
+            n, gs = net.output_space, b["gsums"]
+            ops.gauss_loss_sums(logits, vals, actions, advs, rets, adv_sums, n_global, n, gs, st, scratch=b["scratch"])
+            sh.allreduce_(gs)
+            ops.gauss_loss_fwd_bwd(logits, vals, actions, advs, rets, adv_sums, gs, n_global, n,
+                                   try_key(hyps, "pi_coef", 1.0), hyps["val_coef"], hyps["entr_coef"], dl, dv, stats[2:5], st)
 
         # backward into the flat gradient arena
         if use_bptt:
@@ -330,13 +345,18 @@ class Updater:
         ops.normalize(rets, rets, fake, n_global, 1e-6, st)
 
     def bptt(self, states, h_states, dones):
-        """updater.py:139-169: unrolled recurrent forward; returns (vals (N,), logits (N,A))."""
+        """updater.py:139-169: unrolled recurrent forward; returns (vals (N,), logits (N,A)), or (vals (N,), (mu (N,n),
+        sigma (N,n))) for a continuous net."""
         hyps, net = self.hyps, self.net
         net._ensure_device()
         R, T = int(hyps["n_rollouts"]), int(hyps["n_tsteps"])
+        st = ops.stream()
         vals, logits = net.bptt_forward(self._dev(states), self._dev(h_states), self._dev(dones).reshape(-1), R, T,
-                                        "train", ops.stream())
-        return vals.clone(), logits.clone()
+                                        "train", st)
+        if net.is_discrete:
+            return vals.clone(), logits.clone()
+        mu, sigma = net._policy_out(logits, "train", R * T, st)
+        return vals.clone(), (mu.clone(), sigma.clone())
 
     def gae(self, rewards, values, next_vals, dones, gamma, lambda_):
         """updater.py:172-189 (unused by the reference's own loop; kept for API parity)."""

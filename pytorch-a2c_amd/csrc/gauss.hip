@@ -1,0 +1,202 @@
+// Continuous (Gaussian) action heads of FCModel / GRUFCModel: sigma + sampling, and the reference's Gaussian loss
+// (models.py:396-405, runner.py:98-104, updater.py:108-117).  The heads rows are [mu (n) | raw (n) | value]; sigma =
+// softplus(raw) + 1e-4 with torch's threshold 20.  The loss needs batch-wide sums (F.mse_loss reduces over the whole
+// (N, n) block), so it is two launches: a2c_gauss_loss_sums (fp64 partials, fixed-order grid reduction) and
+// a2c_gauss_loss_fwd_bwd (gradients from the -- possibly all-reduced -- sums).  One lane per row; the rows are short
+// (n <= A2C_GAUSS_MAX_N), so every launch is latency bound at the reference's sizes.
+#include "a2c_common.h"
+
+namespace {
+constexpr float kR2PI = 2.5066282746310002f;     // float(np.sqrt(2*np.pi)) as torch applies it to a float32 tensor
+constexpr int kSumsBlocks = 512;                  // 6 partials per workgroup must fit A2C_REDUCE_SCRATCH_DOUBLES
+static_assert(8 + 6 * kSumsBlocks <= A2C_REDUCE_SCRATCH_DOUBLES, "gauss loss sums: reduce scratch too small");
+
+// torch.nn.functional.softplus (beta 1, threshold 20) + 1e-4
+__device__ __forceinline__ float gauss_sigma(float raw) {
+  return __fadd_rn(raw > 20.f ? raw : log1pf(expf(raw)), 1e-4f);
+}
+
+struct AdvNorm {
+  float mean = 0.f, den = 1.f;
+  bool on = false;
+};
+__device__ __forceinline__ AdvNorm adv_norm(const double* adv_sums, long n_global) {
+  AdvNorm a;
+  if (adv_sums != nullptr) {       // same statistics as loss_kernel (loss.hip) / a2c_normalize
+    const double m = adv_sums[0] / (double)n_global;
+    double var = (adv_sums[1] - (double)n_global * m * m) / (double)(n_global - 1);
+    if (var < 0.0) var = 0.0;
+    a.mean = (float)m;
+    a.den = (float)sqrt(var) + 1e-6f;
+    a.on = true;
+  }
+  return a;
+}
+
+__global__ __launch_bounds__(256) void gauss_head_kernel(const float* __restrict__ heads, long ldh, const float* __restrict__ eps,
+                                                         long lde, float* __restrict__ sigma, long lds,
+                                                         float* __restrict__ actions, long lda, long B, int n) {
+  const long total = B * (long)n;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += gridDim.x * 256L) {
+    const long b = e / n;
+    const int j = (int)(e - b * n);
+    const float* row = heads + b * ldh;
+    const float s = gauss_sigma(row[n + j]);
+    if (sigma != nullptr) sigma[b * lds + j] = s;
+    if (actions != nullptr) actions[b * lda + j] = __fadd_rn(row[j], __fmul_rn(s, eps[b * lde + j]));   // mu + (sigma*eps)
+  }
+}
+
+// sums[0..6) = [sum d^2, sum w/(2c), sum w*l, sum l, sum adv (n == 1), sum (V-R)^2]; w = adv (n >= 2) or 1 (n == 1: the
+// batch mean of the advantages multiplies these two sums in the second launch)
+__global__ __launch_bounds__(256) void gauss_sums_kernel(const float* __restrict__ heads, long ldh, const float* __restrict__ vals,
+                                                         long vstride, const float* __restrict__ actions, long lda,
+                                                         const float* __restrict__ advs, const float* __restrict__ returns,
+                                                         const double* __restrict__ adv_sums, long n_local, long n_global,
+                                                         int n, double* sums, double* scratch) {
+  __shared__ double sm[4];
+  const AdvNorm an = adv_norm(adv_sums, n_global);
+  double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n_local; i += gridDim.x * 256L) {
+    float adv = advs[i];
+    if (an.on) adv = (adv - an.mean) / an.den;
+    const float w = n == 1 ? 1.f : adv;
+    const float* row = heads + i * ldh;
+    const float* act = actions + i * lda;
+    float sd = 0.f, sk = 0.f, sp = 0.f, sl = 0.f;
+    for (int j = 0; j < n; ++j) {
+      const float sg = gauss_sigma(row[n + j]);
+      const float d = row[j] - act[j];
+      const float c = fmaxf(sg * sg, 1e-3f);
+      const float l = logf(fmaxf(kR2PI * sg, 1e-3f));
+      sd += d * d;
+      sk += w / (2.f * c);
+      sp += w * l;
+      sl += l;
+    }
+    const float dv = vals[i * vstride] - returns[i];
+    s[0] += (double)sd;
+    s[1] += (double)sk;
+    s[2] += (double)sp;
+    s[3] += (double)sl;
+    s[4] += n == 1 ? (double)adv : 0.0;
+    s[5] += (double)(dv * dv);
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) s[k] = block_sum_256(s[k], sm);
+  grid_sum_ordered<6>(s, sums, scratch, sm);
+}
+
+__global__ __launch_bounds__(256) void gauss_fwd_bwd_kernel(const float* __restrict__ heads, long ldh,
+                                                            const float* __restrict__ vals, long vstride,
+                                                            const float* __restrict__ actions, long lda,
+                                                            const float* __restrict__ advs, const float* __restrict__ returns,
+                                                            const double* __restrict__ adv_sums, const double* __restrict__ sums,
+                                                            long n_local, long n_global, int n, float pi_coef, float val_coef,
+                                                            float entr_coef, float* __restrict__ dheads, long ldd,
+                                                            float* __restrict__ dvals, long dvstride, double* loss_sums) {
+  const AdvNorm an = adv_norm(adv_sums, n_global);
+  const double M = (double)n_global * (double)n;
+  const double adv_mean = sums[4] / (double)n_global;
+  const double K = n == 1 ? sums[1] * adv_mean : sums[1];
+  const double P = n == 1 ? sums[2] * adv_mean : sums[2];
+  const double mse = sums[0] / M;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    // Updater._finish_host divides every sum by n_global and all-reduces them over the ranks when sharded: each rank
+    // writes its share (n_local / n_global) of the global values (the whole value on one GPU)
+    const double share = (double)n_local / (double)n_global;
+    loss_sums[0] = -(mse * K + P) / (double)n * share;
+    loss_sums[1] = sums[5] * share;
+    loss_sums[2] = sums[3] / (double)n * share;
+  }
+  const float g_mu = (float)((double)pi_coef * K / M * 2.0 / M);     // dL/dmu = g_mu * (mu - a)
+  const float g_pi = (float)((double)pi_coef / M);
+  const float g_en = (float)((double)entr_coef / M);
+  const float mse_f = (float)mse;
+  const float w1 = (float)adv_mean;
+  const float invN = 1.0f / (float)n_global;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n_local; i += gridDim.x * 256L) {
+    float adv = advs[i];
+    if (an.on) adv = (adv - an.mean) / an.den;
+    const float w = n == 1 ? w1 : adv;
+    const float* row = heads + i * ldh;
+    const float* act = actions + i * lda;
+    float* drow = dheads + i * ldd;
+    for (int j = 0; j < n; ++j) {
+      const float raw = row[n + j];
+      const float sg = gauss_sigma(raw);
+      const float s2 = sg * sg;
+      const float c = fmaxf(s2, 1e-3f);
+      const float q = kR2PI * sg;
+      // torch's clamp backward passes the gradient where input >= min
+      const float dc = s2 >= 1e-3f ? 2.f * sg : 0.f;
+      const float dl = q >= 1e-3f ? kR2PI / q : 0.f;
+      const float dsig = g_pi * w * (-mse_f / (2.f * c * c) * dc + dl) + g_en * dl;
+      float draw = dsig;
+      if (!(raw > 20.f)) {             // softplus backward: g * z / (z + 1), z = exp(raw)
+        const float z = expf(raw);
+        draw = dsig * z / (z + 1.f);
+      }
+      drow[j] = g_mu * (row[j] - act[j]);
+      drow[n + j] = draw;
+    }
+    const float dv = vals[i * vstride] - returns[i];
+    dvals[i * dvstride] = val_coef * 2.f * dv * invN;
+  }
+}
+}  // namespace
+
+extern "C" int a2c_gauss_head(const float* heads, int64_t ld_heads, const float* eps, int64_t ld_eps, float* sigma,
+                              int64_t ld_sigma, float* actions, int64_t ld_act, int64_t B, int n, a2c_stream_t stream) {
+  if (B < 0 || n < 1 || n > A2C_GAUSS_MAX_N || ld_heads < 2 * n) return A2C_ERR_ARG;
+  if (sigma == nullptr && actions == nullptr) return A2C_ERR_ARG;
+  if (sigma != nullptr && ld_sigma < n) return A2C_ERR_ARG;
+  if (actions != nullptr && (eps == nullptr || ld_eps < n || ld_act < n)) return A2C_ERR_ARG;
+  if (B == 0) return A2C_OK;
+  if (heads == nullptr) return A2C_ERR_ARG;
+  hipLaunchKernelGGL(gauss_head_kernel, dim3(a2c_grid_1d(B * n, 256)), dim3(256), 0, a2c_s(stream), heads, (long)ld_heads,
+                     eps, (long)ld_eps, sigma, (long)ld_sigma, actions, (long)ld_act, (long)B, n);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+extern "C" int a2c_gauss_loss_sums(const float* heads, int64_t ld_heads, const float* vals, int64_t val_stride,
+                                   const float* actions, int64_t ld_act, const float* advs, const float* returns,
+                                   const double* adv_sums, int64_t n_local, int64_t n_global, int n, double* sums,
+                                   double* scratch, a2c_stream_t stream) {
+  if (n_local < 0 || n_global < n_local || n_global < 1 || n < 1 || n > A2C_GAUSS_MAX_N || !sums || !scratch)
+    return A2C_ERR_ARG;
+  if (adv_sums && n_global < 2) return A2C_ERR_ARG;
+  if (n_local == 0) {
+    a2c_zero_async(sums, 6 * sizeof(double), a2c_s(stream));
+    return A2C_OK;
+  }
+  if (!heads || !vals || !actions || !advs || !returns || ld_heads < 2 * n || ld_act < n) return A2C_ERR_ARG;
+  hipLaunchKernelGGL(gauss_sums_kernel, dim3(a2c_grid_1d(n_local, 256, kSumsBlocks)), dim3(256), 0, a2c_s(stream), heads,
+                     (long)ld_heads, vals, (long)val_stride, actions, (long)ld_act, advs, returns, adv_sums, (long)n_local,
+                     (long)n_global, n, sums, scratch);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+extern "C" int a2c_gauss_loss_fwd_bwd(const float* heads, int64_t ld_heads, const float* vals, int64_t val_stride,
+                                      const float* actions, int64_t ld_act, const float* advs, const float* returns,
+                                      const double* adv_sums, const double* sums, int64_t n_local, int64_t n_global, int n,
+                                      float pi_coef, float val_coef, float entr_coef, float* dheads, int64_t ldd,
+                                      float* dvals, int64_t dval_stride, double* loss_sums, a2c_stream_t stream) {
+  if (n_local < 0 || n_global < n_local || n_global < 1 || n < 1 || n > A2C_GAUSS_MAX_N || !sums || !loss_sums)
+    return A2C_ERR_ARG;
+  if (adv_sums && n_global < 2) return A2C_ERR_ARG;
+  if (n_local == 0) {
+    a2c_zero_async(loss_sums, 3 * sizeof(double), a2c_s(stream));
+    return A2C_OK;
+  }
+  if (!heads || !vals || !actions || !advs || !returns || !dheads || !dvals || ld_heads < 2 * n || ld_act < n || ldd < 2 * n)
+    return A2C_ERR_ARG;
+  hipLaunchKernelGGL(gauss_fwd_bwd_kernel, dim3(a2c_grid_1d(n_local, 256)), dim3(256), 0, a2c_s(stream), heads,
+                     (long)ld_heads, vals, (long)val_stride, actions, (long)ld_act, advs, returns, adv_sums, sums,
+                     (long)n_local, (long)n_global, n, pi_coef, val_coef, entr_coef, dheads, (long)ldd, dvals,
+                     (long)dval_stride, loss_sums);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
