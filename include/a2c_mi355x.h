@@ -603,7 +603,9 @@ int a2c_conv2d_bwd_data_signs_supported(const a2c_conv_desc *d);
  * a lane's float4 are one nibble, two neighbouring lanes make a byte.  Producers: a2c_a3c_rollout's ring kernel
  * (a1_lanemask_rows) or a2c_lanemask_from_act over any tensor whose float count is a multiple of 256.
  * din = conv_transpose(dout, W) * bit: the same values as a2c_conv2d_bwd_data with the float mask, bit for bit, for 1/32 of
- * the mask's HBM reads.  _supported(d, B) = 1 when a2c_conv2d_bwd_data_lanemask can run (layer shape, Cin*H*W % 256 == 0,
+ * the mask's HBM reads -- at any A2C_BWD_X6 setting: both calls take the same kernel for the layer, batch and switch
+ * (the bf16 six-product kernel by default, the fp32 MFMA streaming kernel with A2C_BWD_X6=0), only the mask's encoding
+ * differs.  _supported(d, B) = 1 when a2c_conv2d_bwd_data_lanemask can run (layer shape, Cin*H*W % 256 == 0,
  * B large enough for the streaming kernel); otherwise use a2c_conv2d_bwd_data with the float mask.                     */
 int a2c_lanemask_from_act(const float *act, uint64_t *lanemask, int64_t n_floats, a2c_stream_t stream);
 int a2c_conv2d_bwd_data_lanemask_supported(const a2c_conv_desc *d, int B);

@@ -129,6 +129,27 @@ class _HipNet(nn.Module):
     def _stash_valid(self, x_ptr, n_rows):
         return getattr(self, "_stash", None) == (x_ptr, int(n_rows))
 
+    # the switches an update reads on its way round the stash (models.py only; the runner's are seen through what it stashed)
+    _ROUTE_SWITCHES = ("A2C_NO_STASH", "A2C_NO_LANEMASK", "A2C_NO_EMB_STASH", "A2C_NO_CELL_STASH", "A2C_NO_HEADS_STASH",
+                       "A2C_NO_FRAME_STORE")
+
+    def _route_state(self):
+        """what the last rollout left in the net for the update: (stash, frame store, lane masks, cells)"""
+        return (self._stash, self._stash_frames, getattr(self, "_stash_lm", False), getattr(self, "_cells_done", None))
+
+    def _set_route_state(self, rs):
+        self._stash, self._stash_frames, self._stash_lm, cells = rs
+        if cells is not None:
+            self._cells_done = cells
+
+    def _route_sig(self):
+        """What an update reads besides its buffers and the weights: which rows the stash covers, the frame store, A3CModel's
+        lane masks, GRUModel's cell stash, and the switches read on that route.  Two updates of the same buffers and weights
+        with equal signatures take the same launches (a captured update is only valid for the signature it was captured at)."""
+        st, fr, lm, cells = self._route_state()
+        return (st, None if fr is None else (fr[0].data_ptr(), fr[1].data_ptr(), int(fr[2])), bool(lm), cells,
+                tuple(os.environ.get(k) == "1" for k in self._ROUTE_SWITCHES))
+
     def _need_states(self):
         """about to read the fp32 `states` rows: a rollout that kept the single-frame store only (hyps['lazy_states'])
         materialises them now (Runner.materialize_states)"""

@@ -10,6 +10,8 @@ final read-back of five scalars:
   Gaussian loss forward+backward) -> model backward into the flat gradient
   arena -> [RCCL all-reduce when sharded] -> grad-norm reduction -> fused clip + RMSprop/Adam.
 """
+import sys
+
 import torch
 
 from . import ops, optim as fused_optim
@@ -47,9 +49,13 @@ class _CutShard:
 class _GraphedUpdate:
     def __init__(self, upd, shared_data):
         self.upd, self.graphs, self.colls = upd, [], []
+        self.shared = shared_data
+        self.fallbacks = 0          # replays that ran the eager update instead (the net's route had changed since the capture)
         net = upd.net
         torch.cuda.synchronize()
-        dirty, stash, cells = net._dirty, net._stash, getattr(net, "_cells_done", None)
+        dirty, route = net._dirty, net._route_state()
+        # the route the captured launches take: the rollout's stash, lane masks, frame store and cells, and the switches
+        self.route_sig = net._route_sig()
         real = upd.shard
         upd.shard = _CutShard(self, real)
         self._ctx = None
@@ -68,11 +74,23 @@ class _GraphedUpdate:
         finally:
             upd.shard = real
         self.prep_sig = net._prep_sig() if hasattr(net, "_prep_sig") else ""
-        # the capture itself executed nothing: the net is still in the state the rollout left it in
-        net._dirty, net._stash = dirty, stash
-        if cells is not None:
-            net._cells_done = cells
+        # the capture itself executed nothing: the net is still in the state the rollout left it in (the optimiser step's
+        # mark_dirty cleared all of the stash, not only its rows)
+        net._dirty = dirty
+        net._set_route_state(route)
         upd.optim._steps -= 1
+
+    def _stale_route(self):
+        """the rollout before this replay left the net on another route than the captured one (a partial or split rollout: no
+        stash; no ring kernel: no lane masks; ...): the captured launches would read what an EARLIER rollout left behind"""
+        if self.upd.net._route_sig() == self.route_sig:
+            return False
+        self.fallbacks += 1
+        if not getattr(self.upd, "_fallback_warned", False):
+            self.upd._fallback_warned = True
+            sys.stderr.write("a2c_amd: captured update replayed after a rollout that left the net on another route "
+                             "(stash / lane masks / frame store / cells / switches): running the eager update instead\n")
+        return True
 
     def _stale_prep(self):
         net = self.upd.net
@@ -95,6 +113,8 @@ class _GraphedUpdate:
 
     def replay(self):
         upd = self.upd
+        if self._stale_route():
+            return upd.update_model(self.shared)
         for i, g in enumerate(self.graphs):
             g.replay()
             if i < len(self.colls):
@@ -111,6 +131,8 @@ class _GraphedUpdate:
         """replay() without the blocking read-back: -> token for Updater.collect(token) (the five scalars travel to a
         pinned host buffer behind the update on the stream; the caller may enqueue the NEXT rollout before collecting)"""
         upd = self.upd
+        if self._stale_route():
+            return upd.update_model_async(self.shared)
         for i, g in enumerate(self.graphs):
             g.replay()
             if i < len(self.colls):
@@ -278,7 +300,11 @@ class Updater:
         graph, ... -- so that N-GPU updates are not ~40 eager launches either and no collective sits inside a capture.
         Returns a callable ``replay() -> info`` (same effect as update_model on the same buffers); the caller must
         have run one eager update_model on these buffers first (workspaces, tuners, one-time hipMalloc / hipMemset of
-        the GEMM and conv launchers: none of that is legal inside a capture)."""
+        the GEMM and conv launchers: none of that is legal inside a capture).  The captured launches follow the route the
+        preceding rollout left in the net (net._route_sig: stash, lane masks, frame store, cells, switches); a replay after a
+        rollout that left another route runs the eager update_model instead (``.fallbacks`` counts those, one warning on
+        stderr), so a replay never reads the activations of an earlier rollout.  Every rank of a sharded update decides
+        alike when its rollouts were alike."""
         if not getattr(self.optim, "capture_safe", False):
             # Adam's bias correction takes the step count as a KERNEL ARGUMENT: a replay would apply the captured
             # step's correction for ever

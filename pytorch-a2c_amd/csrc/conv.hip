@@ -1786,7 +1786,7 @@ __global__ __launch_bounds__(BS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 // bwd_x6_kernel (round 6): the same layer -- A3CModel conv2's backward-data, 32 -> 16 channels, 4 x 4, stride 2, 9 x 9 ->
 // 20 x 20 -- on the BF16 matrix pipe with fp32 results.  bwd_stream2_kernel is bound by the fp32 MFMAs it issues (82 TF, the
 // pipe 54 % busy in step-locked phases); here both operands are split into three bf16 pieces (exact) and
-// the six piece products with qa + qb <= 2 are issued (the dropped ones are below 2^-24 of |a b|: gemm_x6_kernel's argument),
+// the six piece products with qa + qb <= 2 are issued (the dropped ones are below 2^-23 of |a b|: gemm_x6_kernel's argument),
 // 6 v_mfma_f32_16x16x32_bf16 (16 cycles) per 32-deep k step instead of 8 v_mfma_f32_16x16x4_f32 (32 cycles): 0.375 of the
 // matrix time.  What makes the layer fit the bf16 instruction:
 //   * all four output-parity classes gather the SAME dOut pixels: dX[ci][2cy+ry][2cx+rx] = sum over taps (a, b) and co of
@@ -1805,7 +1805,7 @@ constexpr int BX_NT = 512, BX_SLOT0 = 81, BX_GST = 82 * 8, BX_PST = 4 * BX_GST, 
 typedef __bf16 bf16x8x __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4x __attribute__((ext_vector_type(4)));
 struct BwdX6P {
-  const float* dout; float* din; const float* wfrag; const unsigned long long* lmask;
+  const float* dout; float* din; const float* wfrag; const unsigned long long* lmask; const float* mask;
   int lmw, B;
   int frag_off[4];
   // RANK: dOut is not read but formed while the sample is staged -- dOut[e] = (a2[e] > 0) ? sum_n dl[n] Wc[n][e] : 0, the sums of
@@ -1829,7 +1829,7 @@ __device__ __forceinline__ void bx_split8(const float e[8], u32x4x o[3]) {
     o[q] = (u32x4x){(unsigned int)pc[q][0] | ((unsigned int)pc[q][1] << 16), (unsigned int)pc[q][2] | ((unsigned int)pc[q][3] << 16),
                     (unsigned int)pc[q][4] | ((unsigned int)pc[q][5] << 16), (unsigned int)pc[q][6] | ((unsigned int)pc[q][7] << 16)};
 }
-template <int MODE, bool RANK = false>               // MODE 0: no mask, 2: lane masks
+template <int MODE, bool RANK = false>               // MODE 0: no mask, 1: float mask, 2: lane masks
 __global__ __launch_bounds__(BX_NT) void bwd_x6_kernel(BwdX6P p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsx[];
   unsigned short* __restrict__ img = reinterpret_cast<unsigned short*>(ldsx);          // dOut of the sample, three piece images
@@ -1924,7 +1924,7 @@ __global__ __launch_bounds__(BX_NT) void bwd_x6_kernel(BwdX6P p) {
     }                                                                                                       \
     bx_split8(pre, so);                                                                                     \
   }
-#define BX_FLUSH(u, pb_, ob_)                                                                               \
+#define BX_FLUSH(mv, u, pb_, ob_)                                                                               \
   {                                                                                                         \
     const int q_ = tid + (u) * BX_NT;                                                                       \
     if (q_ < N4) {                                                                                          \
@@ -1938,12 +1938,19 @@ __global__ __launch_bounds__(BX_NT) void bwd_x6_kernel(BwdX6P p) {
         if (!(nb_ & 4u)) v_.z = 0.f;                                                                        \
         if (!(nb_ & 8u)) v_.w = 0.f;                                                                        \
       }                                                                                                     \
+      if (MODE == 1) {                   /* (mask > 0) exactly as the lane masks encode it: NaN, 0, -0 -> 0 */   \
+        if (!(mv.x > 0.f)) v_.x = 0.f;                                                                      \
+        if (!(mv.y > 0.f)) v_.y = 0.f;                                                                      \
+        if (!(mv.z > 0.f)) v_.z = 0.f;                                                                      \
+        if (!(mv.w > 0.f)) v_.w = 0.f;                                                                      \
+      }                                                                                                     \
       *reinterpret_cast<float4*>(dst_ + i_) = v_;                                                           \
     }                                                                                                       \
   }
   long pb = -1;
   int cur = 0;
   unsigned int lmb = 0;
+  float4 m0 = {}, m1 = {}, m2 = {}, m3 = {};                  // MODE 1: the float mask of sample pb, this thread's flush units
   __syncthreads();                                            // the zero pixels (RANK: the composed matrix)
   BX_FORM()
   for (; b < p.B; b += gridDim.x) {
@@ -1957,13 +1964,18 @@ __global__ __launch_bounds__(BX_NT) void bwd_x6_kernel(BwdX6P p) {
     __syncthreads();
     if (pb >= 0) {                                              // the previous sample's dX: stores first
       const float* __restrict__ ob = outb0 + (cur ^ 1) * OBS;
-      BX_FLUSH(0, pb, ob) BX_FLUSH(1, pb, ob) BX_FLUSH(2, pb, ob) BX_FLUSH(3, pb, ob)
+      BX_FLUSH(m0, 0, pb, ob) BX_FLUSH(m1, 1, pb, ob) BX_FLUSH(m2, 2, pb, ob) BX_FLUSH(m3, 3, pb, ob)
     }
     unsigned int lb0 = 0, lb1 = 0, lb2 = 0, lb3 = 0;
     if (MODE == 2) {           // THIS sample's mask bits (its flush is the next iteration's first act): one byte per flush unit
       const unsigned char* __restrict__ lmp = reinterpret_cast<const unsigned char*>(p.lmask) + b * (long)p.lmw * 8;
       lb0 = lmp[min((tid + 0 * BX_NT) >> 1, N4 / 2 - 1)]; lb1 = lmp[min((tid + 1 * BX_NT) >> 1, N4 / 2 - 1)];
       lb2 = lmp[min((tid + 2 * BX_NT) >> 1, N4 / 2 - 1)]; lb3 = lmp[min((tid + 3 * BX_NT) >> 1, N4 / 2 - 1)];
+    }
+    if (MODE == 1) {           // THIS sample's float mask, issued before the next sample's dOut (the flush above is done with m)
+      const float4* __restrict__ mp = reinterpret_cast<const float4*>(p.mask + b * (long)OBS);
+      m0 = mp[min(tid + 0 * BX_NT, N4 - 1)]; m1 = mp[min(tid + 1 * BX_NT, N4 - 1)];
+      m2 = mp[min(tid + 2 * BX_NT, N4 - 1)]; m3 = mp[min(tid + 3 * BX_NT, N4 - 1)];
     }
     if (RANK) { BX_LDR(nb) } else { BX_LDD(nsrc) }
     {
@@ -2011,7 +2023,7 @@ __global__ __launch_bounds__(BX_NT) void bwd_x6_kernel(BwdX6P p) {
   }
   {
     const float* __restrict__ ob = outb0 + (cur ^ 1) * OBS;
-    BX_FLUSH(0, pb, ob) BX_FLUSH(1, pb, ob) BX_FLUSH(2, pb, ob) BX_FLUSH(3, pb, ob)
+    BX_FLUSH(m0, 0, pb, ob) BX_FLUSH(m1, 1, pb, ob) BX_FLUSH(m2, 2, pb, ob) BX_FLUSH(m3, 3, pb, ob)
   }
 #undef BX_FLUSH
 #undef BX_LDD
@@ -4399,21 +4411,25 @@ int conv_bwd_data_generic(const a2c_conv_desc* d, const float* dout, const float
         const size_t slds2 = 4 * ((size_t)d->Cout * q.PLANE + 64 + 2 * (size_t)d->Cin * d->H * d->W);
         if (slds2 > LDS_HARD_MAX || (lmask && n4 % 64)) return A2C_ERR_ARG;
         if (probe_only && !rank) return A2C_OK;
-        {  // the bf16 x 6 form (bwd_x6_kernel): exactly A3CModel's conv2, mask as bits or none; A2C_BWD_X6=0 keeps the fp32 MFMA kernels
-          if (d->Cout == 32 && d->Cin == 16 && d->OH == 9 && d->OW == 9 && d->H == 20 && d->W == 20 && P == 0 && (lmask || !mask) &&
+        {  // the bf16 x 6 form (bwd_x6_kernel): exactly A3CModel's conv2, with every mask encoding (lane masks, float mask or none),
+           // so that the kernel -- and dX, bit for bit -- does not depend on how the mask came; A2C_BWD_X6=0 keeps the fp32 MFMA kernels
+          if (d->Cout == 32 && d->Cin == 16 && d->OH == 9 && d->OW == 9 && d->H == 20 && d->W == 20 && P == 0 &&
               a2c_env_int("A2C_BWD_X6", 1) != 0) {
             if (probe_only) return A2C_OK;
             BwdX6P xp;
-            xp.dout = dout; xp.din = din; xp.wfrag = wprep_bwd; xp.lmask = lmask; xp.lmw = n4 / 64 * 4; xp.B = B;
+            xp.dout = dout; xp.din = din; xp.wfrag = wprep_bwd; xp.lmask = lmask; xp.mask = lmask ? nullptr : mask;
+            xp.lmw = n4 / 64 * 4; xp.B = B;
             for (int cls = 0; cls < 4; ++cls) xp.frag_off[cls] = q.cls[cls].frag_off;
             xp.dl = nullptr; xp.ldl = 0; xp.nlog = 0; xp.Wc = nullptr; xp.a2b = nullptr; xp.a2b_row = 0;
             if (rank) { xp.dl = rank->dl; xp.ldl = rank->ldl; xp.nlog = rank->nlog; xp.Wc = rank->Wc; xp.a2b = rank->a2b; xp.a2b_row = rank->a2b_row; }
             const size_t xlds = 2 * (size_t)BX_IMG + 2 * 4 * (size_t)d->Cin * d->H * d->W + (rank ? 16 * 2592 : 0);
-            const void* xk = rank ? (const void*)bwd_x6_kernel<2, true> : lmask ? (const void*)bwd_x6_kernel<2> : (const void*)bwd_x6_kernel<0>;
+            const void* xk = rank ? (const void*)bwd_x6_kernel<2, true> : lmask ? (const void*)bwd_x6_kernel<2>
+                           : mask ? (const void*)bwd_x6_kernel<1> : (const void*)bwd_x6_kernel<0>;
             if (xlds > 64 * 1024) (void)hipFuncSetAttribute(xk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds);
             const int xgrid = resident_grid(xk, xlds, B, BX_NT);
             if (rank) hipLaunchKernelGGL((bwd_x6_kernel<2, true>), dim3(xgrid), dim3(BX_NT), xlds, a2c_s(stream), xp);
             else if (lmask) hipLaunchKernelGGL(bwd_x6_kernel<2>, dim3(xgrid), dim3(BX_NT), xlds, a2c_s(stream), xp);
+            else if (mask) hipLaunchKernelGGL(bwd_x6_kernel<1>, dim3(xgrid), dim3(BX_NT), xlds, a2c_s(stream), xp);
             else hipLaunchKernelGGL(bwd_x6_kernel<0>, dim3(xgrid), dim3(BX_NT), xlds, a2c_s(stream), xp);
             A2C_CHECK_LAUNCH();
             return A2C_OK;

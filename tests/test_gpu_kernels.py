@@ -920,6 +920,55 @@ def test_conv2d_backward_data_on_the_bf16_pipe_is_the_fp32_sum(monkeypatch, B):
         assert e6 <= 1.5 * e32 + 1e-7, (i, e6, e32)
 
 
+@pytest.mark.parametrize("B", [2048 + 55, 4096])
+def test_conv2d_backward_data_float_mask_equals_lane_masks_at_default_switches(monkeypatch, B):
+    """At DEFAULT switches (bf16 x 6 form) A3CModel's conv2 backward-data gives the same dX bit for bit whichever way its ReLU
+    mask comes -- the float activation (an update after a rollout without the ring kernel) or lane masks (after a ring rollout)
+    -- so an update does not depend on the rollout before it; zero, -0, a denormal and NaN activations mask as (x > 0).  Both
+    against the fp64 transposed convolution no worse than 1.5 x the fp32 MFMA kernel's error (A2C_BWD_X6=0), masked alike."""
+    ops = _ops()
+    monkeypatch.delenv("A2C_BWD_X6", raising=False)
+    d = ops.conv_desc(16, 20, 20, 32, 4, 2, 0)
+    assert ops.conv_bwd_data_lanemask_supported(d, B)
+    gen = torch.Generator().manual_seed(23)
+    w = ((torch.rand(32, 16, 4, 4, generator=gen) - 0.5) * 0.2)
+    dout = ((torch.rand(B, 32, 9, 9, generator=gen) - 0.5) * (torch.rand(B, 32, 9, 9, generator=gen) < 0.6).float())
+    dout[1] = torch.randn(32, 9, 9, generator=gen) * 1e3                      # a dense sample at another scale
+    act = torch.relu(torch.rand(B, 16, 20, 20, generator=gen) - 0.4)
+    special = torch.tensor([0.0, -0.0, 1e-45, float("nan")])                  # zero, negative zero, a denormal, NaN: (x > 0)
+    for b in (0, B // 2, B - 1):
+        act[b, 0, 0, :4] = special
+        act[b, 15, 19, 16:20] = special.flip(0)
+    doutd, actd = dout.to(DEV), act.to(DEV)
+    lm = torch.zeros(B, 6400 // 64, dtype=torch.int64, device=DEV)
+    ops.lanemask_from_act(actd, lm)
+    wb = torch.empty(ops.conv_prep_floats(d, 1), device=DEV)
+    ops.conv_prep(d, 1, w.to(DEV), wb)
+    got = torch.full((B, 16, 20, 20), float("nan"), device=DEV)
+    ops.conv_bwd_data(d, doutd, wb, actd, got, B)
+    want = torch.full((B, 16, 20, 20), float("nan"), device=DEV)
+    ops.conv_bwd_data_lanemask(d, doutd, wb, lm, want, B)
+    torch.cuda.synchronize()
+    assert not bool(torch.isnan(got).any())                                   # every sample written, NaN masks to 0
+    assert torch.equal(got, want)
+    keep = act > 0
+    for b in (0, B // 2, B - 1):      # zero, -0 and NaN mask to 0; the denormal is > 0 and keeps its dX
+        assert not bool(got[b, 0, 0, [0, 1, 3]].cpu().any()) and not bool(got[b, 15, 19, [16, 18, 19]].cpu().any())
+    monkeypatch.setenv("A2C_BWD_X6", "0")
+    g32 = torch.full((B, 16, 20, 20), float("nan"), device=DEV)
+    ops.conv_bwd_data(d, doutd, wb, actd, g32, B)
+    torch.cuda.synchronize()
+    assert not torch.equal(got, g32)                                          # (the bf16 kernel did run at default switches)
+    got, g32 = got.cpu(), g32.cpu()
+    idx = torch.cat([torch.arange(0, 48), torch.tensor([B // 2]), torch.arange(B - 16, B)])
+    ref = torch.nn.functional.conv_transpose2d(dout[idx].double(), w.double(), stride=2) * keep[idx]
+    for i in range(len(idx)):
+        rms = float(ref[i].pow(2).mean().sqrt())
+        e6 = float((got[idx[i]].double() - ref[i]).pow(2).mean().sqrt()) / rms
+        e32 = float((g32[idx[i]].double() - ref[i]).pow(2).mean().sqrt()) / rms
+        assert e6 <= 1.5 * e32 + 1e-7, (i, e6, e32)
+
+
 @pytest.mark.parametrize("B,pad", [(2048 + 55, 0), (4096, 64)])
 def test_conv2d_weight_gradient_on_the_bf16_pipe_is_the_fp32_sum(monkeypatch, B, pad):
     """wgrad_x6_kernel (default for A3CModel's conv2 at streaming batch): dOut and the activations split into three bf16 pieces

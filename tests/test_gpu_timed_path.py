@@ -111,6 +111,7 @@ def test_graphed_update_replays_equal_eager_updates_and_the_oracle(kind, ingest,
         # the optimiser state the replays left is the eager twin's, bit for bit
         for a, b in zip(eg.upd.optim._flat.values(), ee.upd.optim._flat.values()):
             assert torch.equal(a, b)
+        assert eg.g.fallbacks == 0          # bench.py's sequence (full rollout -> replay) always replays the graph
     finally:
         eg.close()
         ee.close()
@@ -159,19 +160,27 @@ def _graphed_shard_worker(rank, world, port, kind, q, ss):
                 Dl[k].copy_(new[k])
         if u == 0:
             infos.append(upd.update_model(Dl))
+        elif u == 3:
+            # a replay after a rollout that left the net on another route (here: no stash, A2C_NO_STASH=1 as a rollout of
+            # the other switch setting would leave it) falls back to the eager update -- on every rank alike, so the
+            # collectives stay paired
+            os.environ["A2C_NO_STASH"] = "1"
+            infos.append(g.replay())
+            del os.environ["A2C_NO_STASH"]
         else:
             if g is None:
                 g = upd.capture_update(Dl)
             infos.append(g.replay())
-    q.put((rank, infos, [p.detach().cpu().numpy() for p in net.parameters()], len(g.graphs), len(g.colls)))
+    q.put((rank, infos, [p.detach().cpu().numpy() for p in net.parameters()], len(g.graphs), len(g.colls), g.fallbacks))
     dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("kind", ["A3CModel", "GRUModel"])
 def test_sharded_graphed_update_equals_single_process_eager(kind):
     """world 2 (gloo all-reduce of CUDA tensors): update 0 eager, then capture_update and three replays on new data --
-    3 graphs around 2 collectives (advantage moments; gradient arena + loss sums) -- against four single-process eager
-    updates on the whole batch."""
+    3 graphs around 2 collectives (advantage moments; gradient arena + loss sums), the last replay on another route than
+    the captured one (the eager fallback, taken on both ranks) -- against four single-process eager updates on the whole
+    batch."""
     from a2c_amd.updater import Updater
     from test_gpu_system import _free_port
     ss, A, h, R, T = (4, 84, 84), 3, 256, 4, 6
@@ -199,8 +208,8 @@ def test_sharded_graphed_update_equals_single_process_eager(kind):
     # the fourth; everything <= 1e-6 before; 1,603 of 1,037,692 parameters further than 4e-6 in the worst of them).  So:
     # updates 0 and 1 tight, 2 and 3 at 5e-4; parameters within 10 lr, all but half a percent of them within 4e-6.  A stale
     # buffer or a missed replay input is O(1) in every info.
-    for rank, infos, params, n_graphs, n_colls in res:
-        assert (n_graphs, n_colls) == (3, 2)
+    for rank, infos, params, n_graphs, n_colls, n_fallbacks in res:
+        assert (n_graphs, n_colls, n_fallbacks) == (3, 2, 1)
         for u in range(4):
             for k in ref_infos[u]:
                 assert infos[u][k] == pytest.approx(ref_infos[u][k], rel=2e-5 if u < 2 else 5e-4, abs=1e-7), (rank, u, k)
@@ -318,6 +327,7 @@ def test_full_size_headline_update_matches_the_oracle_updater(layout, monkeypatc
             else:
                 g = upd.capture_update(D)
                 info = upd.collect(g.replay_async())                        # bench.py's timed step
+                assert g.fallbacks == 0                                     # ... on the captured route
             assert not upd.flat_scan_fallback
             if store:
                 assert r._states_stale                                      # ... and the update never asked for one
@@ -375,7 +385,9 @@ def test_full_size_conv_32x64_update_matches_the_oracle_updater(layout, monkeypa
             if ep == 0:
                 info = upd.update_model(D)
             else:
-                info = upd.collect(upd.capture_update(D).replay_async())
+                g = upd.capture_update(D)
+                info = upd.collect(g.replay_async())
+                assert g.fallbacks == 0
             if store:
                 assert r._states_stale
                 r.materialize_states()
