@@ -761,6 +761,40 @@ int a2c_clip_rmsprop(float *params, float *grads, float *square_avg, int64_t n,
 int a2c_clip_adam(float *params, float *grads, float *exp_avg, float *exp_avg_sq, int64_t n,
                   const double *sumsq, double max_norm, double lr, double beta1, double beta2,
                   double eps, int64_t step, float *norm_out, a2c_stream_t stream);
+/* the same clip fused with the step of the other torch.optim optimisers, torch's defaults for every setting that is
+ * not an argument (no momentum, no weight decay apart from AdamW's, no maximize / amsgrad).  One launch each, same
+ * validation as a2c_clip_adam: A2C_ERR_ARG on a NULL or non-16-B-aligned array or step < 1, n == 0 is a no-op.
+ * Step-dependent scalars are host doubles; `step` is the 1-based step count.                                   */
+int a2c_clip_sgd(float *params, float *grads, int64_t n, const double *sumsq, double max_norm, double lr,
+                 float *norm_out, a2c_stream_t stream);
+/* clr = lr / (1 + (step-1) lr_decay) */
+int a2c_clip_adagrad(float *params, float *grads, float *sum, int64_t n, const double *sumsq, double max_norm,
+                     double lr, double lr_decay, double eps, int64_t step, float *norm_out, a2c_stream_t stream);
+int a2c_clip_adadelta(float *params, float *grads, float *square_avg, float *acc_delta, int64_t n,
+                      const double *sumsq, double max_norm, double lr, double rho, double eps, float *norm_out,
+                      a2c_stream_t stream);
+/* step_size must hold lr before the first step (torch fills it then); grads keep the clipped, UNmasked gradient */
+int a2c_clip_rprop(float *params, float *grads, float *prev, float *step_size, int64_t n, const double *sumsq,
+                   double max_norm, double etaminus, double etaplus, double step_size_min, double step_size_max,
+                   float *norm_out, a2c_stream_t stream);
+/* params *= 1 - lr weight_decay, then the Adam step */
+int a2c_clip_adamw(float *params, float *grads, float *exp_avg, float *exp_avg_sq, int64_t n,
+                   const double *sumsq, double max_norm, double lr, double beta1, double beta2, double eps,
+                   double weight_decay, int64_t step, float *norm_out, a2c_stream_t stream);
+int a2c_clip_adamax(float *params, float *grads, float *exp_avg, float *exp_inf, int64_t n, const double *sumsq,
+                    double max_norm, double lr, double beta1, double beta2, double eps, int64_t step,
+                    float *norm_out, a2c_stream_t stream);
+/* mu_product = the fp32 state value after this step's mu_product *= mu */
+int a2c_clip_nadam(float *params, float *grads, float *exp_avg, float *exp_avg_sq, int64_t n,
+                   const double *sumsq, double max_norm, double lr, double beta1, double beta2, double eps,
+                   double momentum_decay, int64_t step, double mu_product, float *norm_out,
+                   a2c_stream_t stream);
+int a2c_clip_radam(float *params, float *grads, float *exp_avg, float *exp_avg_sq, int64_t n,
+                   const double *sumsq, double max_norm, double lr, double beta1, double beta2, double eps,
+                   int64_t step, float *norm_out, a2c_stream_t stream);
+/* eta, mu = the fp32 state values the previous step stored (lr and 1 before the first) */
+int a2c_clip_asgd(float *params, float *grads, float *ax, int64_t n, const double *sumsq, double max_norm,
+                  double lambd, double eta, double mu, float *norm_out, a2c_stream_t stream);
 
 /* out5 = [loss_sums[0..2], grad_norm, err]: the five scalars update_model reads back (updater.py:134-136)
  * gathered into ONE device buffer for a single D2H copy                                  */

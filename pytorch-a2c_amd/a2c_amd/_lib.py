@@ -172,6 +172,19 @@ SIGNATURES = {
     "a2c_clip_rmsprop": (c_int, [P, P, P, c_int64, P, c_double, c_double, c_double, c_double, P, P]),
     "a2c_clip_adam": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_double, c_double, c_double,
                                c_int64, P, P]),
+    "a2c_clip_sgd": (c_int, [P, P, c_int64, P, c_double, c_double, P, P]),
+    "a2c_clip_adagrad": (c_int, [P, P, P, c_int64, P, c_double, c_double, c_double, c_double, c_int64, P, P]),
+    "a2c_clip_adadelta": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_double, c_double, P, P]),
+    "a2c_clip_rprop": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_double, c_double, c_double, P, P]),
+    "a2c_clip_adamw": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_double, c_double, c_double, c_double,
+                                c_int64, P, P]),
+    "a2c_clip_adamax": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_double, c_double, c_double, c_int64,
+                                 P, P]),
+    "a2c_clip_nadam": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_double, c_double, c_double, c_double,
+                                c_int64, c_double, P, P]),
+    "a2c_clip_radam": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_double, c_double, c_double, c_int64,
+                                P, P]),
+    "a2c_clip_asgd": (c_int, [P, P, P, c_int64, P, c_double, c_double, c_double, c_double, P, P]),
 }
 
 _lib = None

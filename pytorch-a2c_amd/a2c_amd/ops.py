@@ -1103,3 +1103,60 @@ def clip_adam(params, grads, exp_avg, exp_avg_sq, sumsq, max_norm, lr, beta1, be
     check(lib().a2c_clip_adam(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), params.numel(), _p(sumsq),
                               max_norm, lr, beta1, beta2, eps, step, _p(norm_out),
                               st if st is not None else stream()), "a2c_clip_adam")
+
+
+def _st(st):
+    return st if st is not None else stream()
+
+
+def clip_sgd(params, grads, sumsq, max_norm, lr, norm_out, st=None):
+    check(lib().a2c_clip_sgd(_p(params), _p(grads), params.numel(), _p(sumsq), max_norm, lr, _p(norm_out), _st(st)),
+          "a2c_clip_sgd")
+
+
+def clip_adagrad(params, grads, state_sum, sumsq, max_norm, lr, lr_decay, eps, step, norm_out, st=None):
+    check(lib().a2c_clip_adagrad(_p(params), _p(grads), _p(state_sum), params.numel(), _p(sumsq), max_norm, lr,
+                                 lr_decay, eps, step, _p(norm_out), _st(st)), "a2c_clip_adagrad")
+
+
+def clip_adadelta(params, grads, square_avg, acc_delta, sumsq, max_norm, lr, rho, eps, norm_out, st=None):
+    check(lib().a2c_clip_adadelta(_p(params), _p(grads), _p(square_avg), _p(acc_delta), params.numel(), _p(sumsq),
+                                  max_norm, lr, rho, eps, _p(norm_out), _st(st)), "a2c_clip_adadelta")
+
+
+def clip_rprop(params, grads, prev, step_size, sumsq, max_norm, etaminus, etaplus, step_size_min, step_size_max,
+               norm_out, st=None):
+    check(lib().a2c_clip_rprop(_p(params), _p(grads), _p(prev), _p(step_size), params.numel(), _p(sumsq), max_norm,
+                               etaminus, etaplus, step_size_min, step_size_max, _p(norm_out), _st(st)),
+          "a2c_clip_rprop")
+
+
+def clip_adamw(params, grads, exp_avg, exp_avg_sq, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step,
+               norm_out, st=None):
+    check(lib().a2c_clip_adamw(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), params.numel(), _p(sumsq),
+                               max_norm, lr, beta1, beta2, eps, weight_decay, step, _p(norm_out), _st(st)),
+          "a2c_clip_adamw")
+
+
+def clip_adamax(params, grads, exp_avg, exp_inf, sumsq, max_norm, lr, beta1, beta2, eps, step, norm_out, st=None):
+    check(lib().a2c_clip_adamax(_p(params), _p(grads), _p(exp_avg), _p(exp_inf), params.numel(), _p(sumsq),
+                                max_norm, lr, beta1, beta2, eps, step, _p(norm_out), _st(st)), "a2c_clip_adamax")
+
+
+def clip_nadam(params, grads, exp_avg, exp_avg_sq, sumsq, max_norm, lr, beta1, beta2, eps, momentum_decay, step,
+               mu_product, norm_out, st=None):
+    """mu_product: the fp32 state value after this step's ``mu_product *= mu``"""
+    check(lib().a2c_clip_nadam(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), params.numel(), _p(sumsq),
+                               max_norm, lr, beta1, beta2, eps, momentum_decay, step, mu_product, _p(norm_out),
+                               _st(st)), "a2c_clip_nadam")
+
+
+def clip_radam(params, grads, exp_avg, exp_avg_sq, sumsq, max_norm, lr, beta1, beta2, eps, step, norm_out, st=None):
+    check(lib().a2c_clip_radam(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), params.numel(), _p(sumsq),
+                               max_norm, lr, beta1, beta2, eps, step, _p(norm_out), _st(st)), "a2c_clip_radam")
+
+
+def clip_asgd(params, grads, ax, sumsq, max_norm, lambd, eta, mu, norm_out, st=None):
+    """eta, mu: the fp32 state values the previous step stored"""
+    check(lib().a2c_clip_asgd(_p(params), _p(grads), _p(ax), params.numel(), _p(sumsq), max_norm, lambd, eta, mu,
+                              _p(norm_out), _st(st)), "a2c_clip_asgd")

@@ -1,20 +1,30 @@
 """Fused clip + optimiser steps over the flat parameter arena (updater.py:129-132, 226-229).
 
-``RMSprop`` / ``Adam`` are ``torch.optim.Optimizer`` subclasses whose ``state_dict()`` has the
-same layout as ``torch.optim.RMSprop`` / ``torch.optim.Adam`` (param indices follow
-``net.parameters()``, per-parameter ``step`` / ``square_avg`` / ``exp_avg`` / ``exp_avg_sq``), so
-``optim.p`` checkpoints (training.py:127-128, updater.py:218-219) load either way.  The state
-tensors are views into flat HBM buffers parallel to the net's arena; one kernel launch updates
-every parameter (torch defaults otherwise: alpha .99 / betas (.9,.999), eps 1e-8, no momentum,
-no weight decay, no amsgrad -- the reference only ever passes ``lr``).
+Every optimiser here is a ``torch.optim.Optimizer`` subclass whose ``state_dict()`` has the layout of the
+``torch.optim`` class of the same name (param indices follow ``net.parameters()``, per-parameter ``step`` and the
+rule's state), so ``optim.p`` checkpoints (training.py:127-128, updater.py:218-219) load either way.  The state
+tensors are views into flat HBM buffers parallel to the net's arena; one kernel launch updates every parameter.
+Settings are torch's defaults apart from ``lr`` (the reference only ever passes ``lr``): RMSprop / Adam and the
+other torch optimisers that step without a closure (``OPTIMIZERS``).  A loaded param_group that asks for something
+the kernels do not implement (momentum, maximize, amsgrad, weight decay outside AdamW, ...) raises ``ValueError``.
 """
+import numpy as np
 import torch
 
 from . import ops
 
 
+def _f32(x):
+    """a python float rounded to fp32, as torch stores a 0-d float32 state tensor"""
+    return float(np.float32(x))
+
+
 class _Fused(torch.optim.Optimizer):
-    _state_names = ()
+    _state_names = ()            # state arrays parallel to the trainable arena
+    _scalars = ()                # per-parameter 0-d fp32 state, one value for every parameter, kept on the host
+    _stateless = False           # torch keeps no state at all (SGD without momentum): no `step` either
+    _eager = False               # torch creates the state of EVERY parameter at construction (Adagrad)
+    _fixed = {}                  # param_group settings the kernel does not implement -> the one value it accepts
     capture_safe = False
 
     def __init__(self, net, lr, defaults):
@@ -28,36 +38,54 @@ class _Fused(torch.optim.Optimizer):
         self._scratch = None         # this optimiser's own reduction scratch (ops.new_reduce_scratch), made on first use
         self._norm = torch.zeros(1, dtype=torch.float32, device=ar.params.device)
         self._steps = 0
+        self._scal = {}              # host values of self._scalars (set by the first step, or loaded)
         self._name_of = {id(p): n for n, p in net.named_parameters()}
+        if self._eager:
+            self._publish_state()
 
     def _views(self, p):
         o, k, shp = self.net._arena.offsets[self._name_of[id(p)]]
         return {s: self._flat[s][o:o + k].view(shp) for s in self._state_names}
 
+    def _trainable(self, p):
+        return self._name_of[id(p)] in self.net._arena.trainable
+
     def _publish_state(self):
-        """Expose the flat state as torch-style per-parameter entries (lazily, like torch)."""
-        ar = self.net._arena
+        """Expose the flat state as torch-style per-parameter entries (lazily, like torch, unless _eager)."""
+        if self._stateless:
+            return
         for p in self.param_groups[0]["params"]:
-            if self._name_of[id(p)] not in ar.trainable:
+            if not self._trainable(p):
+                if self._eager and "step" not in self.state[p]:    # never gets a gradient: torch's initial state
+                    self.state[p].update(step=torch.tensor(0.0, dtype=torch.float32),
+                                         **{s: torch.zeros_like(p) for s in self._state_names})
                 continue
             st = self.state[p]
             if "step" not in st:
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
                 st.update(self._views(p))
             st["step"].fill_(float(self._steps))
+            for k in self._scalars:
+                st[k] = torch.tensor(self._scal[k], dtype=torch.float32)
 
     def state_dict(self):
-        if self._steps > 0:
+        if self._steps > 0 or self._eager:
             self._publish_state()
         return super().state_dict()
 
+    def _check_group(self, group):
+        for k, want in self._fixed.items():
+            if k in group and group[k] != want:
+                raise ValueError(f"a2c_amd: {type(self).__name__} implements {k}={want!r} only, got {group[k]!r}")
+
     def load_state_dict(self, state_dict):
+        for g in state_dict["param_groups"]:
+            self._check_group(g)
         super().load_state_dict(state_dict)
-        ar = self.net._arena
         steps = 0
         for p in self.param_groups[0]["params"]:
             st = self.state.get(p)
-            if not st:
+            if not st or not self._trainable(p):
                 continue
             views = self._views(p)
             for s in self._state_names:
@@ -65,6 +93,9 @@ class _Fused(torch.optim.Optimizer):
                 st[s] = views[s]
             steps = max(steps, int(float(st["step"])))
             st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
+            for k in self._scalars:
+                self._scal[k] = _f32(float(st[k]))
+                st[k] = torch.tensor(self._scal[k], dtype=torch.float32)
         self._steps = steps
 
     def zero_grad(self, set_to_none=False):
@@ -75,14 +106,20 @@ class _Fused(torch.optim.Optimizer):
         """Pre-clip global gradient norm of the last step (device float tensor)."""
         return self._norm
 
+    def _first_step(self):
+        """torch's lazy state initialisation at the first step (besides the zeroed arrays): per-rule"""
+
     @torch.no_grad()
     def step(self, closure=None, max_norm=None, st=None):
+        self._check_group(self.param_groups[0])
         ar = self.net._arena
         st = st if st is not None else ops.stream()
         g = ar.train_grads()
         if self._scratch is None or self._scratch.device != g.device:
             self._scratch = ops.new_reduce_scratch(g.device)
         ops.gradnorm_sq(g, self._stats[:1], st, scratch=self._scratch)
+        if self._steps == 0:
+            self._first_step()
         self._steps += 1
         self._launch(ar.train_params(), g, float("1e30") if max_norm is None else float(max_norm), st)
         self.net.mark_dirty()
@@ -113,3 +150,174 @@ class Adam(_Fused):
         grp = self.param_groups[0]
         ops.clip_adam(p, g, self._flat["exp_avg"], self._flat["exp_avg_sq"], self._stats, max_norm, grp["lr"],
                       grp["betas"][0], grp["betas"][1], grp["eps"], self._steps, self._norm, st)
+
+
+def _torch_defaults(name, lr):
+    """the param_group settings of torch.optim.<name>(params, lr=lr): the same keys and default values as torch"""
+    d = dict(getattr(torch.optim, name)([torch.zeros(1, requires_grad=True)], lr=lr).defaults)
+    del d["lr"]
+    return d
+
+
+_NO_DECAY = dict(weight_decay=0, maximize=False)
+
+
+class SGD(_Fused):
+    _stateless = True
+    _fixed = dict(momentum=0, dampening=0, nesterov=False, **_NO_DECAY)
+    capture_safe = True
+
+    def __init__(self, net, lr=1e-3):
+        super().__init__(net, lr, _torch_defaults("SGD", lr))
+
+    def _launch(self, p, g, max_norm, st):
+        ops.clip_sgd(p, g, self._stats, max_norm, self.param_groups[0]["lr"], self._norm, st)
+
+
+class Adagrad(_Fused):
+    _state_names = ("sum",)
+    _eager = True
+    _fixed = dict(initial_accumulator_value=0, **_NO_DECAY)
+
+    def __init__(self, net, lr=1e-2):
+        super().__init__(net, lr, _torch_defaults("Adagrad", lr))
+
+    @property
+    def capture_safe(self):      # clr = lr / (1 + (step-1) lr_decay) is a kernel argument unless lr_decay == 0
+        return self.param_groups[0]["lr_decay"] == 0
+
+    def _launch(self, p, g, max_norm, st):
+        grp = self.param_groups[0]
+        ops.clip_adagrad(p, g, self._flat["sum"], self._stats, max_norm, grp["lr"], grp["lr_decay"], grp["eps"],
+                         self._steps, self._norm, st)
+
+
+class Adadelta(_Fused):
+    _state_names = ("square_avg", "acc_delta")
+    _fixed = _NO_DECAY
+    capture_safe = True
+
+    def __init__(self, net, lr=1.0):
+        super().__init__(net, lr, _torch_defaults("Adadelta", lr))
+
+    def _launch(self, p, g, max_norm, st):
+        grp = self.param_groups[0]
+        ops.clip_adadelta(p, g, self._flat["square_avg"], self._flat["acc_delta"], self._stats, max_norm, grp["lr"],
+                          grp["rho"], grp["eps"], self._norm, st)
+
+
+class Rprop(_Fused):
+    _state_names = ("prev", "step_size")
+    _fixed = dict(maximize=False)
+    capture_safe = True          # step_size is filled with lr by the first (eager) step, not by the kernel
+
+    def __init__(self, net, lr=1e-2):
+        super().__init__(net, lr, _torch_defaults("Rprop", lr))
+
+    def _first_step(self):
+        self._flat["step_size"].fill_(self.param_groups[0]["lr"])      # torch.full_like(grad, lr)
+
+    def _launch(self, p, g, max_norm, st):
+        grp = self.param_groups[0]
+        ops.clip_rprop(p, g, self._flat["prev"], self._flat["step_size"], self._stats, max_norm, grp["etas"][0],
+                       grp["etas"][1], grp["step_sizes"][0], grp["step_sizes"][1], self._norm, st)
+
+
+class AdamW(_Fused):
+    _state_names = ("exp_avg", "exp_avg_sq")
+    _fixed = dict(amsgrad=False, maximize=False, decoupled_weight_decay=True)
+
+    def __init__(self, net, lr=1e-3):
+        super().__init__(net, lr, _torch_defaults("AdamW", lr))
+
+    def _launch(self, p, g, max_norm, st):
+        grp = self.param_groups[0]
+        ops.clip_adamw(p, g, self._flat["exp_avg"], self._flat["exp_avg_sq"], self._stats, max_norm, grp["lr"],
+                       grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], self._steps, self._norm, st)
+
+
+class Adamax(_Fused):
+    _state_names = ("exp_avg", "exp_inf")
+    _fixed = _NO_DECAY
+
+    def __init__(self, net, lr=2e-3):
+        super().__init__(net, lr, _torch_defaults("Adamax", lr))
+
+    def _launch(self, p, g, max_norm, st):
+        grp = self.param_groups[0]
+        ops.clip_adamax(p, g, self._flat["exp_avg"], self._flat["exp_inf"], self._stats, max_norm, grp["lr"],
+                        grp["betas"][0], grp["betas"][1], grp["eps"], self._steps, self._norm, st)
+
+
+class NAdam(_Fused):
+    _state_names = ("exp_avg", "exp_avg_sq")
+    _scalars = ("mu_product",)
+    _fixed = dict(decoupled_weight_decay=False, **_NO_DECAY)
+
+    def __init__(self, net, lr=2e-3):
+        super().__init__(net, lr, _torch_defaults("NAdam", lr))
+
+    def _first_step(self):
+        self._scal["mu_product"] = 1.0
+
+    def _launch(self, p, g, max_norm, st):
+        grp = self.param_groups[0]
+        beta1 = grp["betas"][0]
+        mu = beta1 * (1.0 - 0.5 * (0.96 ** (self._steps * grp["momentum_decay"])))
+        self._scal["mu_product"] = _f32(self._scal["mu_product"] * _f32(mu))            # fp32 `mu_product *= mu`
+        ops.clip_nadam(p, g, self._flat["exp_avg"], self._flat["exp_avg_sq"], self._stats, max_norm, grp["lr"], beta1,
+                       grp["betas"][1], grp["eps"], grp["momentum_decay"], self._steps, self._scal["mu_product"],
+                       self._norm, st)
+
+
+class RAdam(_Fused):
+    _state_names = ("exp_avg", "exp_avg_sq")
+    _fixed = dict(decoupled_weight_decay=False, **_NO_DECAY)
+
+    def __init__(self, net, lr=1e-3):
+        super().__init__(net, lr, _torch_defaults("RAdam", lr))
+
+    def _launch(self, p, g, max_norm, st):
+        grp = self.param_groups[0]
+        ops.clip_radam(p, g, self._flat["exp_avg"], self._flat["exp_avg_sq"], self._stats, max_norm, grp["lr"],
+                       grp["betas"][0], grp["betas"][1], grp["eps"], self._steps, self._norm, st)
+
+
+class ASGD(_Fused):
+    _state_names = ("ax",)
+    _scalars = ("eta", "mu")
+    _fixed = _NO_DECAY
+
+    def __init__(self, net, lr=1e-2):
+        super().__init__(net, lr, _torch_defaults("ASGD", lr))
+
+    def _first_step(self):
+        self._scal.update(eta=_f32(self.param_groups[0]["lr"]), mu=1.0)
+
+    def _launch(self, p, g, max_norm, st):
+        grp = self.param_groups[0]
+        # this step uses the eta / mu the previous one stored, then stores the next ones (fp32 0-d tensors in torch)
+        ops.clip_asgd(p, g, self._flat["ax"], self._stats, max_norm, grp["lambd"], self._scal["eta"], self._scal["mu"],
+                      self._norm, st)
+        lr, lambd, step = grp["lr"], grp["lambd"], float(self._steps)
+        self._scal["eta"] = _f32(lr / ((1 + lambd * lr * step) ** grp["alpha"]))
+        self._scal["mu"] = _f32(1 / max(1, step - grp["t0"]))
+
+
+# Updater.new_optim's registry: hyps["optim_type"] -> class.  The reference builds any torch.optim class by name;
+# the ones missing here cannot run on the reference's nets either, or do not map onto the flat arena.
+OPTIMIZERS = {c.__name__: c for c in (RMSprop, Adam, SGD, Adagrad, Adadelta, Rprop, AdamW, Adamax, NAdam, RAdam, ASGD)}
+UNSUPPORTED = {
+    "LBFGS": "its step() needs a closure",
+    "SparseAdam": "it takes sparse gradients only",
+    "Muon": "it takes 2-D parameters only",
+    "Adafactor": "its factored row / column state does not map onto the flat parameter arena",
+}
+
+
+def check_name(name):
+    """ValueError unless ``name`` is in OPTIMIZERS (no device work)"""
+    if name not in OPTIMIZERS:
+        why = f" ({UNSUPPORTED[name]})" if name in UNSUPPORTED else ""
+        raise ValueError(f"a2c_amd: optim_type {name!r} is not supported{why}; supported: {', '.join(OPTIMIZERS)}")
+    return OPTIMIZERS[name]

@@ -8,7 +8,7 @@ final read-back of five scalars:
   fused GAE + returns scan -> model forward (N = n_rollouts*n_tsteps samples, or the BPTT unroll)
   -> advantage statistics -> fused loss forward+backward (continuous actions: Gaussian loss sums [-> all-reduce] ->
   Gaussian loss forward+backward) -> model backward into the flat gradient
-  arena -> [RCCL all-reduce when sharded] -> grad-norm reduction -> fused clip + RMSprop/Adam.
+  arena -> [RCCL all-reduce when sharded] -> grad-norm reduction -> fused clip + optimiser step (optim.OPTIMIZERS).
 """
 import sys
 
@@ -145,6 +145,7 @@ class _GraphedUpdate:
 
 class Updater:
     def __init__(self, net, hyps, shard=None):
+        fused_optim.check_name(hyps["optim_type"])      # before any device work: an unsupported name is a ValueError
         self.net = net
         self.hyps = hyps
         self.is_discrete = hyps["is_discrete"]
@@ -306,8 +307,8 @@ class Updater:
         stderr), so a replay never reads the activations of an earlier rollout.  Every rank of a sharded update decides
         alike when its rollouts were alike."""
         if not getattr(self.optim, "capture_safe", False):
-            # Adam's bias correction takes the step count as a KERNEL ARGUMENT: a replay would apply the captured
-            # step's correction for ever
+            # Adam's bias correction (and the other step-dependent scalars: NAdam's mu, ASGD's eta, ...) takes the step
+            # count as a KERNEL ARGUMENT: a replay would apply the captured step's values for ever
             raise RuntimeError(f"a2c_amd: {type(self.optim).__name__}.step cannot be captured into a hipGraph "
                                "(its step count is a kernel argument); use update_model")
         if self._bufs is None:
@@ -415,4 +416,4 @@ class Updater:
         self.optim = new_optim
 
     def new_optim(self, lr):
-        return getattr(fused_optim, self.hyps["optim_type"])(self.net, lr=lr)
+        return fused_optim.check_name(self.hyps["optim_type"])(self.net, lr=lr)
