@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the A2C rollout+update hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload a3c|conv|gru|gru_bptt|fc] [--ingest ...] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload a3c|conv|gru|gru_bptt|fc] [--ingest ...] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: a rollout of n_envs x n_tsteps env-steps followed
 by one Updater.update_model (GAE/returns scan, forward, loss, backward, clip + optimiser).
@@ -22,7 +22,9 @@ Multi-GPU: weak scaling, every rank plays its own n_envs envs (own pool); one RC
 gradient arena (+ 2 tiny ones for the whole-batch statistics) per update.  ``python bench.py --gpus N``
 without a launcher spawns ``torch.distributed.run`` itself (before this process touches the GPU).
 
-Prints ONE JSON line (rank 0, <= 4 KB: compact_line), the full report goes to gpurun_out/bench_full_<tag>.json and stderr:
+Prints ONE JSON line (rank 0, <= 4 KB: compact_line) and the full report on stderr.  A plain run sets up, warms up, times
+the steps, writes --dump-outputs and prints the line: nothing else.  ``--full`` adds every figure that takes runs of its
+own, writes the full report to a side file (write_side_file, named by the line's `full_report`) and puts these in the line:
   "roofline":     the kernel the epoch spends most time in.  For the persistent ring rollout kernel `frac` is PER PIPE:
                   achieved / the rate at which this instruction mix would run with every MFMA at its own pipe's peak
                   (conv1 is issued as three exact bf16 products, the rest as fp32 MFMAs: ring_roofline) = matrix time at
@@ -35,7 +37,10 @@ Prints ONE JSON line (rank 0, <= 4 KB: compact_line), the full report goes to gp
   value_<config>: the other BASELINE.json configs (conv 32x64, gru+BPTT 256x128, a3c at 32 / 2048 envs, and the per-GPU shard
                   of configs[4]: ConvModel 256x128 on Breakout-like grey frames over the uint8 transport, --grey),
   value_one_env_thread / host_us_per_env_step / predicted_8rank_weak: the headline with ONE env thread (what a rank of an
-                  8-rank run on a 16-CPU quota has) and 8 x that -- a prediction, not a scaling measurement.
+                  8-rank run on a 16-CPU quota has) and 8 x that -- a prediction, not a scaling measurement,
+  allreduce_ms_per_update: (N > 1) the gradient all-reduce timed on its own.
+--no-configs, --no-secondary and --no-cpu-baseline leave parts of --full out; --no-kernel-timers leaves out the per-site timers
+and the roofline, and the HIP events (rollout_ms, update_ms) of the timed steps of any run.
 """
 import argparse
 import json
@@ -859,6 +864,9 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rollout buffers, losses, parameters) "
                          "as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else: per-site timers and rooflines, the secondary legs, the "
+                         "other BASELINE configs, the CPU baselines, the all-reduce; full report in a side file")
     ap.add_argument("--no-update-graph", action="store_true", help="do not capture the update into a hipGraph")
     ap.add_argument("--frame-store", action="store_true",
                     help="force the single-frame uint8 rollout store + lazy fp32 states (SURVEY.md 8 row f4); it is the default "
@@ -940,6 +948,7 @@ def main():
         elapsed = float(t[0].item())
         if sustained:
             sustained["seconds"] = round(float(t[1].item()), 3)
+    if shard.active and args.full:
         # cost of the one gradient all-reduce per update, timed on its own
         g = b.net._arena.train_grads()
         for _ in range(3):
@@ -952,7 +961,7 @@ def main():
         torch.cuda.synchronize()
         allreduce_ms = e0.elapsed_time(e1) / 10
     summ = None
-    if not args.no_kernel_timers:
+    if args.full and not args.no_kernel_timers:
         summ = b.site_timers(2)
     ingest_desc = b.describe_ingest()
     zero_copy = args.ingest != "device-tape" and b.runner._zero_copy_ok(b.net)
@@ -1005,7 +1014,8 @@ def main():
     if shard.active:
         out["rccl_ranks"] = torch.distributed.get_world_size() if torch.distributed.get_backend() == "nccl" else 0
         out["dist_backend"] = torch.distributed.get_backend()
-        out["allreduce_ms_per_update"] = round(allreduce_ms, 4)
+        if allreduce_ms is not None:
+            out["allreduce_ms_per_update"] = round(allreduce_ms, 4)
         out["allreduce_bytes"] = int(b.net._arena.n_train * 4)
 
     # ---- rooflines
@@ -1091,7 +1101,7 @@ def main():
     del b
     torch.cuda.empty_cache()
 
-    if shard.world == 1:
+    if args.full and shard.world == 1:
         out["scan_roofline"] = scan_roofline(dev)
         if not args.no_secondary and args.workload == "a3c":
             # kernel-side evidence without the ingest: the round-1 path (frames already in HBM, rollout as a hipGraph of
@@ -1255,7 +1265,7 @@ def main():
                         sample="ConvModel's measured per-sample rates (conv_32x64 entry) at N = 32,768 per GPU")
                 out["cpu_baselines"] = cbs
     tag = f"{args.workload}_n{shard.world}" + (f"_e{args.n_envs}" if args.n_envs else "")
-    side = write_side_file(out, tag)
+    side = write_side_file(out, tag) if args.full else None
     print("[bench] full report: " + json.dumps(_finite(out)), file=sys.stderr)
     print(compact_line(out, side), file=json_out)
     json_out.flush()

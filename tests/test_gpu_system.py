@@ -321,7 +321,7 @@ def test_bench_spawns_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, A2C_BENCH_ONE_DEVICE="1", A2C_DIST_BACKEND="gloo")
     env.pop("RANK", None), env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                           "--n-envs", "16", "--n-workers", "1", "--sustain-steps", "0", "--no-cpu-baseline", "--no-configs",
                           "--no-secondary"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -344,7 +344,7 @@ def test_bench_strong_scaling_conv_world2():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, A2C_BENCH_ONE_DEVICE="1", A2C_DIST_BACKEND="gloo")
     env.pop("RANK", None), env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                           "--workload", "conv", "--global-envs", "16", "--n-workers", "1", "--sustain-steps", "0",
                           "--no-cpu-baseline", "--no-configs", "--no-secondary"], capture_output=True, text=True, env=env,
                          timeout=900)
@@ -366,7 +366,7 @@ def test_bench_world2_a3c_ring_with_two_env_threads_per_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, A2C_BENCH_ONE_DEVICE="1", A2C_DIST_BACKEND="gloo")
     env.pop("RANK", None), env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2",
                           "--n-envs", "64", "--n-workers", "2", "--sustain-steps", "0", "--no-cpu-baseline", "--no-configs",
                           "--no-secondary"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -378,6 +378,26 @@ def test_bench_world2_a3c_ring_with_two_env_threads_per_rank():
     full = json.load(open(os.path.join(root, d["full_report"])))
     assert all(np.isfinite(v) for v in full["last_info"].values()), full["last_info"]
     assert d["roofline"]["kernel"].startswith("a3c_ring_kernel")
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the contract's keys for the K timed steps, and none of
+    the figures that take runs of their own (per-site timers and rooflines, secondary legs, CPU baselines), no side file"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--n-envs", "16", "--n-workers", "1"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["metric"] == "env-steps/sec (rollout+update)" and d["unit"] == "env-steps/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["config"]["ingest"] == "host-pinned/zero-copy-persistent/native"
+    extras = ("roofline", "cpu_baseline", "cpu_baseline_values", "full_report", "scan_roofline_frac_saturating")
+    assert not [k for k in d if k in extras or k.startswith("value_")], d
 
 
 # ---------------------------------------------------------------------------------------------- the update through torch.ops

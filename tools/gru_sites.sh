@@ -1,9 +1,7 @@
 #!/bin/bash
 # per-site update timers of the GRU+BPTT config:  tools/gru_sites.sh [ENV=val ...]
-env "$@" timeout 500 python bench.py --workload gru_bptt --steps 6 --warmup 2 --sustain-steps 0 --no-configs --no-secondary --no-cpu-baseline > /dev/null 2>/tmp/gru_err.log
-python - <<PY
-import json
-d=json.load(open("gpurun_out/bench_full_gru_bptt_n1.json"))
-ls=d.get("update_launch_sites_ms") or {}
-print("$*", d["value"], d["rollout_ms"], d["update_ms"], " ".join(f"{k}={v['avg_ms']:.3f}" for k,v in ls.items() if k.startswith("conv") and "data" in k))
-PY
+env "$@" timeout 500 python bench.py --full --workload gru_bptt --steps 6 --warmup 2 --sustain-steps 0 --no-configs --no-secondary --no-cpu-baseline 2>/dev/null | tail -1 | python -c '
+import json,sys
+d=json.loads(sys.stdin.read()); f=json.load(open(d["full_report"]))
+ls=f.get("update_launch_sites_ms") or {}
+print(sys.argv[1], d["value"], d["rollout_ms"], d["update_ms"], " ".join("%s=%.3f" % (k, v["avg_ms"]) for k,v in ls.items() if k.startswith("conv") and "data" in k))' "$*"

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_r2
 mkdir -p $O
-BENCH="python3 $R/bench.py --steps 20 --warmup 3 --sustain-steps 0 --no-configs --no-secondary --no-cpu-baseline"
+BENCH="python3 $R/bench.py --full --steps 20 --warmup 3 --sustain-steps 0 --no-configs --no-secondary --no-cpu-baseline"
 # 1. kernel trace + stats of the headline bench (host-pinned ingest)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $BENCH > $O/trace.json 2> $O/trace.err
 # 2. the same with the device tape (per-launch step kernel, round-1 style)

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_r4
 mkdir -p $O
-COMMON="--sustain-steps 0 --no-configs --no-secondary --no-cpu-baseline"
+COMMON="--full --sustain-steps 0 --no-configs --no-secondary --no-cpu-baseline"
 # 1. kernel trace + stats: headline (A3CModel 256x128, packed transport, ring kernel) and the other BASELINE configs
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_a3c -- python3 $R/bench.py --steps 20 --warmup 3 $COMMON > $O/trace_a3c.json 2> $O/trace_a3c.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_conv32 -- python3 $R/bench.py --workload conv --steps 10 --warmup 3 $COMMON > $O/trace_conv32.json 2> $O/trace_conv32.err

@@ -115,7 +115,7 @@ for n in ("liba2c_mi355x.so", "liba2c_hostpool.so", "liba2c_torch_ops.so"):
     if os.path.exists(pth):
         libs[n] = hashlib.sha256(open(pth, "rb").read()).hexdigest()
 json.dump(dict(round=rnd, csrc_sha256=bench.csrc_sha256(), libraries_sha256=libs, git_head=None,
-               commands=["python3 bench.py --steps 20 --warmup 3 --sustain-steps 0 --no-configs --no-secondary --no-cpu-baseline (trace, headline)",
+               commands=["python3 bench.py --full --steps 20 --warmup 3 --sustain-steps 0 --no-configs --no-secondary --no-cpu-baseline (trace, headline)",
                          "... --workload conv | --workload gru_bptt | --workload conv --n-envs 256 (traces)",
                          "--pmc FETCH_SIZE / WRITE_SIZE / two SQ passes on the headline and on gru_bptt, --no-kernel-timers"],
                note="git_head is filled in by tools/profile_commit.py in the container (the GPU box has no .git); bench.py compares "
