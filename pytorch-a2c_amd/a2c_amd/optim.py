@@ -19,6 +19,18 @@ def _f32(x):
     return float(np.float32(x))
 
 
+def nadam_mu_product(mu_product, step, beta1, momentum_decay):
+    """torch's fp32 ``mu_product *= mu`` at the 1-based ``step``: the python-float mu is rounded to fp32, then the product"""
+    mu = beta1 * (1.0 - 0.5 * (0.96 ** (step * momentum_decay)))
+    return _f32(mu_product * _f32(mu))
+
+
+def asgd_eta_mu(step, lr, lambd, alpha, t0):
+    """the fp32 (eta, mu) torch's ASGD stores at the end of the 1-based ``step``, for the next step to use"""
+    step = float(step)
+    return _f32(lr / ((1 + lambd * lr * step) ** alpha)), _f32(1 / max(1, step - t0))
+
+
 class _Fused(torch.optim.Optimizer):
     _state_names = ()            # state arrays parallel to the trainable arena
     _scalars = ()                # per-parameter 0-d fp32 state, one value for every parameter, kept on the host
@@ -263,8 +275,7 @@ class NAdam(_Fused):
     def _launch(self, p, g, max_norm, st):
         grp = self.param_groups[0]
         beta1 = grp["betas"][0]
-        mu = beta1 * (1.0 - 0.5 * (0.96 ** (self._steps * grp["momentum_decay"])))
-        self._scal["mu_product"] = _f32(self._scal["mu_product"] * _f32(mu))            # fp32 `mu_product *= mu`
+        self._scal["mu_product"] = nadam_mu_product(self._scal["mu_product"], self._steps, beta1, grp["momentum_decay"])
         ops.clip_nadam(p, g, self._flat["exp_avg"], self._flat["exp_avg_sq"], self._stats, max_norm, grp["lr"], beta1,
                        grp["betas"][1], grp["eps"], grp["momentum_decay"], self._steps, self._scal["mu_product"],
                        self._norm, st)
@@ -299,9 +310,7 @@ class ASGD(_Fused):
         # this step uses the eta / mu the previous one stored, then stores the next ones (fp32 0-d tensors in torch)
         ops.clip_asgd(p, g, self._flat["ax"], self._stats, max_norm, grp["lambd"], self._scal["eta"], self._scal["mu"],
                       self._norm, st)
-        lr, lambd, step = grp["lr"], grp["lambd"], float(self._steps)
-        self._scal["eta"] = _f32(lr / ((1 + lambd * lr * step) ** grp["alpha"]))
-        self._scal["mu"] = _f32(1 / max(1, step - grp["t0"]))
+        self._scal["eta"], self._scal["mu"] = asgd_eta_mu(self._steps, grp["lr"], grp["lambd"], grp["alpha"], grp["t0"])
 
 
 # Updater.new_optim's registry: hyps["optim_type"] -> class.  The reference builds any torch.optim class by name;

@@ -88,3 +88,30 @@ def test_header_declares_the_new_entry_points():
     src = open(os.path.join(root, "include", "a2c_mi355x.h")).read()
     for name in ENTRY.values():
         assert f"int {name}(" in src
+
+
+def test_nadam_and_asgd_scalar_chains_equal_torch_for_3000_steps():
+    """the fp32 scalars the NAdam / ASGD classes carry from step to step on the host (optim.nadam_mu_product,
+    optim.asgd_eta_mu: what their _launch calls) against the 0-d state tensors of torch.optim on a 4-element CPU
+    tensor: exact equality at every step (mu_product reaches 0.0 in fp32 near step 1000, in torch too)"""
+    def stepped(opt_cls, **group):
+        p = torch.zeros(4, requires_grad=True)
+        opt = opt_cls([p])
+        opt.param_groups[0].update(group)
+        for step in range(1, 3001):
+            p.grad = torch.full((4,), 1e-3)
+            opt.step()
+            yield step, opt.param_groups[0], opt.state[p]
+
+    mu_product = 1.0
+    for step, grp, st in stepped(torch.optim.NAdam):
+        mu_product = fused_optim.nadam_mu_product(mu_product, step, grp["betas"][0], grp["momentum_decay"])
+        assert mu_product == float(st["mu_product"]), step
+    assert mu_product == 0.0
+    for t0 in (1e6, 2.0, 100.0):
+        mus = set()
+        for step, grp, st in stepped(torch.optim.ASGD, t0=t0):
+            eta, mu = fused_optim.asgd_eta_mu(step, grp["lr"], grp["lambd"], grp["alpha"], grp["t0"])
+            assert (eta, mu) == (float(st["eta"]), float(st["mu"])), (t0, step)
+            mus.add(mu)
+        assert len(mus) == (1 if t0 == 1e6 else 3000 - int(t0))
