@@ -801,6 +801,28 @@ int a2c_clip_asgd(float *params, float *grads, float *ax, int64_t n, const doubl
 int a2c_pack_update_scalars(const double *loss_sums, const float *grad_norm, const int *err,
                             double *out5, a2c_stream_t stream);
 
+/* ------------------------------------------------------------------ Snake worlds in device memory (csrc/snake.hip)
+ * The reference's third env family (gym-snake; preprocessing.py:25-32 snake_prep) with this project's own rules
+ * (DESIGN.md "Snake"; the host twin a2c_amd/snake.py produces the same integers).  A world is G x G cells (4 <= G <= 32)
+ * drawn as unit x unit pixel blocks (1 <= unit <= 16, (G*unit)^2 % 4 == 0) with n_foods foods (1 <= n_foods < G*G - 3);
+ * anything else returns A2C_ERR_ARG without a launch.  Env e of a launch is world env_id0 + e of `seed`: draw i of a
+ * world is hash32(seed, env_id, i).  The state of one env is a2c_snake_state_bytes int32 words: head row, head col,
+ * length, draw counter, step counter, episode reward, 2 spare, then the G*G cells (0 free, -1 food, n > 0 occupied for
+ * n more steps).  The kernels advance the counters in device memory, so a captured launch plays new steps at each replay.
+ * a2c_snake_state_bytes: bytes of ONE env's state, 0 for an unsupported G / n_foods.                                  */
+size_t a2c_snake_state_bytes(int G, int n_foods);
+/* starts B worlds (counters to 0, then the reset draws): state (B rows of state_bytes), frames (B rows of HW = (G*unit)^2
+ * floats: 0 space, 1 body, 1.5 head, 0.33 food) and, when rgb != NULL, the raw frames (B rows of HW*3 bytes, (H, W, 3)).  */
+int a2c_snake_reset(int32_t *state, int B, int env_id0, uint32_t seed, int G, int unit, int n_foods, float *frames,
+                    uint8_t *rgb, a2c_stream_t stream);
+/* one step of B worlds: env e takes (actions[e * act_stride] + action_shift) & 3 (0 up, 1 right, 2 down, 3 left), rew /
+ * done / reset (B floats each; reset == done: a finished world has already been restarted and `frames` holds its reset
+ * frame, what utils.next_state(reset=True) expects).  ep_stats (may be NULL): two int32 the kernel adds to with atomics --
+ * episodes finished, sum of their rewards.                                                                             */
+int a2c_snake_step(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                   uint32_t seed, int G, int unit, int n_foods, float *rew, float *done, float *reset, float *frames,
+                   uint8_t *rgb, int32_t *ep_stats, a2c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

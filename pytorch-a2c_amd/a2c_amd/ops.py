@@ -1160,3 +1160,27 @@ def clip_asgd(params, grads, ax, sumsq, max_norm, lambd, eta, mu, norm_out, st=N
     """eta, mu: the fp32 state values the previous step stored"""
     check(lib().a2c_clip_asgd(_p(params), _p(grads), _p(ax), params.numel(), _p(sumsq), max_norm, lambd, eta, mu,
                               _p(norm_out), _st(st)), "a2c_clip_asgd")
+
+
+# ---------------------------------------------------------------- Snake worlds in device memory (csrc/snake.hip)
+def snake_state_bytes(G, n_foods):
+    """bytes of one env's state; raises for a world the kernels do not support"""
+    n = int(lib().a2c_snake_state_bytes(G, n_foods))
+    if n == 0:
+        raise ValueError(f"a2c_snake_state_bytes: unsupported world grid_size={G} n_foods={n_foods}")
+    return n
+
+
+def snake_reset(state, B, env_id0, seed, G, unit, n_foods, frames, rgb=None, st=None):
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rgb, "rgb", torch.uint8)
+    check(lib().a2c_snake_reset(_p(state), B, env_id0, seed, G, unit, n_foods, _p(frames), _p(rgb), _st(st)),
+          "a2c_snake_reset")
+
+
+def snake_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, G, unit, n_foods, rew, done, reset, frames,
+               rgb=None, ep_stats=None, st=None):
+    """actions_ptr: address of env 0's int64 action, ``act_stride`` elements between envs (a row of the rollout buffer)"""
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rgb, "rgb", torch.uint8)
+    _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset"); _chk(ep_stats, "ep_stats", torch.int32)
+    check(lib().a2c_snake_step(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, G, unit, n_foods,
+                               _p(rew), _p(done), _p(reset), _p(frames), _p(rgb), _p(ep_stats), _st(st)), "a2c_snake_step")

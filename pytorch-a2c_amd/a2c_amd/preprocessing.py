@@ -1,7 +1,7 @@
 """Host-side per-frame preprocessing with the reference's names (a2c/preprocessing.py).  These
 run on the CPU next to the env: pure slicing / thresholding of
-one raw frame, no device work.  ``snake_prep`` is out of scope (gym-snake is not in any
-BASELINE config).
+one raw frame, no device work.  ``snake_prep`` decodes the colour code of the Snake worlds (a2c_amd/snake.py; the
+device worlds write the same four values themselves), pinned by tests/golden/g11_snake_prep.npz.
 
 ``breakout_prep`` (preprocessing.py:19-23) calls ``skimage.color.rgb2grey`` on ``pic[::2, ::2, 0]``, which is already a
 2-D uint8 array.  scikit-image is unpinned in the reference (requirements.txt:7) and absent from this image, so the
@@ -37,3 +37,12 @@ def breakout_prep(pic):                        # preprocessing.py:19-23
     pic = pic[35:195, 8:-8]
     pic = pic[::2, ::2, 0]
     return np.ascontiguousarray(pic)[None]
+
+
+def snake_prep(pic):                           # preprocessing.py:25-32
+    new_pic = np.zeros(pic.shape[:2], dtype=np.float32)
+    new_pic[pic[:, :, 0] == 1] = 1
+    new_pic[pic[:, :, 0] == 255] = 1.5
+    new_pic[pic[:, :, 1] == 255] = 0
+    new_pic[pic[:, :, 2] == 255] = .33
+    return new_pic[None]

@@ -20,9 +20,12 @@ Env pools (``env_pool=``):
       "memcpy"     (every model) per step: actions D2H -> workers step -> hipMemcpyAsync of the
                    frames block from the pinned region into HBM -> the step kernels.
   * ``HostEnvPool`` -- B env objects stepped serially in this process (tests, tiny runs).
-  * a *device resident* pool (``device_step`` protocol: frames / rewards / dones already in HBM,
-    e.g. a synthetic tape): a whole n_tsteps rollout is enqueued without a single host
-    synchronisation and can be captured into one hipGraph.
+  * a *device resident* pool (``device_step`` protocol: frames / rewards / dones already in HBM:
+    ``snake.DeviceSnakePool``, or a synthetic tape): a whole n_tsteps rollout is enqueued without a
+    single host synchronisation and can be captured into one hipGraph.  ``device_step(t, env0, B)``
+    returns (frames (B, HW) fp32, rew, done, reset) device tensors; a pool whose class sets
+    ``needs_actions = True`` is called as ``device_step(t, env0, B, actions=(address, stride))`` with
+    the int64 actions the sampler just wrote, and one with ``episode_stats()`` feeds ``rew_q``.
 """
 import os
 import queue
@@ -188,6 +191,8 @@ class Runner:
         if self.cont and self.proc_pool:
             raise ValueError("a2c_amd.Runner: a continuous-action net needs an in-process (HostEnvPool) or device env pool; "
                              "the process / thread env pools carry int32 actions")
+        if self.cont and getattr(pool, "needs_actions", False):
+            raise ValueError("a2c_amd.Runner: an action-driven device env pool reads int64 actions; the net is continuous")
         self.n_act = int(net.output_space)
         f32 = dict(dtype=torch.float32, device=dev)
         self.bookmark = torch.zeros((B, self.S), **f32)                  # state_bookmark of every env
@@ -318,6 +323,12 @@ class Runner:
             if self.rew_q is not None:
                 self.rew_q.get()
                 self.rew_q.put(self.env_pool.rew_ema())
+        elif getattr(self, "device_pool", False) and self.rew_q is not None and hasattr(self.env_pool, "episode_stats"):
+            # the pool counted finished episodes and summed their rewards on the device: ONE read per rollout.  The k
+            # episodes enter the EMA of runner.py:216 together, as k updates with their mean
+            k, total = self.env_pool.episode_stats()
+            if k:
+                self.rew_q.put(.99 ** k * self.rew_q.get() + (1 - .99 ** k) * total / k)
 
     def check(self):
         if getattr(self, "proc_pool", False) and int(self.rollout_err.item()):
@@ -1042,7 +1053,12 @@ class Runner:
     def _env_step(self, pool, act, a_ptr, a_stride, env0, B, t, slot0, T, shift, acts_host_out, pong):
         """-> (_Frames, rew, done, reset) device views of what the envs returned for the actions just sampled"""
         if self.device_pool:
-            frames, rew, done, reset = pool.device_step(t, env0, B)
+            if getattr(pool, "needs_actions", False):      # an action-driven world: where the sampler wrote this step's actions
+                frames, rew, done, reset = pool.device_step(t, env0, B, actions=(a_ptr, a_stride))
+                if acts_host_out is not None:              # a host `actions` tensor like the reference's: one D2H per step
+                    acts_host_out[slot0 * T + t:(slot0 + B) * T:T] = act.cpu()
+            else:
+                frames, rew, done, reset = pool.device_step(t, env0, B)
             ops._chk(frames, "frames")
             return _Frames(ptr32=frames.data_ptr()), rew, done, reset
         if self.proc_pool:

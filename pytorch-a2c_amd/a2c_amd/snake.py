@@ -1,0 +1,239 @@
+"""Snake: the third env family of the reference (gym-snake, ``snake_prep``), as a world that can live in HBM.
+
+Two implementations of ONE set of rules (DESIGN.md "Snake"), which produce the same integers:
+
+  * ``SnakeEnv``         -- the host twin in NumPy with a gym-like surface (``reset()``, ``step(a)``,
+                            ``action_space.n == 4``, raw RGB frames), usable behind ``SequentialEnvironment(env_fn=...)``,
+                            ``HostEnvPool``, ``ProcessEnvPool`` and ``StatsRunner``;
+  * ``DeviceSnakePool``  -- ``n_envs`` worlds in device memory stepped by a2c_snake_step (csrc/snake.hip): the Runner's
+                            device-pool protocol (``start`` / ``device_step``), driven by the actions the sampler wrote.
+                            Frames arrive already prepped (``snake_prep``'s values); a whole rollout is enqueued without
+                            a host synchronisation and can be captured: the draw counters live in device memory.
+
+Rules.  G x G cells, every cell a u x u block of one colour: space [0,255,0], body [1,0,0], head [255,0,0], food
+[0,0,255].  Actions 0 up, 1 right, 2 down, 3 left (``(action + action_shift) & 3``); the head moves one cell per step.
+Leaving the grid or entering a body cell (neck and tail cell included: the tail is vacated after the move) ends the
+episode with reward -1.  Entering a food cell gives +1, the snake grows by one and a new food appears on a free cell; if
+no free cell is left the grid is full and the episode ends (with that step's +1).  Every other move gives 0.  A reset
+draws heading and head cell, lays a snake of length 3 behind the head and places ``n_foods`` foods.  After a done the env
+resets itself: the frame returned is the reset frame and ``reset == done``.
+
+Randomness is counter based: draw number i of env e is ``hash32(seed, e, i)`` (below); a free cell is the k-th free cell
+in row-major order with ``k = draw mod n_free``.  The body is a time-to-live map: a cell holds 0 (free), -1 (food) or the
+number of steps it stays occupied (head = length)."""
+import numpy as np
+
+N_ACTIONS = 4
+DR = (-1, 0, 1, 0)
+DC = (0, 1, 0, -1)
+SPACE, BODY, HEAD, FOOD = (0, 255, 0), (1, 0, 0), (255, 0, 0), (0, 0, 255)
+PREP_SPACE, PREP_BODY, PREP_HEAD, PREP_FOOD = 0.0, 1.0, 1.5, .33          # what snake_prep makes of the four colours
+_M = 0xFFFFFFFF
+
+
+def _fin(x):
+    """the integer finaliser (lowbias32): x ^= x>>16; x *= 0x7FEB352D; x ^= x>>15; x *= 0x846CA68B; x ^= x>>16 (mod 2^32)"""
+    x &= _M
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & _M
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & _M
+    x ^= x >> 16
+    return x
+
+
+def hash32(seed, env_id, draw_index):
+    """fin(fin(fin(seed + 0x9E3779B9) ^ env_id) ^ draw_index), everything mod 2^32"""
+    return _fin(_fin(_fin((int(seed) + 0x9E3779B9) & _M) ^ (int(env_id) & _M)) ^ (int(draw_index) & _M))
+
+
+def check_world(grid_size, unit_size, n_foods):
+    """the bounds a2c_snake_step enforces (A2C_ERR_ARG): same ones for the host twin"""
+    G, u, nf = int(grid_size), int(unit_size), int(n_foods)
+    if not (4 <= G <= 32 and 1 <= u <= 16 and ((G * u) ** 2) % 4 == 0 and 1 <= nf < G * G - 3):
+        raise ValueError(f"Snake: unsupported world grid_size={G} unit_size={u} n_foods={nf} (4 <= grid_size <= 32, "
+                         "1 <= unit_size <= 16, (grid_size*unit_size)^2 a multiple of 4, 1 <= n_foods < grid_size^2 - 3)")
+    return G, u, nf
+
+
+def world_from_hyps(hyps):
+    """(grid_size, unit_size, n_foods) from the reference's keys (``grid_size`` may be an int or [g, g])"""
+    g = hyps.get("grid_size", 15)
+    if isinstance(g, (list, tuple)):
+        if len(g) != 2 or g[0] != g[1]:
+            raise ValueError("Snake: grid_size must be square")
+        g = g[0]
+    return check_world(15 if g is None else g, hyps.get("unit_size", 4) or 4, hyps.get("n_foods", 2) or 2)
+
+
+class _ActionSpace:
+    n = N_ACTIONS
+
+
+class SnakeEnv:
+    """One Snake world on the host.  ``reset()`` -> raw (G*u, G*u, 3) uint8 frame; ``step(a)`` -> (frame, reward, done,
+    info).  Like a gym env it does NOT reset itself: ``frame`` after a done is the terminal position's (a dead snake
+    stays where it was) and the caller resets -- the Runner does, which yields exactly what the device world returns."""
+    action_space = _ActionSpace()
+
+    def __init__(self, seed=0, env_id=0, grid_size=15, unit_size=4, n_foods=2):
+        self.G, self.u, self.n_foods = check_world(grid_size, unit_size, n_foods)
+        self.seed_, self.env_id = int(seed) & _M, int(env_id)
+        self.cells = np.zeros((self.G, self.G), dtype=np.int32)
+        self.head, self.length, self.draws, self.steps = (0, 0), 0, 0, 0
+        self.over = True
+
+    def seed(self, seed):
+        self.seed_ = int(seed) & _M
+
+    # ---- randomness
+    def _draw(self):
+        d = hash32(self.seed_, self.env_id, self.draws)
+        self.draws = (self.draws + 1) & _M
+        return d
+
+    def _place_food(self, n_free):
+        """food on the k-th free cell in row-major order, k = draw mod n_free"""
+        k = self._draw() % n_free
+        free = np.flatnonzero(self.cells.reshape(-1) == 0)
+        assert len(free) == n_free, (len(free), n_free)
+        self.cells.reshape(-1)[free[k]] = -1
+
+    # ---- gym surface
+    def reset(self):
+        G = self.G
+        self.cells[:] = 0
+        h = self._draw() & 3
+        k = self._draw() % ((G - 2) * G)
+        a, b = k // G, k % G                   # a: along the heading's axis (room for the body behind), b: across
+        if h == 0:
+            r, c = a, b
+        elif h == 1:
+            r, c = b, a + 2
+        elif h == 2:
+            r, c = a + 2, b
+        else:
+            r, c = b, a
+        for i in range(3):                     # head = 3, then 2, 1 behind it
+            self.cells[r - i * DR[h], c - i * DC[h]] = 3 - i
+        self.head, self.length, self.over = (r, c), 3, False
+        for i in range(self.n_foods):
+            self._place_food(G * G - 3 - i)
+        return self.render_rgb()
+
+    def step(self, action):
+        if self.over:
+            raise RuntimeError("SnakeEnv.step() after done: call reset()")
+        a = int(action) & 3
+        G, cells = self.G, self.cells
+        r, c = self.head[0] + DR[a], self.head[1] + DC[a]
+        self.steps += 1
+        if not (0 <= r < G and 0 <= c < G) or cells[r, c] > 0:
+            self.over = True
+            return self.render_rgb(), -1.0, True, {}
+        if cells[r, c] < 0:                    # food: grow, no cell is vacated
+            self.length += 1
+            cells[r, c] = self.length
+            self.head = (r, c)
+            n_free = G * G - self.length - (self.n_foods - 1)
+            if n_free == 0:                    # the grid is full
+                self.over = True
+                return self.render_rgb(), 1.0, True, {}
+            self._place_food(n_free)
+            return self.render_rgb(), 1.0, False, {}
+        cells[cells > 0] -= 1                  # the tail cell is vacated AFTER the move was judged
+        cells[r, c] = self.length
+        self.head = (r, c)
+        return self.render_rgb(), 0.0, False, {}
+
+    def render(self):
+        return self.render_rgb()
+
+    # ---- frames
+    def render_rgb(self):
+        c = self.cells
+        pic = np.empty((self.G, self.G, 3), dtype=np.uint8)
+        pic[:] = SPACE
+        pic[c > 0] = BODY
+        pic[c < 0] = FOOD
+        pic[(c == self.length) & (c > 0)] = HEAD
+        return np.ascontiguousarray(pic.repeat(self.u, axis=0).repeat(self.u, axis=1))
+
+
+class SnakeFactory:
+    """picklable ``env_fn`` for ``SequentialEnvironment`` / the env worker processes"""
+
+    def __init__(self, **kw):
+        self.kw = kw
+
+    def __call__(self, *a, **k):
+        return SnakeEnv(**self.kw)
+
+
+class DeviceSnakePool:
+    """``n_envs`` Snake worlds in device memory (the Runner's device-pool protocol).  Env j is the world
+    ``SnakeEnv(seed, env_id=j, ...)``: same draws, same frames.  ``needs_actions``: the Runner hands ``device_step`` the
+    address and stride of the int64 actions the sampler just wrote."""
+    needs_actions = True
+
+    def __init__(self, n_envs, device="cuda", seed=0, grid_size=15, unit_size=4, n_foods=2, raw_frames=False):
+        import torch
+        from . import ops
+        self.G, self.u, self.n_foods = check_world(grid_size, unit_size, n_foods)
+        self.B, self.seed, self.device = int(n_envs), int(seed) & _M, torch.device(device)
+        side = self.G * self.u
+        self.frame_shape = (1, side, side)
+        self.HW = side * side
+        self.words = ops.snake_state_bytes(self.G, self.n_foods) // 4
+        dev = self.device
+        self.state = torch.zeros((self.B, self.words), dtype=torch.int32, device=dev)
+        self.frames = torch.zeros((self.B, self.HW), dtype=torch.float32, device=dev)
+        self.rgb = torch.zeros((self.B, side, side, 3), dtype=torch.uint8, device=dev) if raw_frames else None
+        self.rew, self.done, self.reset_mask = (torch.zeros(self.B, dtype=torch.float32, device=dev) for _ in range(3))
+        self.ep_stats = torch.zeros(2, dtype=torch.int32, device=dev)      # finished episodes, sum of their rewards
+        self.action_shift = 0
+        self.started = False
+
+    def __len__(self):
+        return self.B
+
+    def reset(self):
+        """(re)starts every world: state, frames (and raw frames) of the reset positions"""
+        from . import ops
+        ops.snake_reset(self.state, self.B, 0, self.seed, self.G, self.u, self.n_foods, self.frames, self.rgb)
+        self.started = True
+
+    def start(self, runner):
+        import torch
+        from . import ops
+        self.action_shift = int(runner.hyps["action_shift"])
+        self.reset()
+        ones = torch.ones(self.B, dtype=torch.float32, device=self.device)
+        ops.frame_stack_push(self.frames, ones, runner.bookmark.data_ptr(), runner.S, runner.bookmark.data_ptr(), runner.S,
+                             self.B, runner.C, runner.HW)
+
+    def step(self, actions_ptr, act_stride, env0=0, B=None):
+        """advance envs env0..env0+B by the int64 actions at ``actions_ptr`` (element stride ``act_stride``)"""
+        from . import ops
+        B = self.B - env0 if B is None else B
+        if not self.started:
+            raise RuntimeError("DeviceSnakePool: reset() / start(runner) first")
+        if env0 < 0 or B < 1 or env0 + B > self.B:
+            raise ValueError("DeviceSnakePool: env range outside the pool")
+        sl = slice(env0, env0 + B)
+        ops.snake_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, env0, self.seed, self.G, self.u,
+                       self.n_foods, self.rew[sl], self.done[sl], self.reset_mask[sl], self.frames[sl],
+                       None if self.rgb is None else self.rgb[sl], self.ep_stats)
+        return self.frames[sl], self.rew[sl], self.done[sl], self.reset_mask[sl]
+
+    def device_step(self, t, env0, B, actions=None):
+        if actions is None:
+            raise ValueError("DeviceSnakePool.device_step needs actions=(address, stride)")
+        return self.step(actions[0], actions[1], env0, B)
+
+    def episode_stats(self):
+        """(episodes finished, sum of their rewards) since the last call; one device read"""
+        n, s = (int(v) for v in self.ep_stats.tolist())
+        if n:
+            self.ep_stats.zero_()
+        return n, s

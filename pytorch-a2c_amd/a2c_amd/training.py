@@ -64,6 +64,9 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     default process env pool ``env_fn`` travels to the worker processes pickled: lambdas and closures need
     ``cloudpickle`` (else pass a module-level callable, or ``hyps['env_pool'] = 'serial'``).  ``uniform_fn`` /
     ``on_epoch(epoch, updater, shared_data)`` are test hooks (sampler uniforms; called after every update).
+    ``env_type`` "Snake-device" / "Snake-host" (a2c_amd/snake.py; keys ``grid_size``, ``unit_size``, ``n_foods``) need no
+    gym: the first plays ``n_envs`` worlds in device memory (``DeviceSnakePool``), the second ``SnakeEnv``s behind the usual
+    ``env_pool`` choices with ``prep_fxn="snake_prep"``; both are evaluated on host ``SnakeEnv``s.
     Returns the best evaluation reward."""
     hyps = dict(DEFAULTS, **hyps)
     if hyps["n_rollouts"] is None:
@@ -83,7 +86,29 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     # environments
     serial = try_key(hyps, "env_pool", "process") == "serial"
     probe = None
-    if env_fn is None:
+    snake_world = None
+    if env_fn is None and hyps["env_type"] in ("Snake-device", "Snake-host"):
+        from . import snake
+        G, unit, n_foods = snake_world = snake.world_from_hyps(hyps)
+        hyps["prep_fxn"], hyps["preprocessor"] = "snake_prep", preprocessing.snake_prep
+        hyps["is_discrete"], n_act = True, snake.N_ACTIONS
+        # a policy that circles never ends its evaluation episode: cap it (StatsRunner reads the key)
+        hyps["max_eval_steps"] = try_key(hyps, "max_eval_steps", 2000)
+        world = dict(seed=hyps["seed"], grid_size=G, unit_size=unit, n_foods=n_foods)
+        mk_env = lambda j: SequentialEnvironment(hyps["env_type"], preprocessing.snake_prep, seed=hyps["seed"],
+                                                 env_fn=snake.SnakeFactory(env_id=j, **world))
+        if hyps["env_type"] == "Snake-device":
+            pool = snake.DeviceSnakePool(hyps["n_envs"], device=cuda_if(torch.zeros(1)).device, **world)
+        elif serial:
+            pool = HostEnvPool([mk_env(j) for j in range(hyps["n_envs"])], frame_shape=(1, G * unit, G * unit))
+        else:
+            from .hostpool import ProcessEnvPool
+            kws = [dict(env_type=hyps["env_type"], preprocessor=preprocessing.snake_prep, seed=hyps["seed"],
+                        env_fn=snake.SnakeFactory(env_id=j, **world)) for j in range(hyps["n_envs"])]
+            pool = ProcessEnvPool(SequentialEnvironment, hyps["n_envs"], env_kwargs=kws,
+                                  n_workers=try_key(hyps, "n_env_workers", None), pong=False,
+                                  action_shift=try_key(hyps, "action_shift", 0), frame_bits=False)
+    elif env_fn is None:
         hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
         probe = eval_env or SequentialEnvironment(**hyps)             # the probe for shapes (training.py:60-65)
         hyps["is_discrete"], n_act = probe.is_discrete, probe.n
@@ -95,7 +120,9 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
             raise ValueError("a2c_amd: continuous action spaces need env_pool='serial' (the process env pool carries "
                              "int32 actions)")
         serial = True
-    if env_fn is None:
+    if snake_world is not None:
+        pass
+    elif env_fn is None:
         kws = [dict({k: v for k, v in hyps.items() if k != "seed"}, seed=hyps["seed"] + j) for j in range(hyps["n_envs"])]
         if serial:
             envs = [SequentialEnvironment(**kw) for kw in kws]
@@ -172,6 +199,8 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     # evaluation: the caller's single env (reference loop), else n_test_eps gym envs in lock-step on the device
     if eval_env is not None:
         stats_runner = StatsRunner(hyps, env=eval_env)
+    elif snake_world is not None:      # host twins of worlds the training pool does not play (env ids from 10007 on)
+        stats_runner = StatsRunner(hyps, envs=[mk_env(10007 + j) for j in range(try_key(hyps, "n_test_eps", 15))])
     else:
         stats_runner = StatsRunner(hyps) if env_fn is None else None
     entr_coef_diff, lr_diff = hyps["entr_coef"] - hyps["entr_coef_low"], hyps["lr"] - hyps["lr_low"]
