@@ -796,6 +796,62 @@ int a2c_clip_radam(float *params, float *grads, float *exp_avg, float *exp_avg_s
 int a2c_clip_asgd(float *params, float *grads, float *ax, int64_t n, const double *sumsq, double max_norm,
                   double lambd, double eta, double mu, float *norm_out, a2c_stream_t stream);
 
+/* ---- capturable Adam family: step count and step-dependent scalars in device memory (torch's capturable=True).
+ * The launchers above take `step` (and NAdam's mu_product, ASGD's eta / mu) as HOST arguments, so a hipGraph replay would
+ * repeat the captured step's bias corrections for ever.  Here they live in one per-optimiser device block:
+ * a2c_optim_advance increments the step and recomputes the scalars on the device, a2c_clip_step_dev is the same step
+ * kernel with its scalars read from the block.  [advance, step] can be captured and replayed; eager runs are the same two
+ * launches.  The block is A2C_OPTIM_BLOCK_BYTES of device memory, 16-byte aligned.  To start or restore an optimiser write
+ * step, mu_product, eta and mu (a2c_memcpy_async or any copy; zero the rest): a fresh block is step 0, mu_product 1,
+ * eta (float)lr, mu 1.  Everything from `rectify` on is overwritten by every advance.
+ *
+ *   offset  field       written by advance for        meaning
+ *    0      step        all (step += 1)               int64, steps taken
+ *    8      mu_product  NAdam (*= (float)mu)          running fp32 state, torch's 0-d `mu_product`
+ *   12      eta         ASGD                          running fp32 state stored at the END of step `step` (torch's `eta`)
+ *   16      mu          ASGD                          running fp32 state stored at the END of step `step` (torch's `mu`)
+ *   20      rectify     RAdam                         int32, rho_t > 5
+ *   24      mu_is_one   ASGD                          int32, mu_used == 1
+ *   28      step_size   Adam, AdamW                   lr / (1 - beta1^step)
+ *   32      bc2_sqrt    Adam, AdamW, RAdam            sqrt(1 - beta2^step)
+ *   36      neg_clr     Adamax                        -lr / (1 - beta1^step)
+ *   40      bc2         NAdam                         1 - beta2^step
+ *   44      c_grad      NAdam                         -lr (1 - mu) / (1 - mu_product)
+ *   48      c_avg       NAdam                         -lr mu_next / (1 - mu_product mu_next)
+ *   52      bc1         RAdam                         1 - beta1^step
+ *   56      rect        RAdam                         the rectification term (0 unless rectify)
+ *   60      decay       AdamW: 1 - lr weight_decay    ASGD: 1 - lambd eta_used
+ *   64      neg_eta     ASGD                          -eta_used   (eta_used / mu_used: what step - 1 stored)
+ *   68      mu_used     ASGD
+ *   72      lr          all                           the hyper-parameters of the advance, rounded to fp32 as the
+ *   76      omb1        all   1 - beta1               launchers above round them
+ *   80      beta2       all
+ *   84      omb2        all   1 - beta2
+ *   88      eps         all
+ *   92      (padding)                                                                                                  */
+#define A2C_OPTIM_BLOCK_BYTES 96
+typedef struct a2c_optim_block {
+  int64_t step;
+  float mu_product, eta, mu;
+  int32_t rectify, mu_is_one;
+  float step_size, bc2_sqrt, neg_clr, bc2, c_grad, c_avg, bc1, rect, decay, neg_eta, mu_used;
+  float lr, omb1, beta2, omb2, eps;
+  float pad_;
+} a2c_optim_block;
+enum { A2C_OPTIM_ADAM = 0, A2C_OPTIM_ADAMW = 1, A2C_OPTIM_ADAMAX = 2, A2C_OPTIM_NADAM = 3, A2C_OPTIM_RADAM = 4,
+       A2C_OPTIM_ASGD = 5 };
+/* One launch of one wavefront; one lane does the work in double with the formulas (and their order) of a2c_clip_adam /
+ * _adamw / _adamax / _nadam / _radam / _asgd and of torch's fp32 running state (mu_product *= (float)mu; eta, mu).  The
+ * hyper-parameters are arguments of THIS launch: a capture fixes them, as it fixes lr for RMSprop.  Arguments a kind does
+ * not use are ignored.  A2C_ERR_ARG on a NULL or non-16-B-aligned block or an unknown kind.                          */
+int a2c_optim_advance(int kind, void *block, double lr, double beta1, double beta2, double eps, double weight_decay,
+                      double momentum_decay, double lambd, double alpha, double t0, a2c_stream_t stream);
+/* The clip + step launch of `kind` (same kernel body and element arithmetic as a2c_clip_<kind>, same bytes per parameter)
+ * with the rule's scalars read from the block inside the kernel.  state_b is ignored for ASGD.  Validation as
+ * a2c_clip_adam (NULL or non-16-B-aligned arrays: A2C_ERR_ARG; n == 0: no-op), plus the block checks of the advance.    */
+int a2c_clip_step_dev(int kind, float *params, float *grads, float *state_a, float *state_b, int64_t n,
+                      const double *sumsq, double max_norm, const void *block, float *norm_out, a2c_stream_t stream);
+
 /* out5 = [loss_sums[0..2], grad_norm, err]: the five scalars update_model reads back (updater.py:134-136)
  * gathered into ONE device buffer for a single D2H copy                                  */
 int a2c_pack_update_scalars(const double *loss_sums, const float *grad_norm, const int *err,

@@ -185,6 +185,9 @@ SIGNATURES = {
     "a2c_clip_radam": (c_int, [P, P, P, P, c_int64, P, c_double, c_double, c_double, c_double, c_double, c_int64,
                                 P, P]),
     "a2c_clip_asgd": (c_int, [P, P, P, c_int64, P, c_double, c_double, c_double, c_double, P, P]),
+    "a2c_optim_advance": (c_int, [c_int, P, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
+                                   c_double, c_double, P]),
+    "a2c_clip_step_dev": (c_int, [c_int, P, P, P, P, c_int64, P, c_double, P, P, P]),
     "a2c_snake_state_bytes": (c_size_t, [c_int, c_int]),
     "a2c_snake_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, c_int, c_int, P, P, P]),
     "a2c_snake_step": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, c_int, P, P, P, P, P, P, P]),

@@ -7,6 +7,7 @@ on the CPU: a non-CUDA tensor raises.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1160,6 +1161,49 @@ def clip_asgd(params, grads, ax, sumsq, max_norm, lambd, eta, mu, norm_out, st=N
     """eta, mu: the fp32 state values the previous step stored"""
     check(lib().a2c_clip_asgd(_p(params), _p(grads), _p(ax), params.numel(), _p(sumsq), max_norm, lambd, eta, mu,
                               _p(norm_out), _st(st)), "a2c_clip_asgd")
+
+
+# ---- capturable Adam family: step count + step-dependent scalars in a device block (include/a2c_mi355x.h: a2c_optim_block)
+OPTIM_KINDS = {"Adam": 0, "AdamW": 1, "Adamax": 2, "NAdam": 3, "RAdam": 4, "ASGD": 5}
+OPTIM_BLOCK_BYTES = 96
+OPTIM_BLOCK_DTYPE = np.dtype([("step", "<i8"), ("mu_product", "<f4"), ("eta", "<f4"), ("mu", "<f4"), ("rectify", "<i4"),
+                              ("mu_is_one", "<i4"), ("step_size", "<f4"), ("bc2_sqrt", "<f4"), ("neg_clr", "<f4"),
+                              ("bc2", "<f4"), ("c_grad", "<f4"), ("c_avg", "<f4"), ("bc1", "<f4"), ("rect", "<f4"),
+                              ("decay", "<f4"), ("neg_eta", "<f4"), ("mu_used", "<f4"), ("lr", "<f4"), ("omb1", "<f4"),
+                              ("beta2", "<f4"), ("omb2", "<f4"), ("eps", "<f4"), ("pad_", "<f4")])
+assert OPTIM_BLOCK_DTYPE.itemsize == OPTIM_BLOCK_BYTES
+
+
+def optim_block_new(device):
+    """a zeroed device block (uint8 tensor); set it with optim_block_set before the first advance"""
+    return note_tensor(torch.zeros(OPTIM_BLOCK_BYTES, dtype=torch.uint8, device=device))
+
+
+def optim_block_set(block, step, mu_product=1.0, eta=0.0, mu=1.0):
+    """start or restore an optimiser: the step count and the running fp32 state; every derived field is zeroed (the next
+    advance writes them).  One small copy on the current stream, outside the hot path."""
+    rec = np.zeros(1, dtype=OPTIM_BLOCK_DTYPE)
+    rec["step"], rec["mu_product"], rec["eta"], rec["mu"] = int(step), mu_product, eta, mu
+    block.copy_(torch.from_numpy(rec.view(np.uint8)))
+
+
+def optim_block_read(block):
+    """the block's fields as python values (one device -> host read)"""
+    rec = block.cpu().numpy().view(OPTIM_BLOCK_DTYPE)[0]
+    return {k: rec[k].item() for k in OPTIM_BLOCK_DTYPE.names if k != "pad_"}
+
+
+def optim_advance(kind, block, lr, beta1=0.0, beta2=0.0, eps=0.0, weight_decay=0.0, momentum_decay=0.0, lambd=0.0,
+                  alpha=0.0, t0=0.0, st=None):
+    """step += 1 and this step's scalars, computed on the device (one wavefront); kind: OPTIM_KINDS[name]"""
+    check(lib().a2c_optim_advance(kind, _p(block), lr, beta1, beta2, eps, weight_decay, momentum_decay, lambd, alpha,
+                                  t0, _st(st)), "a2c_optim_advance")
+
+
+def clip_step_dev(kind, params, grads, state_a, state_b, sumsq, max_norm, block, norm_out, st=None):
+    """the fused clip + step of ``kind`` with its scalars read from the device block (state_b: None for ASGD)"""
+    check(lib().a2c_clip_step_dev(kind, _p(params), _p(grads), _p(state_a), _p(state_b), params.numel(), _p(sumsq),
+                                  max_norm, _p(block), _p(norm_out), _st(st)), "a2c_clip_step_dev")
 
 
 # ---------------------------------------------------------------- Snake worlds in device memory (csrc/snake.hip)

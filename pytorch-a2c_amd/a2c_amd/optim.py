@@ -7,6 +7,10 @@ tensors are views into flat HBM buffers parallel to the net's arena; one kernel 
 Settings are torch's defaults apart from ``lr`` (the reference only ever passes ``lr``): RMSprop / Adam and the
 other torch optimisers that step without a closure (``OPTIMIZERS``).  A loaded param_group that asks for something
 the kernels do not implement (momentum, maximize, amsgrad, weight decay outside AdamW, ...) raises ``ValueError``.
+
+``capturable=True`` (Adam, AdamW, Adamax, NAdam, RAdam, ASGD; torch's flag of the same name) keeps the step count and the
+step-dependent scalars in a device block (``ops.optim_block_*``): ``step()`` is then [advance, step] with no step-dependent
+kernel argument, so ``Updater.capture_update`` can replay it.  The mode is fixed at construction.
 """
 import numpy as np
 import torch
@@ -37,11 +41,18 @@ class _Fused(torch.optim.Optimizer):
     _stateless = False           # torch keeps no state at all (SGD without momentum): no `step` either
     _eager = False               # torch creates the state of EVERY parameter at construction (Adagrad)
     _fixed = {}                  # param_group settings the kernel does not implement -> the one value it accepts
+    _kind = None                 # ops.OPTIM_KINDS entry of the rules that have a device-scalar (capturable) step
     capture_safe = False
 
-    def __init__(self, net, lr, defaults):
+    def __init__(self, net, lr, defaults, capturable=False):
         net._ensure_device()
         self.net = net
+        self._capturable = bool(capturable)
+        if self._capturable:
+            if self._kind is None:
+                raise ValueError(f"a2c_amd: {type(self).__name__} has no capturable mode")
+            defaults = dict(defaults, capturable=True)
+            self.capture_safe = True     # no step-dependent kernel argument: [advance, step] replays exactly
         super().__init__(list(net.parameters()), dict(lr=lr, **defaults))
         ar = net._arena
         self._flat = {k: torch.zeros(ar.n_train, dtype=torch.float32, device=ar.params.device)
@@ -52,6 +63,7 @@ class _Fused(torch.optim.Optimizer):
         self._steps = 0
         self._scal = {}              # host values of self._scalars (set by the first step, or loaded)
         self._name_of = {id(p): n for n, p in net.named_parameters()}
+        self._block = ops.optim_block_new(ar.params.device) if self._capturable else None
         if self._eager:
             self._publish_state()
 
@@ -66,6 +78,8 @@ class _Fused(torch.optim.Optimizer):
         """Expose the flat state as torch-style per-parameter entries (lazily, like torch, unless _eager)."""
         if self._stateless:
             return
+        blk = ops.optim_block_read(self._block) if self._capturable else None     # the device's count, one read-back
+        dev = self.net._arena.params.device
         for p in self.param_groups[0]["params"]:
             if not self._trainable(p):
                 if self._eager and "step" not in self.state[p]:    # never gets a gradient: torch's initial state
@@ -76,6 +90,11 @@ class _Fused(torch.optim.Optimizer):
             if "step" not in st:
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
                 st.update(self._views(p))
+            if blk is not None:            # torch's capturable layout: 0-d fp32 tensors on the parameter's device
+                st["step"] = torch.tensor(float(blk["step"]), dtype=torch.float32, device=dev)
+                for k in self._scalars:
+                    st[k] = torch.tensor(blk[k], dtype=torch.float32, device=dev)
+                continue
             st["step"].fill_(float(self._steps))
             for k in self._scalars:
                 st[k] = torch.tensor(self._scal[k], dtype=torch.float32)
@@ -89,8 +108,16 @@ class _Fused(torch.optim.Optimizer):
         for k, want in self._fixed.items():
             if k in group and group[k] != want:
                 raise ValueError(f"a2c_amd: {type(self).__name__} implements {k}={want!r} only, got {group[k]!r}")
+        if self._kind is not None and bool(group.get("capturable", False)) != self._capturable:
+            raise ValueError(f"a2c_amd: this {type(self).__name__} was built with capturable={self._capturable!r}; the "
+                             "mode is fixed at construction (build a new optimiser and load this one's state_dict)")
 
     def load_state_dict(self, state_dict):
+        if self._kind is not None:
+            # a checkpoint written in the other mode (or by torch / the reference) carries ITS `capturable`: the state
+            # loads either way and the group keeps this object's mode
+            state_dict = dict(state_dict, param_groups=[dict(g, capturable=self._capturable)
+                                                        for g in state_dict["param_groups"]])
         for g in state_dict["param_groups"]:
             self._check_group(g)
         super().load_state_dict(state_dict)
@@ -109,6 +136,9 @@ class _Fused(torch.optim.Optimizer):
                 self._scal[k] = _f32(float(st[k]))
                 st[k] = torch.tensor(self._scal[k], dtype=torch.float32)
         self._steps = steps
+        if self._capturable and steps > 0:
+            ops.optim_block_set(self._block, steps, **self._scal)
+            self._publish_state()            # the published step / scalars are device tensors in this mode
 
     def zero_grad(self, set_to_none=False):
         # gradients live in the arena and are overwritten by every backward pass
@@ -132,9 +162,27 @@ class _Fused(torch.optim.Optimizer):
         ops.gradnorm_sq(g, self._stats[:1], st, scratch=self._scratch)
         if self._steps == 0:
             self._first_step()
+            if self._capturable:
+                ops.optim_block_set(self._block, 0, **self._scal)
         self._steps += 1
-        self._launch(ar.train_params(), g, float("1e30") if max_norm is None else float(max_norm), st)
+        max_norm = float("1e30") if max_norm is None else float(max_norm)
+        if self._capturable:
+            # the device path, whether or not a capture is in progress: eager and graphed runs are the same launches
+            self._advance(st)
+            fl = [self._flat[k] for k in self._state_names] + [None]
+            ops.clip_step_dev(self._kind, ar.train_params(), g, fl[0], fl[1], self._stats, max_norm, self._block,
+                              self._norm, st)
+        else:
+            self._launch(ar.train_params(), g, max_norm, st)
         self.net.mark_dirty()
+
+    def _advance(self, st):
+        """a2c_optim_advance with this rule's hyper-parameters (they are arguments of the launch: a capture fixes them)"""
+        grp = self.param_groups[0]
+        b1, b2 = grp.get("betas", (0.0, 0.0))
+        ops.optim_advance(self._kind, self._block, grp["lr"], b1, b2, grp.get("eps", 0.0), grp.get("weight_decay", 0.0),
+                          grp.get("momentum_decay", 0.0), grp.get("lambd", 0.0), grp.get("alpha", 0.0),
+                          grp.get("t0", 0.0), st)
 
 
 class RMSprop(_Fused):
@@ -153,10 +201,12 @@ class RMSprop(_Fused):
 
 class Adam(_Fused):
     _state_names = ("exp_avg", "exp_avg_sq")
+    _kind = ops.OPTIM_KINDS["Adam"]
 
-    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False):
         super().__init__(net, lr, dict(betas=betas, eps=eps, weight_decay=0, amsgrad=False, maximize=False,
-                                       foreach=None, capturable=False, differentiable=False, fused=None))
+                                       foreach=None, capturable=False, differentiable=False, fused=None,
+                                       decoupled_weight_decay=False), capturable)
 
     def _launch(self, p, g, max_norm, st):
         grp = self.param_groups[0]
@@ -236,11 +286,12 @@ class Rprop(_Fused):
 
 
 class AdamW(_Fused):
+    _kind = ops.OPTIM_KINDS["AdamW"]
     _state_names = ("exp_avg", "exp_avg_sq")
     _fixed = dict(amsgrad=False, maximize=False, decoupled_weight_decay=True)
 
-    def __init__(self, net, lr=1e-3):
-        super().__init__(net, lr, _torch_defaults("AdamW", lr))
+    def __init__(self, net, lr=1e-3, capturable=False):
+        super().__init__(net, lr, _torch_defaults("AdamW", lr), capturable)
 
     def _launch(self, p, g, max_norm, st):
         grp = self.param_groups[0]
@@ -249,11 +300,12 @@ class AdamW(_Fused):
 
 
 class Adamax(_Fused):
+    _kind = ops.OPTIM_KINDS["Adamax"]
     _state_names = ("exp_avg", "exp_inf")
     _fixed = _NO_DECAY
 
-    def __init__(self, net, lr=2e-3):
-        super().__init__(net, lr, _torch_defaults("Adamax", lr))
+    def __init__(self, net, lr=2e-3, capturable=False):
+        super().__init__(net, lr, _torch_defaults("Adamax", lr), capturable)
 
     def _launch(self, p, g, max_norm, st):
         grp = self.param_groups[0]
@@ -262,12 +314,13 @@ class Adamax(_Fused):
 
 
 class NAdam(_Fused):
+    _kind = ops.OPTIM_KINDS["NAdam"]
     _state_names = ("exp_avg", "exp_avg_sq")
     _scalars = ("mu_product",)
     _fixed = dict(decoupled_weight_decay=False, **_NO_DECAY)
 
-    def __init__(self, net, lr=2e-3):
-        super().__init__(net, lr, _torch_defaults("NAdam", lr))
+    def __init__(self, net, lr=2e-3, capturable=False):
+        super().__init__(net, lr, _torch_defaults("NAdam", lr), capturable)
 
     def _first_step(self):
         self._scal["mu_product"] = 1.0
@@ -282,11 +335,12 @@ class NAdam(_Fused):
 
 
 class RAdam(_Fused):
+    _kind = ops.OPTIM_KINDS["RAdam"]
     _state_names = ("exp_avg", "exp_avg_sq")
     _fixed = dict(decoupled_weight_decay=False, **_NO_DECAY)
 
-    def __init__(self, net, lr=1e-3):
-        super().__init__(net, lr, _torch_defaults("RAdam", lr))
+    def __init__(self, net, lr=1e-3, capturable=False):
+        super().__init__(net, lr, _torch_defaults("RAdam", lr), capturable)
 
     def _launch(self, p, g, max_norm, st):
         grp = self.param_groups[0]
@@ -295,12 +349,13 @@ class RAdam(_Fused):
 
 
 class ASGD(_Fused):
+    _kind = ops.OPTIM_KINDS["ASGD"]
     _state_names = ("ax",)
     _scalars = ("eta", "mu")
     _fixed = _NO_DECAY
 
-    def __init__(self, net, lr=1e-2):
-        super().__init__(net, lr, _torch_defaults("ASGD", lr))
+    def __init__(self, net, lr=1e-2, capturable=False):
+        super().__init__(net, lr, _torch_defaults("ASGD", lr), capturable)
 
     def _first_step(self):
         self._scal.update(eta=_f32(self.param_groups[0]["lr"]), mu=1.0)

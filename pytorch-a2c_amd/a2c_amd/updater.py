@@ -308,9 +308,10 @@ class Updater:
         alike when its rollouts were alike."""
         if not getattr(self.optim, "capture_safe", False):
             # Adam's bias correction (and the other step-dependent scalars: NAdam's mu, ASGD's eta, ...) takes the step
-            # count as a KERNEL ARGUMENT: a replay would apply the captured step's values for ever
+            # count as a KERNEL ARGUMENT: a replay would apply the captured step's values for ever.  With
+            # hyps["optim_capturable"] the count and the scalars live on the device and the optimiser is capture_safe.
             raise RuntimeError(f"a2c_amd: {type(self.optim).__name__}.step cannot be captured into a hipGraph "
-                               "(its step count is a kernel argument); use update_model")
+                               "(its step count is a kernel argument); use update_model, or hyps['optim_capturable'] = True")
         if self._bufs is None:
             raise RuntimeError("a2c_amd: capture_update needs one eager update_model on these buffers first")
         return _GraphedUpdate(self, shared_data)
@@ -416,4 +417,9 @@ class Updater:
         self.optim = new_optim
 
     def new_optim(self, lr):
-        return fused_optim.check_name(self.hyps["optim_type"])(self.net, lr=lr)
+        cls = fused_optim.check_name(self.hyps["optim_type"])
+        # hyps["optim_capturable"]: torch's capturable=True for the Adam family (step count and bias corrections on the
+        # device, so capture_update / replay work); the other optimisers are capture-safe as they are and ignore it
+        if try_key(self.hyps, "optim_capturable", False) and cls._kind is not None:
+            return cls(self.net, lr=lr, capturable=True)
+        return cls(self.net, lr=lr)

@@ -136,6 +136,13 @@ struct RpropRule {          // a = prev, b = step_size
   }
 };
 
+struct AdamRule {           // a = exp_avg, b = exp_avg_sq (a2c_clip_adam keeps its own kernel; this is adam1 as a functor)
+  float omb1, beta2, omb2, eps, step_size, bc2_sqrt;
+  __device__ void operator()(float& p, float g, float& a, float& b) const {
+    adam1(p, g, a, b, 1.0f, omb1, beta2, omb2, eps, step_size, bc2_sqrt);
+  }
+};
+
 struct AdamWRule {          // a = exp_avg, b = exp_avg_sq: param.mul_(1 - lr*wd), then Adam's step
   float decay, omb1, beta2, omb2, eps, step_size, bc2_sqrt;
   __device__ void operator()(float& p, float g, float& a, float& b) const {
@@ -191,11 +198,8 @@ struct AsgdRule {           // a = ax; eta / mu are the values the PREVIOUS step
 };
 
 template <int NS, class Rule>
-__global__ __launch_bounds__(256) void clip_step_kernel(float* __restrict__ p, float* __restrict__ g,
-                                                        float* __restrict__ sa, float* __restrict__ sb, long n,
-                                                        const double* sumsq, float max_norm, Rule rule,
-                                                        float* norm_out) {
-  const float coef = clip_coef(sumsq, max_norm, norm_out);
+__device__ __forceinline__ void clip_step_body(float* __restrict__ p, float* __restrict__ g, float* __restrict__ sa,
+                                               float* __restrict__ sb, long n, float coef, const Rule& rule) {
   const long n4 = n >> 2;
   float4* p4 = reinterpret_cast<float4*>(p);
   float4* g4 = reinterpret_cast<float4*>(g);
@@ -225,6 +229,14 @@ __global__ __launch_bounds__(256) void clip_step_kernel(float* __restrict__ p, f
     if (NS > 0) sa[i] = av;
     if (NS > 1) sb[i] = bv;
   }
+}
+
+template <int NS, class Rule>
+__global__ __launch_bounds__(256) void clip_step_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                        float* __restrict__ sa, float* __restrict__ sb, long n,
+                                                        const double* sumsq, float max_norm, Rule rule,
+                                                        float* norm_out) {
+  clip_step_body<NS>(p, g, sa, sb, n, clip_coef(sumsq, max_norm, norm_out), rule);
 }
 
 // a2c_clip_adam's validation contract: A2C_ERR_ARG on a NULL or non-16-B-aligned array (NS state arrays), n == 0 a no-op
@@ -408,5 +420,155 @@ int a2c_clip_asgd(float* params, float* grads, float* ax, int64_t n, const doubl
   // eta, mu: the fp32 state values the previous step stored (lr and 1 before the first step)
   const AsgdRule r{(float)(1.0 - lambd * eta), (float)-eta, (float)mu, (float)mu == 1.0f};
   return clip_step_launch<1>(params, grads, ax, nullptr, n, sumsq, max_norm, r, norm_out, stream);
+}
+}
+
+// ---- capturable Adam family: the step count and the step-dependent scalars live in a device block (a2c_optim_block,
+// include/a2c_mi355x.h), so a hipGraph replay of [advance, step] steps like an eager run.  optim_advance_kernel is the
+// scalar part of the launchers above moved onto the device: the same double formulas in the same order, rounded to fp32
+// at the same places; clip_step_dev_kernel is clip_step_body with the functor filled from the block.
+namespace {
+static_assert(sizeof(a2c_optim_block) == A2C_OPTIM_BLOCK_BYTES, "a2c_optim_block layout");
+
+__global__ __launch_bounds__(64) void optim_advance_kernel(int kind, a2c_optim_block* blk, double lr, double beta1,
+                                                           double beta2, double eps, double weight_decay,
+                                                           double momentum_decay, double lambd, double alpha,
+                                                           double t0) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  a2c_optim_block b = *blk;
+  b.step += 1;
+  const double s = (double)b.step;
+  b.lr = (float)lr;
+  b.omb1 = (float)(1.0 - beta1);
+  b.beta2 = (float)beta2;
+  b.omb2 = (float)(1.0 - beta2);
+  b.eps = (float)eps;
+  switch (kind) {
+    case A2C_OPTIM_ADAM:
+    case A2C_OPTIM_ADAMW: {                                   // a2c_clip_adam / a2c_clip_adamw
+      const double bc1 = 1.0 - pow(beta1, s);
+      const double bc2 = 1.0 - pow(beta2, s);
+      b.decay = (float)(1.0 - lr * weight_decay);
+      b.step_size = (float)(lr / bc1);
+      b.bc2_sqrt = (float)sqrt(bc2);
+      break;
+    }
+    case A2C_OPTIM_ADAMAX: {                                  // a2c_clip_adamax
+      const double clr = lr / (1.0 - pow(beta1, s));
+      b.neg_clr = (float)-clr;
+      break;
+    }
+    case A2C_OPTIM_NADAM: {                                   // optim.nadam_mu_product, then a2c_clip_nadam
+      const double mu = beta1 * (1.0 - 0.5 * pow(0.96, s * momentum_decay));
+      b.mu_product = (float)((double)b.mu_product * (double)(float)mu);
+      const double mu_product = (double)b.mu_product;
+      const double mu_next = beta1 * (1.0 - 0.5 * pow(0.96, (s + 1.0) * momentum_decay));
+      const double mu_product_next = mu_product * mu_next;
+      b.bc2 = (float)(1.0 - pow(beta2, s));
+      b.c_grad = (float)(-lr * (1.0 - mu) / (1.0 - mu_product));
+      b.c_avg = (float)((-lr * mu_next) / (1.0 - mu_product_next));
+      break;
+    }
+    case A2C_OPTIM_RADAM: {                                   // a2c_clip_radam
+      const double bc1 = 1.0 - pow(beta1, s);
+      const double bc2 = 1.0 - pow(beta2, s);
+      const double rho_inf = 2.0 / (1.0 - beta2) - 1.0;
+      const double rho_t = rho_inf - 2.0 * s * pow(beta2, s) / bc2;
+      b.rectify = rho_t > 5.0;
+      const double rect = b.rectify ? pow((rho_t - 4.0) * (rho_t - 2.0) * rho_inf /
+                                          ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t), 0.5) : 0.0;
+      b.bc1 = (float)bc1;
+      b.bc2_sqrt = (float)pow(bc2, 0.5);
+      b.rect = (float)rect;
+      break;
+    }
+    default: {                                                // A2C_OPTIM_ASGD: a2c_clip_asgd, then optim.asgd_eta_mu
+      const double eta = (double)b.eta, mu = (double)b.mu;    // what the previous step stored
+      b.decay = (float)(1.0 - lambd * eta);
+      b.neg_eta = (float)-eta;
+      b.mu_used = (float)mu;
+      b.mu_is_one = (float)mu == 1.0f;
+      b.eta = (float)(lr / pow(1.0 + lambd * lr * s, alpha));
+      b.mu = (float)(1.0 / fmax(1.0, s - t0));
+      break;
+    }
+  }
+  *blk = b;
+}
+
+template <class Rule> __device__ __forceinline__ Rule rule_from_block(const a2c_optim_block& b);
+template <> __device__ __forceinline__ AdamRule rule_from_block<AdamRule>(const a2c_optim_block& b) {
+  return AdamRule{b.omb1, b.beta2, b.omb2, b.eps, b.step_size, b.bc2_sqrt};
+}
+template <> __device__ __forceinline__ AdamWRule rule_from_block<AdamWRule>(const a2c_optim_block& b) {
+  return AdamWRule{b.decay, b.omb1, b.beta2, b.omb2, b.eps, b.step_size, b.bc2_sqrt};
+}
+template <> __device__ __forceinline__ AdamaxRule rule_from_block<AdamaxRule>(const a2c_optim_block& b) {
+  return AdamaxRule{b.omb1, b.beta2, b.eps, b.neg_clr};
+}
+template <> __device__ __forceinline__ NAdamRule rule_from_block<NAdamRule>(const a2c_optim_block& b) {
+  return NAdamRule{b.omb1, b.beta2, b.omb2, b.eps, b.bc2, b.c_grad, b.c_avg};
+}
+template <> __device__ __forceinline__ RAdamRule rule_from_block<RAdamRule>(const a2c_optim_block& b) {
+  return RAdamRule{b.omb1, b.beta2, b.omb2, b.eps, b.bc1, b.lr, b.bc2_sqrt, b.rect, b.rectify};
+}
+template <> __device__ __forceinline__ AsgdRule rule_from_block<AsgdRule>(const a2c_optim_block& b) {
+  return AsgdRule{b.decay, b.neg_eta, b.mu_used, b.mu_is_one};
+}
+
+// the block was written by an earlier launch on the stream and is only read here: every thread block sees the same step
+template <int NS, class Rule>
+__global__ __launch_bounds__(256) void clip_step_dev_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                            float* __restrict__ sa, float* __restrict__ sb, long n,
+                                                            const double* sumsq, float max_norm,
+                                                            const a2c_optim_block* __restrict__ blk, float* norm_out) {
+  const Rule rule = rule_from_block<Rule>(*blk);
+  clip_step_body<NS>(p, g, sa, sb, n, clip_coef(sumsq, max_norm, norm_out), rule);
+}
+
+template <int NS, class Rule>
+int clip_step_dev_launch(float* p, float* g, float* sa, float* sb, int64_t n, const double* sumsq, double max_norm,
+                         const a2c_optim_block* blk, float* norm_out, a2c_stream_t stream) {
+  if (clip_step_args_bad<NS>(p, g, sa, sb, n, sumsq)) return A2C_ERR_ARG;
+  if (n == 0) return A2C_OK;
+  hipLaunchKernelGGL((clip_step_dev_kernel<NS, Rule>), dim3(a2c_grid_1d((n + 3) / 4, 256)), dim3(256), 0, a2c_s(stream),
+                     p, g, sa, sb, (long)n, sumsq, (float)max_norm, blk, norm_out);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+bool optim_block_bad(int kind, const void* block) {
+  return kind < A2C_OPTIM_ADAM || kind > A2C_OPTIM_ASGD || !block || (uintptr_t)block % 16 != 0;
+}
+}  // namespace
+
+extern "C" {
+int a2c_optim_advance(int kind, void* block, double lr, double beta1, double beta2, double eps, double weight_decay,
+                      double momentum_decay, double lambd, double alpha, double t0, a2c_stream_t stream) {
+  if (optim_block_bad(kind, block)) return A2C_ERR_ARG;
+  hipLaunchKernelGGL(optim_advance_kernel, dim3(1), dim3(64), 0, a2c_s(stream), kind, (a2c_optim_block*)block, lr,
+                     beta1, beta2, eps, weight_decay, momentum_decay, lambd, alpha, t0);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+int a2c_clip_step_dev(int kind, float* params, float* grads, float* state_a, float* state_b, int64_t n,
+                      const double* sumsq, double max_norm, const void* block, float* norm_out, a2c_stream_t stream) {
+  if (optim_block_bad(kind, block)) return A2C_ERR_ARG;
+  const a2c_optim_block* blk = (const a2c_optim_block*)block;
+  switch (kind) {
+    case A2C_OPTIM_ADAM:
+      return clip_step_dev_launch<2, AdamRule>(params, grads, state_a, state_b, n, sumsq, max_norm, blk, norm_out, stream);
+    case A2C_OPTIM_ADAMW:
+      return clip_step_dev_launch<2, AdamWRule>(params, grads, state_a, state_b, n, sumsq, max_norm, blk, norm_out, stream);
+    case A2C_OPTIM_ADAMAX:
+      return clip_step_dev_launch<2, AdamaxRule>(params, grads, state_a, state_b, n, sumsq, max_norm, blk, norm_out, stream);
+    case A2C_OPTIM_NADAM:
+      return clip_step_dev_launch<2, NAdamRule>(params, grads, state_a, state_b, n, sumsq, max_norm, blk, norm_out, stream);
+    case A2C_OPTIM_RADAM:
+      return clip_step_dev_launch<2, RAdamRule>(params, grads, state_a, state_b, n, sumsq, max_norm, blk, norm_out, stream);
+    default:                    // A2C_OPTIM_ASGD: one state array (ax); state_b is not touched
+      return clip_step_dev_launch<1, AsgdRule>(params, grads, state_a, nullptr, n, sumsq, max_norm, blk, norm_out, stream);
+  }
 }
 }
