@@ -9,7 +9,7 @@
  * MI355X through ONE region of pinned host memory (POSIX shared memory that the GPU process
  * registers with hipHostRegister), laid out as
  *
- *     header | cmd[n_envs] | rec[n_envs] | frames[n_envs][frame_stride]
+ *     header | cmd[n_envs] | rec[n_envs] | frames[n_envs][frame_stride] [| tagged mirror] [| act[n_envs][act_stride]]
  *
  *   cmd[j]  8-byte granule written by the DEVICE (persistent rollout kernel, system-scope store) or
  *           by the GPU process after a D2H copy:   (seq << 32) | (uint32) action
@@ -28,6 +28,22 @@
  * overtake its payload.  The device reads frames with system-scope (sc0 sc1) loads either directly
  * from this memory (zero-copy ingest inside a2c_a3c_rollout) or after a hipMemcpyAsync of the
  * frames block into HBM (memcpy ingest, a2c_frame_stack_push_u8 / a2c_a3c_step).
+ *
+ * CONTINUOUS actions (Gaussian policies; the reference hands env.step a float vector like any other action,
+ * runner.py:98-104, 207-208): a pool may carry an optional block of FLOAT ACTION GRANULES behind everything else,
+ * enabled after a2c_pool_init with a2c_pool_enable_actions_f32 (header fields off_act / act_dim / act_stride; all 0 on
+ * an int pool, whose size, offsets and entry points are untouched):
+ *
+ *   act[j*act_stride + k]   8-byte granule, k < act_dim:   (seq << 32) | float_bits(action[j][k])
+ *           written by the DEVICE (a2c_gauss_head_publish: the thread that computes component k stores it, one
+ *           system-scope store) or by the GPU process (a2c_pool_post_actions_f32); seq modulo 2^32 as in cmd;
+ *           act_stride (granules between envs) is act_dim rounded up to 8: every env's granules start a 64-byte line.
+ *   cmd[j]  stays the DOORBELL:   (seq << 32) | act_dim   -- the workers poll it exactly as on an int pool.
+ * A worker that finds the doorbell of step seq accepts the action only when ALL act_dim granules of the env carry seq
+ * (a2c_pool_take_f32 waits for that inside its spin budget and otherwise hands nothing out): every float travels with
+ * its own tag, so nothing depends on the order in which the act_dim + 1 separate stores reach host memory -- the
+ * doorbell may arrive first, last or in between.  A granule of step seq is rewritten only after the worker has
+ * answered step seq (the device publishes step seq + 1 after it ingested that answer), i.e. after it was consumed.
  */
 #ifndef A2C_HOSTPOOL_H
 #define A2C_HOSTPOOL_H
@@ -51,6 +67,7 @@ extern "C" {
  * bits in registers -- 8x fewer bytes over the host link, results bit-identical to the uint8 transport.  A worker
  * that meets a pixel other than 0/1 fails loudly (a2c_pool_publish_bits returns -1).                              */
 #define A2C_FRAME_BITS 2
+#define A2C_POOL_MAX_ACT_DIM 64 /* = A2C_GAUSS_MAX_N (a2c_mi355x.h): longest float action vector */
 
 typedef struct {
   uint64_t magic;
@@ -72,6 +89,10 @@ typedef struct {
    * rec[j] and the fetch of frames[j] (two dependent PCIe round trips) become ONE 16-byte load per lane.            */
   uint64_t off_tagged;
   uint32_t tagged_stride, tagged_chunks;
+  /* optional float action granules (a2c_pool_enable_actions_f32; all 0 = an int pool): act_dim granules per env,
+   * act_stride granules (8 bytes each) between the envs                                                          */
+  uint64_t off_act;
+  uint32_t act_dim, act_stride;
 } a2c_pool_header;
 
 /* bytes of the region for n_envs envs with frame_bytes per frame (page aligned)             */
@@ -82,6 +103,13 @@ size_t a2c_pool_bytes_tagged(int n_envs, int frame_bytes, uint32_t frame_elems);
  * mirror out behind the frames; the workers then keep it up to date (a2c_pool_publish_bits and the native worker
  * threads write it before they publish rec).  0, or -1 (not a bits pool / region too small)                      */
 int a2c_pool_enable_tagged(void *base, size_t region_bytes);
+/* bytes of a region that also carries act_dim float action granules per env (0: act_dim outside 1..64)  */
+size_t a2c_pool_bytes_f32(int n_envs, int frame_bytes, int act_dim);
+/* after a2c_pool_init (and a2c_pool_enable_tagged, if used), before the workers attach: lay the float action granules
+ * out behind everything the region holds, every granule ~0 ("no step yet").  region_bytes >= header.total_bytes +
+ * (a2c_pool_bytes_f32 - a2c_pool_bytes).  0, or -1 (unformatted region / region too small / act_dim outside
+ * 1..A2C_POOL_MAX_ACT_DIM / already enabled)                                                                     */
+int a2c_pool_enable_actions_f32(void *base, size_t region_bytes, int act_dim);
 /* format a zero-filled region (GPU process, before the workers attach); 0 or -1             */
 int a2c_pool_init(void *base, size_t bytes, int n_envs, int frame_bytes, int frame_dtype,
                   int n_workers, double rew_ema0);
@@ -104,6 +132,12 @@ int32_t a2c_pool_action(const void *base, int env);
 /* a2c_pool_poll + a2c_pool_action in one call: *action = the action of the env returned              */
 int a2c_pool_take(void *base, int env0, int n, const uint32_t *next_seq, int64_t spin_ns,
                   int32_t *action);
+/* float-action pools: a2c_pool_poll (the doorbell cmd[j] = (seq << 32) | act_dim), then -- inside the same spin_ns
+ * budget -- wait until all act_dim granules of that env carry next_seq[i] and copy the act_dim floats, bit for bit, to
+ * action_out.  Returns i; -1 when no doorbell came or the tags did not complete in time (action_out untouched: poll
+ * again); -2 on SHUTDOWN                                                                                        */
+int a2c_pool_take_f32(void *base, int env0, int n, const uint32_t *next_seq, int64_t spin_ns,
+                      float *action_out);
 /* frames[env] = frame (frame_bytes), then rec[env] = {seq, done, rew} with release order     */
 void a2c_pool_publish(void *base, int env, const void *frame, uint32_t seq, float rew, int done);
 /* A2C_FRAME_BITS pools: pack the frame_elems uint8 pixels of `frame_u8` (each 0 or 1) into the env's slot, then
@@ -118,6 +152,10 @@ void a2c_pool_worker_failed(void *base, int worker_id);
 /* cmd[env0+i] = (seq << 32) | actions[i*stride]                                              */
 void a2c_pool_post_actions(void *base, int env0, int n, const int64_t *actions, int64_t stride,
                            uint32_t seq);
+/* float-action pools: act[(env0+i)*act_stride + k] = (seq << 32) | bits(actions[i*stride + k]), k < act_dim, then the
+ * doorbell cmd[env0+i] = (seq << 32) | act_dim with release order (stride in floats)                          */
+void a2c_pool_post_actions_f32(void *base, int env0, int n, const float *actions, int64_t stride,
+                               uint32_t seq);
 /* wait until rec.seq == seq for all envs env0..env0+n-1: 0, or -1 on timeout, -3 on worker error */
 int a2c_pool_wait_frames(void *base, int env0, int n, uint32_t seq, int64_t timeout_ns);
 /* unpack rec[env0..] into rew[i], done[i] (floats, e.g. a pinned staging buffer)             */

@@ -442,6 +442,18 @@ int a2c_loss_fwd_bwd(const float *logits, int64_t ld_logits, const float *vals, 
  * rounded like torch's two ops (runner.py:98-104).  B rows of heads with row stride ld_heads (>= 2n).                 */
 int a2c_gauss_head(const float *heads, int64_t ld_heads, const float *eps, int64_t ld_eps, float *sigma,
                    int64_t ld_sigma, float *actions, int64_t ld_act, int64_t B, int n, a2c_stream_t stream);
+/* a2c_gauss_head that ALSO hands the sampled actions to the env workers of a float-action host pool (a2c_hostpool.h:
+ * "CONTINUOUS actions"; runner.py:207-208 env.step(action)) -- same arithmetic, sigma and actions bit-identical.  With
+ * s = seq_base[0] + seq_off (modulo 2^32; seq_base in DEVICE memory, so a captured launch replays for later rollouts)
+ * the thread that computes action (b, k) stores the granule act[b*act_stride + k] = (s << 32) | float_bits(action) and
+ * the thread of k == 0 then the doorbell cmd[b] = (s << 32) | n: system-scope 8-byte stores (act / cmd = device
+ * addresses of the registered pinned region).  Every granule carries its own tag, so the worker's acceptance does not
+ * depend on the doorbell arriving last.  cmd == NULL: exactly a2c_gauss_head, act / seq_base are not touched.  With
+ * cmd != NULL: actions, eps, act, seq_base non-NULL and act_stride >= n.                                         */
+int a2c_gauss_head_publish(const float *heads, int64_t ld_heads, const float *eps, int64_t ld_eps, float *sigma,
+                           int64_t ld_sigma, float *actions, int64_t ld_act, int64_t B, int n, uint64_t *act,
+                           int64_t act_stride, uint64_t *cmd, const uint32_t *seq_base, uint32_t seq_off,
+                           a2c_stream_t stream);
 /* The reference's Gaussian loss (updater.py:108-117), first of two launches.  With d = mu - a, c = clamp(sigma^2, 1e-3),
  * l = log(clamp(sqrt(2 pi) sigma, 1e-3)) and adv the (optionally normalised, as in a2c_loss_fwd_bwd) advantage:
  * sums[0..5] (double) = sum d^2, sum w/(2c), sum w*l, sum l, sum adv, sum (V-R)^2 over the local rows, where

@@ -91,6 +91,8 @@ SIGNATURES = {
     "a2c_loss_fwd_bwd": (c_int, [P, c_int64, P, c_int64, P, P, P, P, c_int64, c_int64, c_int, c_float, c_float,
                                   c_float, P, c_int64, P, c_int64, P, P, P]),
     "a2c_gauss_head": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, c_int64, c_int64, c_int, P]),
+    "a2c_gauss_head_publish": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, c_int64, c_int64, c_int, P, c_int64, P, P,
+                                        ctypes.c_uint32, P]),
     "a2c_gauss_loss_sums": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, c_int64, c_int64, c_int, P, P, P]),
     "a2c_gauss_loss_fwd_bwd": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, P, c_int64, c_int64, c_int, c_float,
                                         c_float, c_float, P, c_int64, P, c_int64, P, P]),

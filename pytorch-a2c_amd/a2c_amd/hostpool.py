@@ -43,7 +43,8 @@ class PoolHeader(Structure):
                 ("off_cmd", c_uint64), ("off_rec", c_uint64), ("off_frames", c_uint64), ("total_bytes", c_uint64),
                 ("phase", c_uint32), ("workers_ready", c_uint32), ("worker_error", c_uint32), ("ema_lock", c_uint32),
                 ("rew_ema", c_double), ("episodes", c_uint64), ("frame_elems", c_uint32), ("seq_start", c_uint32),
-                ("off_tagged", c_uint64), ("tagged_stride", c_uint32), ("tagged_chunks", c_uint32)]
+                ("off_tagged", c_uint64), ("tagged_stride", c_uint32), ("tagged_chunks", c_uint32),
+                ("off_act", c_uint64), ("act_dim", c_uint32), ("act_stride", c_uint32)]
 
 
 P = c_void_p
@@ -51,6 +52,8 @@ POOL_SIGNATURES = {   # one entry per prototype in include/a2c_hostpool.h
     "a2c_pool_bytes": (c_size_t, [c_int, c_int]),
     "a2c_pool_bytes_tagged": (c_size_t, [c_int, c_int, c_uint32]),
     "a2c_pool_enable_tagged": (c_int, [P, c_size_t]),
+    "a2c_pool_bytes_f32": (c_size_t, [c_int, c_int, c_int]),
+    "a2c_pool_enable_actions_f32": (c_int, [P, c_size_t, c_int]),
     "a2c_pool_init": (c_int, [P, c_size_t, c_int, c_int, c_int, c_int, c_double]),
     "a2c_pool_set_frame_elems": (None, [P, c_uint32]),
     "a2c_pool_set_seq_start": (None, [P, c_uint32]),
@@ -60,12 +63,14 @@ POOL_SIGNATURES = {   # one entry per prototype in include/a2c_hostpool.h
     "a2c_pool_poll": (c_int, [P, c_int, c_int, P, c_int64]),
     "a2c_pool_action": (c_int32, [P, c_int]),
     "a2c_pool_take": (c_int, [P, c_int, c_int, P, c_int64, P]),
+    "a2c_pool_take_f32": (c_int, [P, c_int, c_int, P, c_int64, P]),
     "a2c_pool_publish": (None, [P, c_int, P, c_uint32, c_float, c_int]),
     "a2c_pool_publish_bits": (c_int, [P, c_int, P, c_uint32, c_float, c_int]),
     "a2c_pool_episode": (None, [P, c_double]),
     "a2c_pool_worker_ready": (None, [P]),
     "a2c_pool_worker_failed": (None, [P, c_int]),
     "a2c_pool_post_actions": (None, [P, c_int, c_int, P, c_int64, c_uint32]),
+    "a2c_pool_post_actions_f32": (None, [P, c_int, c_int, P, c_int64, c_uint32]),
     "a2c_pool_wait_frames": (c_int, [P, c_int, c_int, c_uint32, c_int64]),
     "a2c_pool_unpack": (None, [P, c_int, c_int, P, P]),
     "a2c_pool_rew_ema": (c_double, [P]),
@@ -145,10 +150,12 @@ class Region:
         self.cmd = arr[h.off_cmd:h.off_cmd + 8 * n].view(np.uint64)
         self.rec = arr[h.off_rec:h.off_rec + 8 * n].view(np.uint64)
         self.frames = arr[h.off_frames:h.off_frames + n * h.frame_stride].reshape(n, h.frame_stride)
+        if h.off_act:       # float action granules (continuous policies): (n_envs, act_stride) uint64, act_dim of them used
+            self.act = arr[h.off_act:h.off_act + 8 * n * h.act_stride].view(np.uint64).reshape(n, h.act_stride)
         return self
 
     def close(self, unlink=False):
-        for k in ("cmd", "rec", "frames", "header", "_buf"):
+        for k in ("cmd", "rec", "frames", "act", "header", "_buf"):
             self.__dict__.pop(k, None)
         try:
             self.mm.close()
@@ -182,8 +189,14 @@ class _PinnedPool:
 
     device_pool = False
 
-    def _setup(self, n_envs, frame_shape, frame_dtype, n_workers, rew_ema0, register, frame_bits=False, seq_start=0):
+    def _setup(self, n_envs, frame_shape, frame_dtype, n_workers, rew_ema0, register, frame_bits=False, seq_start=0,
+               action_dim=None):
         self.n_envs, self.n_workers = int(n_envs), int(n_workers)
+        # continuous policies: the pool carries float action vectors of this length (a2c_hostpool.h: float action
+        # granules behind the frames, cmd stays the doorbell); 0 = the int32 command-word pool
+        self.act_dim = int(action_dim or 0)
+        if action_dim is not None and not 1 <= self.act_dim <= 64:
+            raise ValueError("action_dim: 1 .. 64 (A2C_GAUSS_MAX_N)")
         self.frame_shape = tuple(int(s) for s in frame_shape)
         self.frame_dtype = np.dtype(np.uint8 if np.dtype(frame_dtype) in (np.dtype(np.uint8), np.dtype(bool)) else np.float32)
         self.frame_elems = int(np.prod(self.frame_shape))
@@ -244,6 +257,9 @@ class _PinnedPool:
         tagged = self.frame_bits and self.frame_elems <= 63 * 112 and os.environ.get("A2C_TAGGED") == "1"
         nbytes = lib.a2c_pool_bytes_tagged(self.n_envs, self.frame_bytes, self.frame_elems) if tagged else \
             lib.a2c_pool_bytes(self.n_envs, self.frame_bytes)
+        if self.act_dim:
+            nbytes += lib.a2c_pool_bytes_f32(self.n_envs, self.frame_bytes, self.act_dim) - \
+                lib.a2c_pool_bytes(self.n_envs, self.frame_bytes)
         self.name = f"a2c_pool_{os.getpid()}_{id(self) & 0xffffff:x}_{int(time.time() * 1e3) & 0xffffff:x}"
         reg = self.region = Region(self.name, create_bytes=nbytes)
         ctypes.memset(reg.base, 0, nbytes)          # first touch of every page from the (NUMA-placed) creating thread
@@ -254,6 +270,8 @@ class _PinnedPool:
         lib.a2c_pool_set_seq_start(reg.base, self.seq_start & 0xffffffff)
         if tagged and lib.a2c_pool_enable_tagged(reg.base, nbytes):
             raise RuntimeError("a2c_pool_enable_tagged failed")
+        if self.act_dim and lib.a2c_pool_enable_actions_f32(reg.base, nbytes, self.act_dim):
+            raise RuntimeError("a2c_pool_enable_actions_f32 failed")
         reg.bind()
         if self.register:       # pin + map into the GPU's address space (no copy): hipHostRegister
             from . import ops
@@ -289,7 +307,15 @@ class _PinnedPool:
         pool_lib().a2c_pool_set_phase(self.region.base, phase)
 
     def post_actions(self, actions, env0=0, seq=None):
-        """cmd[env0+i] = (seq, actions[i]) -- actions: contiguous int64 numpy array (e.g. a pinned staging view)"""
+        """cmd[env0+i] = (seq, actions[i]) -- actions: contiguous int64 numpy array (e.g. a pinned staging view).  A pool with
+        float action granules (action_dim=n) takes float32 rows (B, n): granules (seq, actions[i][k]), then the doorbells"""
+        if self.act_dim:
+            a = np.ascontiguousarray(actions, dtype=np.float32).reshape(-1, self.act_dim)
+            if seq is None:
+                seq = self.seq_of(env0, a.shape[0])
+            pool_lib().a2c_pool_post_actions_f32(self.region.base, env0, a.shape[0], a.ctypes.data, self.act_dim,
+                                                 int(seq) & 0xffffffff)
+            return
         a = np.ascontiguousarray(actions, dtype=np.int64)
         if seq is None:
             seq = self.seq_of(env0, a.shape[0])
@@ -323,6 +349,11 @@ class _PinnedPool:
     @property
     def dev_cmd(self):
         return self.dev_ptr + self.header.off_cmd
+
+    @property
+    def dev_act(self):
+        """device address of the float action granules of env 0 (0: an int pool, or a region the GPU has not mapped)"""
+        return self.dev_ptr + self.header.off_act if (self.dev_ptr and self.header.off_act) else 0
 
     @property
     def dev_phase(self):
@@ -359,11 +390,14 @@ class ProcessEnvPool(_PinnedPool):
     returning already prepped frames of shape (1, H, W) / (1, L) (what SequentialEnvironment returns).
     ``action_shift`` / ``pong`` are the hyps of runner.py:208,212-214 (the Pong done override only affects
     the episode-reward EMA here; the device applies it to the ``dones`` buffer).
+    ``action_dim=n`` (continuous policies): the region also carries n float action granules per env and the workers call
+    ``env.step`` with a float32 ``(n,)`` vector (``act_dim``, ``dev_act``, float rows in ``post_actions``); unset, the pool
+    is the int32 command-word pool.
     """
 
     def __init__(self, env_factory, n_envs, env_kwargs=None, n_workers=None, action_shift=0, pong=False,
                  frame_shape=None, frame_dtype=None, rew_ema0=-1.0, register=True, spin=True, sys_path=None,
-                 probe_reset=False, frame_bits=False, seq_start=0):
+                 probe_reset=False, frame_bits=False, seq_start=0, action_dim=None):
         self.env_factory, self.n_envs = env_factory, int(n_envs)
         self.env_kwargs = list(env_kwargs) if env_kwargs is not None else [dict() for _ in range(n_envs)]
         assert len(self.env_kwargs) == self.n_envs
@@ -380,7 +414,8 @@ class ProcessEnvPool(_PinnedPool):
             obs = np.asarray(env_factory(**self.env_kwargs[0]).reset())
             frame_shape = obs.shape if frame_shape is None else frame_shape
             frame_dtype = obs.dtype if frame_dtype is None else frame_dtype
-        self._setup(n_envs, frame_shape, frame_dtype, n_workers, rew_ema0, register, frame_bits=frame_bits, seq_start=seq_start)
+        self._setup(n_envs, frame_shape, frame_dtype, n_workers, rew_ema0, register, frame_bits=frame_bits, seq_start=seq_start,
+                    action_dim=action_dim)
         self.spin = bool(spin)
         self.sys_path = list(sys_path) if sys_path is not None else [p for p in sys.path if p]
         self.procs = []

@@ -68,6 +68,12 @@ def run(spec, lib, reg, base, env0, n):
     ep_rew = [0.0] * n
     act = ctypes.c_int32(0)
     actp = ctypes.addressof(act)
+    act_dim = int(reg.header.act_dim)
+    if act_dim:       # float action granules: the whole vector, accepted only when every granule carries the step's tag
+        take = lib.a2c_pool_take_f32
+        fact = np.zeros(act_dim, dtype=np.float32)
+        actp = fact.ctypes.data
+        fshift = np.float32(shift)
     spin_ns = 500_000_000
     while True:
         i = take(base, env0, n, nsp, spin_ns, actp)
@@ -77,7 +83,8 @@ def run(spec, lib, reg, base, env0, n):
             if os.getppid() != parent:      # the GPU process is gone
                 break
             continue
-        obs, rew, done, _ = envs[i].step(act.value + shift)
+        # (a float pool hands env.step a fresh float32 (n,) vector, like the reference's get_action, runner.py:98-104)
+        obs, rew, done, _ = envs[i].step(fact + fshift if act_dim else act.value + shift)
         ep_rew[i] += rew
         reset = bool(done)
         if pong and rew != 0:

@@ -61,7 +61,7 @@ class TorchAbi:
     def note(self, t):
         import bisect
         import weakref
-        if t is None or not t.is_cuda:
+        if t is None or not getattr(t, "is_cuda", False):      # (None, or a raw address wrapper: looked up by address)
             return
         st = t.untyped_storage()
         base, nb = st.data_ptr(), st.nbytes()
@@ -708,6 +708,18 @@ def gauss_head(heads, n, B, sigma=None, eps=None, actions_ptr=0, act_ld=0, st=No
     check(lib().a2c_gauss_head(_p(heads), heads.stride(0), _p(eps), eps.stride(0) if eps is not None else 0, _p(sigma),
                                sigma.stride(0) if sigma is not None else 0, actions_ptr or None, act_ld, B, n,
                                st if st is not None else stream()), "a2c_gauss_head")
+
+
+def gauss_head_publish(heads, n, B, eps, actions_ptr, act_ld, act_ptr, act_stride, cmd_ptr, seq_base, seq_off, sigma=None,
+                       st=None):
+    """gauss_head whose sampling threads also hand the actions to the env workers of a float-action host pool: granules
+    act[b*act_stride + k] = (seq_base[0] + seq_off, bits of action (b, k)) and the doorbells cmd[b] (device addresses of the
+    pinned pool region, or of plain device buffers); seq_base: int32 device tensor.  cmd_ptr == 0: plain gauss_head."""
+    _chk(heads, "heads", contig=False); _chk(sigma, "sigma", contig=False); _chk(eps, "eps", contig=False)
+    check(lib().a2c_gauss_head_publish(_p(heads), heads.stride(0), _p(eps), eps.stride(0) if eps is not None else 0, _p(sigma),
+                                       sigma.stride(0) if sigma is not None else 0, actions_ptr or None, act_ld, B, n,
+                                       act_ptr or None, act_stride, cmd_ptr or None, _p(seq_base), int(seq_off) & 0xffffffff,
+                                       st if st is not None else stream()), "a2c_gauss_head_publish")
 
 
 def gauss_loss_sums(heads, vals, actions, advs, returns, adv_sums, n_global, n, sums, st=None, scratch=None):

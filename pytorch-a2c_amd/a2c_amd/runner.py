@@ -188,12 +188,16 @@ class Runner:
         self.proc_pool = hasattr(pool, "post_actions")
         # continuous nets (is_discrete=False): actions are float rows of n, sampled by a2c_gauss_head
         self.cont = not getattr(net, "is_discrete", True)
-        if self.cont and self.proc_pool:
-            raise ValueError("a2c_amd.Runner: a continuous-action net needs an in-process (HostEnvPool) or device env pool; "
-                             "the process / thread env pools carry int32 actions")
+        self.n_act = int(net.output_space)
+        # ... over a process pool they travel as float action granules (ProcessEnvPool(action_dim=n), a2c_hostpool.h)
+        if self.cont and self.proc_pool and int(getattr(pool, "act_dim", 0) or 0) != self.n_act:
+            raise ValueError("a2c_amd.Runner: a continuous-action net needs an in-process (HostEnvPool) or device env pool, or "
+                             "a ProcessEnvPool(action_dim=n) with n = the net's action size; the int process pool and the "
+                             "thread env pool carry int32 actions")
+        if not self.cont and int(getattr(pool, "act_dim", 0) or 0):
+            raise ValueError("a2c_amd.Runner: a pool with float action granules (action_dim) needs a continuous-action net")
         if self.cont and getattr(pool, "needs_actions", False):
             raise ValueError("a2c_amd.Runner: an action-driven device env pool reads int64 actions; the net is continuous")
-        self.n_act = int(net.output_space)
         f32 = dict(dtype=torch.float32, device=dev)
         self.bookmark = torch.zeros((B, self.S), **f32)                  # state_bookmark of every env
         self.val_prev = torch.zeros(B, **f32)
@@ -207,7 +211,8 @@ class Runner:
         if self.proc_pool:
             # worker processes behind the pinned region: frame 0 of every env (its env.reset()) is already there
             pool.start()
-            self.h_rew, self.h_done, self.h_act = mk(B), mk(B), mk(B, dt=torch.int64)
+            self.h_rew, self.h_done = mk(B), mk(B)
+            self.h_act = mk(B, self.n_act) if self.cont else mk(B, dt=torch.int64)
             self.np_rew, self.np_done, self.np_act = self.h_rew.numpy(), self.h_done.numpy(), self.h_act.numpy()
             self.d_rew, self.d_done = torch.zeros(B, **f32), torch.zeros(B, **f32)
             self.u8 = pool.frame_dtype == np.uint8
@@ -427,9 +432,13 @@ class Runner:
             return self.datas["actions"].data_ptr() + 4 * n * (slot0 * T + t), T * n
         return self.datas["actions"].data_ptr() + 8 * (slot0 * T + t), T
 
-    def _sample(self, net, logits, u, eps, a_ptr, a_stride, B, st):
-        """actions of the step from the policy heads: softmax sampling, or mu + sigma*eps (a2c_gauss_head)"""
-        if self.cont:
+    def _sample(self, net, logits, u, eps, a_ptr, a_stride, B, st, pub=None):
+        """actions of the step from the policy heads: softmax sampling, or mu + sigma*eps (a2c_gauss_head).  pub = (act, act_stride,
+        cmd, seq_base, seq_off), continuous nets behind the device relay: the sampling threads hand the actions to the env
+        workers themselves (a2c_gauss_head_publish) -- no publish launch behind this one"""
+        if self.cont and pub is not None:
+            ops.gauss_head_publish(logits, self.n_act, B, eps, a_ptr, a_stride, *pub, st=st)
+        elif self.cont:
             ops.gauss_head(logits, self.n_act, B, eps=eps, actions_ptr=a_ptr, act_ld=a_stride, st=st)
         else:
             ops.softmax_sample(logits, u, a_ptr, a_stride, B, net.output_space, st=st)
@@ -897,8 +906,14 @@ class Runner:
             finally:
                 net._frames_src = None
             if not out.get("sampled", False):
+                gpub = None
+                if c.get("relay") and self.cont:      # float action granules + doorbells of env step k, from the sampling threads
+                    ast = int(pool.header.act_stride)
+                    gpub = (pool.dev_act + 8 * ast * env0, ast, pool.dev_cmd + 8 * env0, self._seq_dev, k)
                 self._sample(net, out["logits"], u, self._e_buf[k, env0:env0 + B] if self.cont else None, a_ptr, a_stride,
-                             B, st)
+                             B, st, pub=gpub)
+                if gpub is not None:
+                    out["published"] = True
             if out.get("h_next_src") is not None:      # cell stash: the next segment's post kernel reads h_new from there
                 pass
             elif h is not None and out["h"].data_ptr() != h.data_ptr():    # (the GRU models update h in place)

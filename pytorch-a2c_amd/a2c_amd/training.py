@@ -64,6 +64,8 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     default process env pool ``env_fn`` travels to the worker processes pickled: lambdas and closures need
     ``cloudpickle`` (else pass a module-level callable, or ``hyps['env_pool'] = 'serial'``).  ``uniform_fn`` /
     ``on_epoch(epoch, updater, shared_data)`` are test hooks (sampler uniforms; called after every update).
+    Continuous (``Box``) envs step in this process unless ``hyps['env_pool'] = 'process_f32'``: worker processes behind a
+    pool that carries float action vectors (``ProcessEnvPool(action_dim=n)``); ``'process'`` stays the int32 pool.
     ``env_type`` "Snake-device" / "Snake-host" (a2c_amd/snake.py; keys ``grid_size``, ``unit_size``, ``n_foods``) need no
     gym: the first plays ``n_envs`` worlds in device memory (``DeviceSnakePool``), the second ``SnakeEnv``s behind the usual
     ``env_pool`` choices with ``prep_fxn="snake_prep"``; both are evaluated on host ``SnakeEnv``s.
@@ -119,7 +121,15 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
         if "env_pool" in hyps and hyps["env_pool"] == "process":
             raise ValueError("a2c_amd: continuous action spaces need env_pool='serial' (the process env pool carries "
                              "int32 actions)")
-        serial = True
+        # ... unless asked for: env_pool='process_f32' = worker processes behind a pool with float action granules
+        serial = try_key(hyps, "env_pool", None) != "process_f32"
+    elif try_key(hyps, "env_pool", None) == "process_f32":
+        raise ValueError("a2c_amd: env_pool='process_f32' carries float action vectors: it needs a continuous action space "
+                         "(discrete envs use env_pool='process')")
+    # float action granules per env (ProcessEnvPool(action_dim=n)); None = the int32 command-word pool
+    f32_dim = None
+    if not hyps["is_discrete"] and not serial:
+        f32_dim = int(n_act if env_fn is None else hyps["action_size"])
     if snake_world is not None:
         pass
     elif env_fn is None:
@@ -135,7 +145,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
             pool = ProcessEnvPool(SequentialEnvironment, hyps["n_envs"], env_kwargs=kws,
                                   n_workers=try_key(hyps, "n_env_workers", None), pong="Pong" in hyps["env_type"],
                                   action_shift=1 if hyps["env_type"] == "Pong-v0" else try_key(hyps, "action_shift", 0),
-                                  frame_bits=bool(bits))
+                                  frame_bits=bool(bits), action_dim=f32_dim)
     else:
         if serial:
             pool = HostEnvPool([env_fn(j) for j in range(hyps["n_envs"])])
@@ -144,7 +154,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
             pool = ProcessEnvPool(_PositionalFactory(env_fn), hyps["n_envs"], env_kwargs=[dict(j=j) for j in range(hyps["n_envs"])],
                                   n_workers=try_key(hyps, "n_env_workers", None), pong="Pong" in hyps["env_type"],
                                   action_shift=1 if hyps["env_type"] == "Pong-v0" else try_key(hyps, "action_shift", 0),
-                                  probe_reset=True, frame_bits=bool(try_key(hyps, "frame_bits", False)))
+                                  probe_reset=True, frame_bits=bool(try_key(hyps, "frame_bits", False)), action_dim=f32_dim)
         n_act = hyps["action_size"]
     hyps["state_shape"] = [hyps["n_frame_stack"]] + list(pool.frame_shape[1:])
     if hyps["env_type"] == "Pong-v0":

@@ -33,17 +33,33 @@ __device__ __forceinline__ AdvNorm adv_norm(const double* adv_sums, long n_globa
   return a;
 }
 
+// PUB: the thread that computes action (b, j) also hands it to env b's worker -- granule (step << 32) | bits, then (j == 0) the
+// doorbell; per-lane system-scope 8-byte stores, each granule self-tagged (a2c_hostpool.h), so their order does not matter
+template <bool PUB>
 __global__ __launch_bounds__(256) void gauss_head_kernel(const float* __restrict__ heads, long ldh, const float* __restrict__ eps,
                                                          long lde, float* __restrict__ sigma, long lds,
-                                                         float* __restrict__ actions, long lda, long B, int n) {
+                                                         float* __restrict__ actions, long lda, long B, int n,
+                                                         unsigned long long* __restrict__ act, long act_stride,
+                                                         unsigned long long* __restrict__ cmd,
+                                                         const unsigned int* __restrict__ seq_base, unsigned int seq_off) {
   const long total = B * (long)n;
+  unsigned long long tag = 0;
+  if (PUB) tag = (unsigned long long)(seq_base[0] + seq_off) << 32;
   for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += gridDim.x * 256L) {
     const long b = e / n;
     const int j = (int)(e - b * n);
     const float* row = heads + b * ldh;
     const float s = gauss_sigma(row[n + j]);
     if (sigma != nullptr) sigma[b * lds + j] = s;
-    if (actions != nullptr) actions[b * lda + j] = __fadd_rn(row[j], __fmul_rn(s, eps[b * lde + j]));   // mu + (sigma*eps)
+    if (actions != nullptr) {
+      const float a = __fadd_rn(row[j], __fmul_rn(s, eps[b * lde + j]));   // mu + (sigma*eps)
+      actions[b * lda + j] = a;
+      if (PUB) {
+        __hip_atomic_store(act + b * act_stride + j, tag | (unsigned long long)__float_as_uint(a), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+        if (j == 0) __hip_atomic_store(cmd + b, tag | (unsigned long long)(unsigned int)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
   }
 }
 
@@ -146,18 +162,34 @@ __global__ __launch_bounds__(256) void gauss_fwd_bwd_kernel(const float* __restr
 }
 }  // namespace
 
-extern "C" int a2c_gauss_head(const float* heads, int64_t ld_heads, const float* eps, int64_t ld_eps, float* sigma,
-                              int64_t ld_sigma, float* actions, int64_t ld_act, int64_t B, int n, a2c_stream_t stream) {
+extern "C" int a2c_gauss_head_publish(const float* heads, int64_t ld_heads, const float* eps, int64_t ld_eps, float* sigma,
+                                      int64_t ld_sigma, float* actions, int64_t ld_act, int64_t B, int n, uint64_t* act,
+                                      int64_t act_stride, uint64_t* cmd, const uint32_t* seq_base, uint32_t seq_off,
+                                      a2c_stream_t stream) {
   if (B < 0 || n < 1 || n > A2C_GAUSS_MAX_N || ld_heads < 2 * n) return A2C_ERR_ARG;
   if (sigma == nullptr && actions == nullptr) return A2C_ERR_ARG;
   if (sigma != nullptr && ld_sigma < n) return A2C_ERR_ARG;
   if (actions != nullptr && (eps == nullptr || ld_eps < n || ld_act < n)) return A2C_ERR_ARG;
+  if (cmd != nullptr && (actions == nullptr || act == nullptr || seq_base == nullptr || act_stride < n)) return A2C_ERR_ARG;
   if (B == 0) return A2C_OK;
   if (heads == nullptr) return A2C_ERR_ARG;
-  hipLaunchKernelGGL(gauss_head_kernel, dim3(a2c_grid_1d(B * n, 256)), dim3(256), 0, a2c_s(stream), heads, (long)ld_heads,
-                     eps, (long)ld_eps, sigma, (long)ld_sigma, actions, (long)ld_act, (long)B, n);
+  const dim3 grid(a2c_grid_1d(B * n, 256));
+  if (cmd != nullptr)
+    hipLaunchKernelGGL(gauss_head_kernel<true>, grid, dim3(256), 0, a2c_s(stream), heads, (long)ld_heads, eps, (long)ld_eps,
+                       sigma, (long)ld_sigma, actions, (long)ld_act, (long)B, n, (unsigned long long*)act, (long)act_stride,
+                       (unsigned long long*)cmd, seq_base, seq_off);
+  else
+    hipLaunchKernelGGL(gauss_head_kernel<false>, grid, dim3(256), 0, a2c_s(stream), heads, (long)ld_heads, eps, (long)ld_eps,
+                       sigma, (long)ld_sigma, actions, (long)ld_act, (long)B, n, (unsigned long long*)nullptr, 0L,
+                       (unsigned long long*)nullptr, (const unsigned int*)nullptr, 0u);
   A2C_CHECK_LAUNCH();
   return A2C_OK;
+}
+
+extern "C" int a2c_gauss_head(const float* heads, int64_t ld_heads, const float* eps, int64_t ld_eps, float* sigma,
+                              int64_t ld_sigma, float* actions, int64_t ld_act, int64_t B, int n, a2c_stream_t stream) {
+  return a2c_gauss_head_publish(heads, ld_heads, eps, ld_eps, sigma, ld_sigma, actions, ld_act, B, n, nullptr, 0, nullptr,
+                                nullptr, 0u, stream);
 }
 
 extern "C" int a2c_gauss_loss_sums(const float* heads, int64_t ld_heads, const float* vals, int64_t val_stride,

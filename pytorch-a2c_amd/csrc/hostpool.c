@@ -95,6 +95,31 @@ int a2c_pool_enable_tagged(void *base, size_t region_bytes) {
   return 0;
 }
 
+/* ---- float action granules (continuous policies): see the header comment ---- */
+static size_t act_stride_of(int act_dim) { return align_up((size_t)act_dim, 8); }   /* every env starts a 64-byte line */
+static inline uint64_t *act_of(void *base) { return (uint64_t *)((char *)base + hdr(base)->off_act); }
+
+size_t a2c_pool_bytes_f32(int n_envs, int frame_bytes, int act_dim) {
+  const size_t base = a2c_pool_bytes(n_envs, frame_bytes);
+  if (!base || act_dim < 1 || act_dim > A2C_POOL_MAX_ACT_DIM) return 0;
+  return base + align_up((size_t)n_envs * act_stride_of(act_dim) * 8u, 4096);
+}
+
+int a2c_pool_enable_actions_f32(void *base, size_t region_bytes, int act_dim) {
+  if (a2c_pool_check(base)) return -1;
+  a2c_pool_header *h = hdr(base);
+  if (act_dim < 1 || act_dim > A2C_POOL_MAX_ACT_DIM || h->off_act) return -1;
+  const size_t stride = act_stride_of(act_dim);
+  const size_t off = align_up(h->total_bytes, 4096), need = off + align_up((size_t)h->n_envs * stride * 8u, 4096);
+  if (region_bytes < need) return -1;
+  h->act_dim = (uint32_t)act_dim;
+  h->act_stride = (uint32_t)stride;
+  h->total_bytes = need;
+  memset((char *)base + off, 0xff, (size_t)h->n_envs * stride * 8u);      /* tag 0xffffffff: no step yet */
+  __atomic_store_n(&h->off_act, (uint64_t)off, __ATOMIC_RELEASE);
+  return 0;
+}
+
 /* the mirror of env's packed frame (see a2c_pool_header): every chunk leaves as ONE aligned 16-byte store */
 static void write_tagged(void *base, int env, const uint8_t *packed, uint32_t seq, float rew, int done) {
   const a2c_pool_header *h = chdr(base);
@@ -183,6 +208,35 @@ int a2c_pool_take(void *base, int env0, int n, const uint32_t *next_seq, int64_t
   const int i = a2c_pool_poll(base, env0, n, next_seq, spin_ns);
   if (i >= 0) *action = a2c_pool_action(base, env0 + i);
   return i;
+}
+
+int a2c_pool_take_f32(void *base, int env0, int n, const uint32_t *next_seq, int64_t spin_ns, float *action_out) {
+  const a2c_pool_header *h = chdr(base);
+  if (!h->off_act || !action_out) return -1;
+  const int64_t t0 = now_ns();
+  const int i = a2c_pool_poll(base, env0, n, next_seq, spin_ns);
+  if (i < 0) return i;
+  /* the doorbell of step next_seq[i] is there; its floats count only once EVERY granule carries that step's tag */
+  const uint64_t *g = act_of(base) + (size_t)(env0 + i) * h->act_stride;
+  const uint32_t want = next_seq[i], d = h->act_dim;
+  uint32_t bits[A2C_POOL_MAX_ACT_DIM];
+  for (unsigned sweep = 0;; ++sweep) {
+    uint32_t k = 0;
+    for (; k < d; ++k) {
+      const uint64_t v = __atomic_load_n(g + k, __ATOMIC_ACQUIRE);
+      if ((uint32_t)(v >> 32) != want) break;
+      bits[k] = (uint32_t)v;
+    }
+    if (k == d) {
+      memcpy(action_out, bits, (size_t)d * 4u);
+      return i;
+    }
+    if ((sweep & 15) == 15) {
+      if (a2c_pool_phase(base) == A2C_POOL_SHUTDOWN) return -2;
+      if (now_ns() - t0 > spin_ns) return -1;
+    }
+    cpu_relax();
+  }
 }
 
 void a2c_pool_publish(void *base, int env, const void *frame, uint32_t seq, float rew, int done) {
@@ -307,6 +361,23 @@ void a2c_pool_post_actions(void *base, int env0, int n, const int64_t *actions, 
   uint64_t *c = cmd_of(base) + env0;
   for (int i = 0; i < n; ++i)
     __atomic_store_n(c + i, ((uint64_t)seq << 32) | (uint32_t)(int32_t)actions[(int64_t)i * stride], __ATOMIC_RELEASE);
+}
+
+void a2c_pool_post_actions_f32(void *base, int env0, int n, const float *actions, int64_t stride, uint32_t seq) {
+  const a2c_pool_header *h = chdr(base);
+  if (!h->off_act) return;
+  uint64_t *c = cmd_of(base) + env0;
+  const uint32_t d = h->act_dim;
+  for (int i = 0; i < n; ++i) {
+    uint64_t *g = act_of(base) + (size_t)(env0 + i) * h->act_stride;
+    const float *a = actions + (int64_t)i * stride;
+    for (uint32_t k = 0; k < d; ++k) {
+      uint32_t b;
+      memcpy(&b, a + k, 4);
+      __atomic_store_n(g + k, ((uint64_t)seq << 32) | b, __ATOMIC_RELAXED);     /* data and tag in one granule */
+    }
+    __atomic_store_n(c + i, ((uint64_t)seq << 32) | d, __ATOMIC_RELEASE);
+  }
 }
 
 int a2c_pool_wait_frames(void *base, int env0, int n, uint32_t seq, int64_t timeout_ns) {
