@@ -891,6 +891,35 @@ int a2c_snake_step(int32_t *state, const int64_t *actions, int64_t act_stride, i
                    uint32_t seed, int G, int unit, int n_foods, float *rew, float *done, float *reset, float *frames,
                    uint8_t *rgb, int32_t *ep_stats, a2c_stream_t stream);
 
+/* ------------------------------------------------------------------ Pong worlds in device memory (csrc/pong.hip)
+ * The reference's main env (preprocessing.py:11-17 pong_prep, the "Pong" done override of runner.py:212-214) with this
+ * project's own integer rules (the host twin a2c_amd/pong.py produces the same integers; parity with
+ * ALE is not claimed).  Field 80 x 80; opponent paddle in columns 8..9, agent paddle in columns 70..71 (2 x 8 each), a
+ * 2 x 2 ball; a prepped frame is 6400 floats, 1 on the three rectangles, 0 elsewhere.  World parameters and their bounds
+ * (anything else returns A2C_ERR_ARG without a launch): 1 <= points_to_win <= 21, 1 <= max_episode_steps <= 2^24,
+ * 1 <= opp_skill_den <= 2^16, 0 <= opp_skill_num <= opp_skill_den (the opponent moves on the steps whose draw mod den is
+ * below num).  Also A2C_ERR_ARG: B <= 0, env_id0 < 0, act_stride < 0, a NULL state / actions / frames / rew / done / reset,
+ * frames not 16-byte aligned, frame_ld < 6400 or not a multiple of 4.  Env e of a launch is world env_id0 + e of `seed`:
+ * draw i of a world is hash32(seed, env_id, i).  The state of one env is 16 int32 words: agent paddle y, opponent paddle
+ * y, ball x, ball y, vx, vy, agent score, opponent score, draw counter, step counter, episode-step counter, reward since
+ * the last done, 4 spare.  The kernels advance the counters in device memory: a captured launch plays new steps at each
+ * replay.
+ * a2c_pong_state_bytes: bytes of ONE env's state, 0 for an unsupported points_to_win.                                  */
+size_t a2c_pong_state_bytes(int points_to_win);
+/* starts B worlds (counters to 0, scores to 0, paddles centred, then the serve draw): state (B rows of 16 words) and
+ * frames (B rows of 6400 floats, frame_ld floats apart).                                                               */
+int a2c_pong_reset(int32_t *state, int B, int env_id0, uint32_t seed, int points_to_win, int max_episode_steps,
+                   int opp_skill_num, int opp_skill_den, float *frames, int64_t frame_ld, a2c_stream_t stream);
+/* one step of B worlds: env e takes (actions[e * act_stride] + action_shift) mod 3 (0 stay, 1 up, 2 down).  rew: +1 the
+ * opponent missed, -1 the agent missed, else 0.  reset: 1 when the episode ended (a score reached points_to_win, or
+ * max_episode_steps steps): the world has already been restarted and `frames` holds its reset frame, what
+ * utils.next_state(reset=True) expects.  done = (rew != 0) or reset, the done of a "Pong" env type.  ep_count /
+ * ep_rew_sum (each may be NULL): one int32 each, added to with atomics -- the dones, and the rewards they closed.       */
+int a2c_pong_step(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                  uint32_t seed, int points_to_win, int max_episode_steps, int opp_skill_num, int opp_skill_den,
+                  float *frames, int64_t frame_ld, float *rew, float *done, float *reset, int32_t *ep_count,
+                  int32_t *ep_rew_sum, a2c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

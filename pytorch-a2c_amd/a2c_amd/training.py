@@ -69,6 +69,10 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     ``env_type`` "Snake-device" / "Snake-host" (a2c_amd/snake.py; keys ``grid_size``, ``unit_size``, ``n_foods``) need no
     gym: the first plays ``n_envs`` worlds in device memory (``DeviceSnakePool``), the second ``SnakeEnv``s behind the usual
     ``env_pool`` choices with ``prep_fxn="snake_prep"``; both are evaluated on host ``SnakeEnv``s.
+    ``env_type`` "Pong-device" / "Pong-host" (a2c_amd/pong.py; keys ``points_to_win``, ``max_episode_steps``,
+    ``opp_skill_num``, ``opp_skill_den``) likewise: ``DevicePongPool``, or ``PongEnv``s behind the usual pools with
+    ``prep_fxn="pong_prep"`` (the process pool carries their {0, 1} frames packed, one bit per pixel); 3 actions,
+    ``action_shift`` 0 unless given, the "Pong" done override applies, evaluation on host ``PongEnv``s.
     Returns the best evaluation reward."""
     hyps = dict(DEFAULTS, **hyps)
     if hyps["n_rollouts"] is None:
@@ -88,7 +92,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     # environments
     serial = try_key(hyps, "env_pool", "process") == "serial"
     probe = None
-    snake_world = None
+    snake_world = pong_world = None
     if env_fn is None and hyps["env_type"] in ("Snake-device", "Snake-host"):
         from . import snake
         G, unit, n_foods = snake_world = snake.world_from_hyps(hyps)
@@ -110,6 +114,28 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
             pool = ProcessEnvPool(SequentialEnvironment, hyps["n_envs"], env_kwargs=kws,
                                   n_workers=try_key(hyps, "n_env_workers", None), pong=False,
                                   action_shift=try_key(hyps, "action_shift", 0), frame_bits=False)
+    elif env_fn is None and hyps["env_type"] in ("Pong-device", "Pong-host"):
+        from . import pong
+        pong_world = pong.world_from_hyps(hyps)
+        hyps["prep_fxn"], hyps["preprocessor"] = "pong_prep", preprocessing.pong_prep
+        hyps["is_discrete"], n_act = True, pong.N_ACTIONS
+        hyps["max_eval_steps"] = try_key(hyps, "max_eval_steps", 2000)
+        world = dict(zip(("points_to_win", "max_episode_steps", "opp_skill_num", "opp_skill_den"), pong_world),
+                     seed=hyps["seed"])
+        mk_env = lambda j: SequentialEnvironment(hyps["env_type"], preprocessing.pong_prep, seed=hyps["seed"],
+                                                 env_fn=pong.PongFactory(env_id=j, **world))
+        if hyps["env_type"] == "Pong-device":
+            pool = pong.DevicePongPool(hyps["n_envs"], device=cuda_if(torch.zeros(1)).device, **world)
+        elif serial:
+            pool = HostEnvPool([mk_env(j) for j in range(hyps["n_envs"])], frame_shape=pong.DevicePongPool.frame_shape)
+        else:
+            from .hostpool import ProcessEnvPool
+            kws = [dict(env_type=hyps["env_type"], preprocessor=preprocessing.pong_prep, seed=hyps["seed"],
+                        env_fn=pong.PongFactory(env_id=j, **world)) for j in range(hyps["n_envs"])]
+            # pong_prep yields {0,1} uint8 planes: one bit per pixel crosses the host link
+            pool = ProcessEnvPool(SequentialEnvironment, hyps["n_envs"], env_kwargs=kws,
+                                  n_workers=try_key(hyps, "n_env_workers", None), pong=True,
+                                  action_shift=try_key(hyps, "action_shift", 0), frame_bits=True)
     elif env_fn is None:
         hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
         probe = eval_env or SequentialEnvironment(**hyps)             # the probe for shapes (training.py:60-65)
@@ -130,7 +156,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     f32_dim = None
     if not hyps["is_discrete"] and not serial:
         f32_dim = int(n_act if env_fn is None else hyps["action_size"])
-    if snake_world is not None:
+    if snake_world is not None or pong_world is not None:
         pass
     elif env_fn is None:
         kws = [dict({k: v for k, v in hyps.items() if k != "seed"}, seed=hyps["seed"] + j) for j in range(hyps["n_envs"])]
@@ -209,7 +235,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     # evaluation: the caller's single env (reference loop), else n_test_eps gym envs in lock-step on the device
     if eval_env is not None:
         stats_runner = StatsRunner(hyps, env=eval_env)
-    elif snake_world is not None:      # host twins of worlds the training pool does not play (env ids from 10007 on)
+    elif snake_world is not None or pong_world is not None:      # host twins of worlds the training pool does not play (env ids from 10007 on)
         stats_runner = StatsRunner(hyps, envs=[mk_env(10007 + j) for j in range(try_key(hyps, "n_test_eps", 15))])
     else:
         stats_runner = StatsRunner(hyps) if env_fn is None else None

@@ -1,0 +1,184 @@
+// Pong worlds in device memory: a2c_pong_reset / a2c_pong_step (rules: DESIGN.md section 6c; host twin: a2c_amd/pong.py).
+//
+// One wavefront per env.  The state of an env is PONG_WORDS int32 words in HBM; a step is a short, loop-free, wave-uniform
+// integer computation (every lane computes the same values from the same words), after which lanes 0..PONG_WORDS-1 store
+// one word each and all 64 lanes render the 80 x 80 prepped frame row (1 on the two paddles and the ball, 0 elsewhere)
+// as 16-byte stores where the frame-stack kernels read it.  The draw, step and episode-step counters are part of the
+// state the kernel advances, so a captured launch plays NEW steps at every replay.
+#include "a2c_common.h"
+#include "pong_rng.h"
+
+namespace {
+
+constexpr int PONG_WORDS = 16;      // agent y, opponent y, ball x, ball y, vx, vy, agent score, opponent score, draws, steps,
+                                    // episode steps, reward since the last done, 4 spare
+constexpr int PW = 80, PH = 80, PONG_HW = PW * PH;
+constexpr int PADDLE_H = 8, PADDLE_W = 2, BALL = 2;
+constexpr int OPP_X = 8, AGENT_X = 70;
+constexpr int PADDLE_MAX_Y = PH - PADDLE_H, BALL_MAX_Y = PH - BALL;
+constexpr int PADDLE_START_Y = 36, SERVE_X = 39, SERVE_Y = 39;
+constexpr int MISS_RIGHT = AGENT_X + PADDLE_W, MISS_LEFT = OPP_X - BALL;
+constexpr int MAX_POINTS = 21, MAX_EPISODE_STEPS = 1 << 24, MAX_SKILL_DEN = 1 << 16;
+
+struct PongWorld {
+  int ay, oy, bx, by, vx, vy, sa, so;
+};
+
+__device__ __forceinline__ int pong_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// the hit table: off = ball y + 1 - paddle y in 0..8 -> vy = {-2,-2,-1,-1,0,1,1,2,2}[off], |vx| = {2,2,1,1,1,1,1,2,2}[off]
+__device__ __forceinline__ int pong_hit_vy(int off) { return off <= 1 ? -2 : (off <= 3 ? -1 : (off == 4 ? 0 : (off <= 6 ? 1 : 2))); }
+__device__ __forceinline__ int pong_hit_speed(int off) { return (off <= 1 || off >= 7) ? 2 : 1; }
+
+__device__ __forceinline__ void pong_serve(PongWorld& w, uint32_t d, bool towards_agent) {
+  w.bx = SERVE_X; w.by = SERVE_Y;
+  w.vx = towards_agent ? 1 : -1;
+  w.vy = (int)((d >> 1) % 5u) - 2;
+}
+
+__device__ __forceinline__ void pong_new_episode(PongWorld& w, uint32_t seed, uint32_t env, uint32_t& draws, int& ep_steps) {
+  w.ay = w.oy = PADDLE_START_Y;
+  w.sa = w.so = 0;
+  ep_steps = 0;
+  const uint32_t d = pong_hash(seed, env, draws++);
+  pong_serve(w, d, (d & 1u) != 0u);
+}
+
+__device__ __forceinline__ bool pong_in(int x, int y, int rx, int ry, int rw, int rh) {
+  return x >= rx && x < rx + rw && y >= ry && y < ry + rh;
+}
+
+// the prepped frame row: PONG_HW floats as float4 stores, 4 pixels of one row each (PW % 4 == 0)
+__device__ __forceinline__ void pong_write_frame(const PongWorld& w, float* __restrict__ frame, int lane) {
+  float4* f4 = reinterpret_cast<float4*>(frame);
+  for (int q = lane; q < PONG_HW / 4; q += 64) {
+    const int y = q / (PW / 4), x0 = 4 * (q - y * (PW / 4));
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int x = x0 + j;
+      const bool on = pong_in(x, y, OPP_X, w.oy, PADDLE_W, PADDLE_H) || pong_in(x, y, AGENT_X, w.ay, PADDLE_W, PADDLE_H) ||
+                      pong_in(x, y, w.bx, w.by, BALL, BALL);
+      v[j] = on ? 1.0f : 0.0f;
+    }
+    f4[q] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+template <bool STEP>
+__global__ __launch_bounds__(64) void pong_kernel(int32_t* __restrict__ state, const int64_t* __restrict__ actions,
+                                                  int64_t act_stride, int action_shift, int env_id0, uint32_t seed,
+                                                  int points_to_win, int max_episode_steps, int skill_num, int skill_den,
+                                                  float* __restrict__ frames, int64_t frame_ld, float* __restrict__ rew,
+                                                  float* __restrict__ done, float* __restrict__ reset,
+                                                  int32_t* __restrict__ ep_count, int32_t* __restrict__ ep_rew_sum) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  const uint32_t env = (uint32_t)(env_id0 + e);
+  int32_t* st = state + (int64_t)e * PONG_WORDS;
+  PongWorld w;
+  uint32_t draws = 0u;
+  int steps = 0, ep_steps = 0, ep_rew = 0;
+  if (STEP) {
+    w.ay = st[0]; w.oy = st[1]; w.bx = st[2]; w.by = st[3]; w.vx = st[4]; w.vy = st[5]; w.sa = st[6]; w.so = st[7];
+    draws = (uint32_t)st[8]; steps = st[9]; ep_steps = st[10]; ep_rew = st[11];
+    const int64_t a64 = (actions[(int64_t)e * act_stride] + (int64_t)action_shift) % 3;
+    const int a = (int)(a64 < 0 ? a64 + 3 : a64);
+    ++steps;
+    ++ep_steps;
+    // 1. the agent's paddle
+    w.ay = pong_clamp(w.ay + (a == 1 ? -2 : (a == 2 ? 2 : 0)), 0, PADDLE_MAX_Y);
+    // 2. the opponent's paddle: towards the ball's centre, on the steps the draw allows
+    if ((int)(pong_hash(seed, env, draws++) % (uint32_t)skill_den) < skill_num) {
+      const int cb = w.by + 1, cp = w.oy + PADDLE_H / 2;
+      w.oy = pong_clamp(w.oy + (cb < cp ? -1 : (cb > cp ? 1 : 0)), 0, PADDLE_MAX_Y);
+    }
+    // 3. the ball, the walls
+    const int x0 = w.bx;
+    int x = x0 + w.vx, y = w.by + w.vy;
+    if (y < 0) { y = -y; w.vy = -w.vy; }
+    else if (y > BALL_MAX_Y) { y = 2 * BALL_MAX_Y - y; w.vy = -w.vy; }
+    // 4. the paddles
+    if (w.vx > 0 && x0 + 1 < AGENT_X && x + 1 >= AGENT_X && y >= w.ay - 1 && y <= w.ay + PADDLE_H - 1) {
+      const int off = y + 1 - w.ay;
+      x = AGENT_X - BALL; w.vx = -pong_hit_speed(off); w.vy = pong_hit_vy(off);
+    } else if (w.vx < 0 && x0 > OPP_X + 1 && x <= OPP_X + 1 && y >= w.oy - 1 && y <= w.oy + PADDLE_H - 1) {
+      const int off = y + 1 - w.oy;
+      x = OPP_X + PADDLE_W; w.vx = pong_hit_speed(off); w.vy = pong_hit_vy(off);
+    }
+    w.bx = x; w.by = y;
+    // 5. a point
+    int r = 0;
+    if (x >= MISS_RIGHT) { r = -1; ++w.so; }
+    else if (x <= MISS_LEFT) { r = 1; ++w.sa; }
+    // 6. the end of the episode, or the serve
+    const bool over = w.sa >= points_to_win || w.so >= points_to_win || ep_steps >= max_episode_steps;
+    const bool closed = over || r != 0;          // the `done` of a "Pong" env type (runner.py:212-214)
+    ep_rew += r;
+    if (closed) {
+      if (lane == 0) {
+        if (ep_count != nullptr) atomicAdd(ep_count, 1);
+        if (ep_rew_sum != nullptr) atomicAdd(ep_rew_sum, ep_rew);
+      }
+      ep_rew = 0;
+    }
+    if (over) pong_new_episode(w, seed, env, draws, ep_steps);
+    else if (r != 0) pong_serve(w, pong_hash(seed, env, draws++), r < 0);
+    if (lane == 0) {
+      rew[e] = (float)r;
+      done[e] = closed ? 1.0f : 0.0f;
+      reset[e] = over ? 1.0f : 0.0f;
+    }
+  } else {
+    pong_new_episode(w, seed, env, draws, ep_steps);
+  }
+  if (lane < PONG_WORDS) {
+    const int hv = lane == 0 ? w.ay : lane == 1 ? w.oy : lane == 2 ? w.bx : lane == 3 ? w.by : lane == 4 ? w.vx
+                 : lane == 5 ? w.vy : lane == 6 ? w.sa : lane == 7 ? w.so : lane == 8 ? (int)draws : lane == 9 ? steps
+                 : lane == 10 ? ep_steps : lane == 11 ? ep_rew : 0;
+    st[lane] = hv;
+  }
+  pong_write_frame(w, frames + (int64_t)e * frame_ld, lane);
+}
+
+bool pong_world_ok(int points_to_win, int max_episode_steps, int skill_num, int skill_den) {
+  return points_to_win >= 1 && points_to_win <= MAX_POINTS && max_episode_steps >= 1 && max_episode_steps <= MAX_EPISODE_STEPS &&
+         skill_den >= 1 && skill_den <= MAX_SKILL_DEN && skill_num >= 0 && skill_num <= skill_den;
+}
+
+bool pong_frames_ok(const float* frames, int64_t frame_ld) {
+  return frames != nullptr && ((uintptr_t)frames & 15u) == 0 && frame_ld >= PONG_HW && frame_ld % 4 == 0;
+}
+
+}  // namespace
+
+extern "C" size_t a2c_pong_state_bytes(int points_to_win) {
+  if (points_to_win < 1 || points_to_win > MAX_POINTS) return 0;
+  return sizeof(int32_t) * (size_t)PONG_WORDS;
+}
+
+extern "C" int a2c_pong_reset(int32_t* state, int B, int env_id0, uint32_t seed, int points_to_win, int max_episode_steps,
+                              int opp_skill_num, int opp_skill_den, float* frames, int64_t frame_ld, a2c_stream_t stream) {
+  if (B <= 0 || env_id0 < 0 || !pong_world_ok(points_to_win, max_episode_steps, opp_skill_num, opp_skill_den))
+    return A2C_ERR_ARG;
+  if (state == nullptr || !pong_frames_ok(frames, frame_ld)) return A2C_ERR_ARG;
+  hipLaunchKernelGGL(pong_kernel<false>, dim3(B), dim3(64), 0, a2c_s(stream), state, (const int64_t*)nullptr, (int64_t)0, 0,
+                     env_id0, seed, points_to_win, max_episode_steps, opp_skill_num, opp_skill_den, frames, frame_ld,
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+extern "C" int a2c_pong_step(int32_t* state, const int64_t* actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                             uint32_t seed, int points_to_win, int max_episode_steps, int opp_skill_num, int opp_skill_den,
+                             float* frames, int64_t frame_ld, float* rew, float* done, float* reset, int32_t* ep_count,
+                             int32_t* ep_rew_sum, a2c_stream_t stream) {
+  if (B <= 0 || env_id0 < 0 || act_stride < 0 || !pong_world_ok(points_to_win, max_episode_steps, opp_skill_num, opp_skill_den))
+    return A2C_ERR_ARG;
+  if (state == nullptr || actions == nullptr || rew == nullptr || done == nullptr || reset == nullptr ||
+      !pong_frames_ok(frames, frame_ld))
+    return A2C_ERR_ARG;
+  hipLaunchKernelGGL(pong_kernel<true>, dim3(B), dim3(64), 0, a2c_s(stream), state, actions, act_stride, action_shift, env_id0,
+                     seed, points_to_win, max_episode_steps, opp_skill_num, opp_skill_den, frames, frame_ld, rew, done, reset,
+                     ep_count, ep_rew_sum);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
