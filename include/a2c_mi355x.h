@@ -920,6 +920,34 @@ int a2c_pong_step(int32_t *state, const int64_t *actions, int64_t act_stride, in
                   float *frames, int64_t frame_ld, float *rew, float *done, float *reset, int32_t *ep_count,
                   int32_t *ep_rew_sum, a2c_stream_t stream);
 
+/* ------------------------------------------------------------------ Breakout worlds in device memory (csrc/breakout.hip)
+ * The env of the reference's Breakout runs (preprocessing.py:19-23 breakout_prep: grey frames with more than two levels,
+ * real dones only) with this project's own integer rules (the host twin a2c_amd/breakout.py produces
+ * the same integers; parity with ALE is not claimed).  Field 72 columns x 80 rows; 6 x 18 bricks of 4 x 3 pixels from row
+ * 11 on (grey levels 200, 198, 180, 162, 72, 66 and 7, 7, 4, 4, 1, 1 points by row, top row first), an 8 x 2 paddle in rows
+ * 77..78 and a 2 x 2 ball, both of level 200; a prepped frame is 5760 floats holding those levels, 0 elsewhere.  World
+ * parameters and their bounds (anything else returns A2C_ERR_ARG without a launch): 1 <= lives <= 5,
+ * 1 <= max_episode_steps <= 2^24.  Also A2C_ERR_ARG: B <= 0, env_id0 < 0, act_stride < 0, a NULL state / actions / frames /
+ * rew / done / reset, frames not 16-byte aligned, frame_ld < 5760 or not a multiple of 4.  Env e of a launch is world
+ * env_id0 + e of `seed`: draw i of a world is hash32(seed, env_id, i); the only draws are serves.  The state of one env is
+ * 24 int32 words: paddle x, ball x, ball y, vx, vy, lives left, bricks left, draw counter, step counter, episode-step
+ * counter, reward since the last done, the six brick rows' masks (bit c = brick column c alive, top row first), 7 spare.
+ * The kernels advance the counters in device memory: a captured launch plays new steps at each replay.
+ * a2c_breakout_state_bytes: bytes of ONE env's state, 0 for an unsupported lives.                                        */
+size_t a2c_breakout_state_bytes(int lives);
+/* starts B worlds (counters to 0, all 108 bricks, `lives` lives, the paddle at x = 32, then the serve draw): state (B rows
+ * of 24 words) and frames (B rows of 5760 floats, frame_ld floats apart).                                                */
+int a2c_breakout_reset(int32_t *state, int B, int env_id0, uint32_t seed, int lives, int max_episode_steps, float *frames,
+                       int64_t frame_ld, a2c_stream_t stream);
+/* one step of B worlds: env e takes (actions[e * act_stride] + action_shift) mod 4 (0 nothing, 1 = ALE's FIRE: nothing,
+ * 2 right, 3 left).  rew: the points of the brick the ball removed, else 0.  done == reset: 1 when the episode ended (no
+ * life left, no brick left, or max_episode_steps steps): the world has already been restarted and `frames` holds its reset
+ * frame, what utils.next_state(reset=True) expects.  ep_count / ep_rew_sum (each may be NULL): one int32 each, added to
+ * with atomics -- the episodes finished, and the sum of their rewards.                                                   */
+int a2c_breakout_step(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                      uint32_t seed, int lives, int max_episode_steps, float *frames, int64_t frame_ld, float *rew,
+                      float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, a2c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

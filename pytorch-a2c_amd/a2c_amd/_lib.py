@@ -197,6 +197,9 @@ SIGNATURES = {
     "a2c_pong_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, c_int, c_int, c_int, P, c_int64, P]),
     "a2c_pong_step": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, c_int, c_int, P, c_int64, P, P, P, P,
                               P, P]),
+    "a2c_breakout_state_bytes": (c_size_t, [c_int]),
+    "a2c_breakout_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P]),
+    "a2c_breakout_step": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P, P, P]),
 }
 
 _lib = None

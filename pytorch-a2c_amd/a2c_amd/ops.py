@@ -1266,3 +1266,28 @@ def pong_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, po
     check(lib().a2c_pong_step(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
                               max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew), _p(done),
                               _p(reset), _p(ep_count), _p(ep_rew_sum), _st(st)), "a2c_pong_step")
+
+
+# ---------------------------------------------------------------- Breakout worlds in device memory (csrc/breakout.hip)
+def breakout_state_bytes(lives=5):
+    """bytes of one env's state; raises for a world the kernels do not support"""
+    n = int(lib().a2c_breakout_state_bytes(lives))
+    if n == 0:
+        raise ValueError(f"a2c_breakout_state_bytes: unsupported world lives={lives}")
+    return n
+
+
+def breakout_reset(state, B, env_id0, seed, lives, max_episode_steps, frames, frame_ld, st=None):
+    _chk(state, "state", torch.int32); _chk(frames, "frames")
+    check(lib().a2c_breakout_reset(_p(state), B, env_id0, seed, lives, max_episode_steps, _p(frames), frame_ld, _st(st)),
+          "a2c_breakout_reset")
+
+
+def breakout_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames, frame_ld,
+                  rew, done, reset, ep_count=None, ep_rew_sum=None, st=None):
+    """actions_ptr: address of env 0's int64 action, ``act_stride`` elements between envs (a row of the rollout buffer)"""
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
+    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    check(lib().a2c_breakout_step(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
+                                  max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
+                                  _p(ep_rew_sum), _st(st)), "a2c_breakout_step")

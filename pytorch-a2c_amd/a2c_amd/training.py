@@ -73,6 +73,11 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     ``opp_skill_num``, ``opp_skill_den``) likewise: ``DevicePongPool``, or ``PongEnv``s behind the usual pools with
     ``prep_fxn="pong_prep"`` (the process pool carries their {0, 1} frames packed, one bit per pixel); 3 actions,
     ``action_shift`` 0 unless given, the "Pong" done override applies, evaluation on host ``PongEnv``s.
+    ``env_type`` "Breakout-device" / "Breakout-host" (a2c_amd/breakout.py; keys ``lives``, ``max_episode_steps``) likewise:
+    ``DeviceBreakoutPool``, or ``BreakoutEnv``s behind the usual pools with ``prep_fxn="breakout_prep"`` (grey levels
+    0..255 on the uint8 transport; with ``hyps["device_prep"] = "breakout_prep"`` the process pool carries the RAW frames
+    and the device preps them); 4 actions, ``action_shift`` 0 unless given, real dones only, evaluation on host
+    ``BreakoutEnv``s.
     Returns the best evaluation reward."""
     hyps = dict(DEFAULTS, **hyps)
     if hyps["n_rollouts"] is None:
@@ -92,7 +97,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     # environments
     serial = try_key(hyps, "env_pool", "process") == "serial"
     probe = None
-    snake_world = pong_world = None
+    snake_world = pong_world = breakout_world = None
     if env_fn is None and hyps["env_type"] in ("Snake-device", "Snake-host"):
         from . import snake
         G, unit, n_foods = snake_world = snake.world_from_hyps(hyps)
@@ -136,6 +141,33 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
             pool = ProcessEnvPool(SequentialEnvironment, hyps["n_envs"], env_kwargs=kws,
                                   n_workers=try_key(hyps, "n_env_workers", None), pong=True,
                                   action_shift=try_key(hyps, "action_shift", 0), frame_bits=True)
+    elif env_fn is None and hyps["env_type"] in ("Breakout-device", "Breakout-host"):
+        from . import breakout
+        breakout_world = breakout.world_from_hyps(hyps)
+        # device_prep: the workers hand on the RAW frames (null_prep) and a2c_frame_prep_u8 crops / strides them
+        raw = try_key(hyps, "device_prep", None) is not None
+        if raw and (hyps["device_prep"] != "breakout_prep" or hyps["env_type"] == "Breakout-device" or serial):
+            raise ValueError("a2c_amd: device_prep on Breakout worlds is 'breakout_prep', on env_type='Breakout-host' behind "
+                             "the process env pool (the device worlds write prepped frames themselves)")
+        hyps["prep_fxn"] = "null_prep" if raw else "breakout_prep"
+        prep = hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
+        hyps["is_discrete"], n_act = True, breakout.N_ACTIONS
+        hyps["max_eval_steps"] = try_key(hyps, "max_eval_steps", 2000)
+        world = dict(zip(("lives", "max_episode_steps"), breakout_world), seed=hyps["seed"])
+        mk_env = lambda j: SequentialEnvironment(hyps["env_type"], preprocessing.breakout_prep, seed=hyps["seed"],
+                                                 env_fn=breakout.BreakoutFactory(env_id=j, **world))
+        if hyps["env_type"] == "Breakout-device":
+            pool = breakout.DeviceBreakoutPool(hyps["n_envs"], device=cuda_if(torch.zeros(1)).device, **world)
+        elif serial:
+            pool = HostEnvPool([mk_env(j) for j in range(hyps["n_envs"])], frame_shape=breakout.DeviceBreakoutPool.frame_shape)
+        else:
+            from .hostpool import ProcessEnvPool
+            kws = [dict(env_type=hyps["env_type"], preprocessor=prep, seed=hyps["seed"],
+                        env_fn=breakout.BreakoutFactory(env_id=j, **world)) for j in range(hyps["n_envs"])]
+            # grey levels 0..255: one byte per pixel crosses the host link (the packed one-bit transport does not apply)
+            pool = ProcessEnvPool(SequentialEnvironment, hyps["n_envs"], env_kwargs=kws,
+                                  n_workers=try_key(hyps, "n_env_workers", None), pong=False,
+                                  action_shift=try_key(hyps, "action_shift", 0), frame_bits=False)
     elif env_fn is None:
         hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
         probe = eval_env or SequentialEnvironment(**hyps)             # the probe for shapes (training.py:60-65)
@@ -156,7 +188,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     f32_dim = None
     if not hyps["is_discrete"] and not serial:
         f32_dim = int(n_act if env_fn is None else hyps["action_size"])
-    if snake_world is not None or pong_world is not None:
+    if snake_world is not None or pong_world is not None or breakout_world is not None:
         pass
     elif env_fn is None:
         kws = [dict({k: v for k, v in hyps.items() if k != "seed"}, seed=hyps["seed"] + j) for j in range(hyps["n_envs"])]
@@ -183,6 +215,8 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                                   probe_reset=True, frame_bits=bool(try_key(hyps, "frame_bits", False)), action_dim=f32_dim)
         n_act = hyps["action_size"]
     hyps["state_shape"] = [hyps["n_frame_stack"]] + list(pool.frame_shape[1:])
+    if breakout_world is not None and raw:      # the pool carries raw frames: the states are what the device makes of them
+        hyps["state_shape"] = [hyps["n_frame_stack"]] + list(breakout.DeviceBreakoutPool.frame_shape[1:])
     if hyps["env_type"] == "Pong-v0":
         action_size, hyps["action_shift"] = 3, 1                      # training.py:67-69
     else:
@@ -235,7 +269,8 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     # evaluation: the caller's single env (reference loop), else n_test_eps gym envs in lock-step on the device
     if eval_env is not None:
         stats_runner = StatsRunner(hyps, env=eval_env)
-    elif snake_world is not None or pong_world is not None:      # host twins of worlds the training pool does not play (env ids from 10007 on)
+    elif snake_world is not None or pong_world is not None or breakout_world is not None:
+        # host twins of worlds the training pool does not play (env ids from 10007 on)
         stats_runner = StatsRunner(hyps, envs=[mk_env(10007 + j) for j in range(try_key(hyps, "n_test_eps", 15))])
     else:
         stats_runner = StatsRunner(hyps) if env_fn is None else None

@@ -1,0 +1,211 @@
+// Breakout worlds in device memory: a2c_breakout_reset / a2c_breakout_step (rules: DESIGN.md section 6d; host twin:
+// a2c_amd/breakout.py).
+//
+// One wavefront per env.  The state of an env is BRK_WORDS int32 words in HBM; a step is a short, loop-free, wave-uniform
+// integer computation (every lane computes the same values from the same words), after which lanes 0..BRK_WORDS-1 store
+// one word each and all 64 lanes render the 80 x 72 prepped frame row (the grey levels breakout_prep hands on, as floats)
+// as 16-byte stores where the frame-stack kernels read it.  72 / 4 = 18 = the number of brick columns, so a 16-byte store
+// lies in one brick column of one row: its brick test is one shift of one row mask.  The draw, step and episode-step
+// counters are part of the state the kernel advances, so a captured launch plays NEW steps at every replay.
+#include "a2c_common.h"
+#include "pong_rng.h"
+
+namespace {
+
+constexpr int BRK_WORDS = 24;       // paddle x, ball x, ball y, vx, vy, lives, bricks left, draws, steps, episode steps,
+                                    // reward since the last done, the 6 brick rows' 18-bit masks, 7 spare
+constexpr int BW = 72, BH = 80, BRK_HW = BW * BH;
+constexpr int BRICK_ROWS = 6, BRICK_COLS = 18, BRICK_W = 4, BRICK_H = 3, BRICK_TOP = 11;
+constexpr int BRICK_BOTTOM = BRICK_TOP + BRICK_ROWS * BRICK_H;
+constexpr int FULL_ROW = (1 << BRICK_COLS) - 1, N_BRICKS = BRICK_ROWS * BRICK_COLS;
+constexpr int PADDLE_W = 8, PADDLE_H = 2, PADDLE_Y = 77, PADDLE_SPEED = 3, PADDLE_START_X = 32, PADDLE_MAX_X = BW - PADDLE_W;
+constexpr int BALL = 2, BALL_MAX_X = BW - BALL, LOST_Y = 78;
+constexpr int SERVE_Y = 40, SERVE_X0 = 8, SERVE_SPAN = 56;
+constexpr int MAX_LIVES = 5, MAX_EPISODE_STEPS = 1 << 24;
+constexpr float LEVEL = 200.0f;     // the paddle and the ball
+
+static_assert(BW == BRICK_COLS * BRICK_W && BRICK_W == 4, "one 16-byte store per brick column");
+
+struct BrkWorld {
+  int px, bx, by, vx, vy, lives, left;
+  int rows[BRICK_ROWS];
+};
+
+__device__ __forceinline__ int brk_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// grey level (channel 0 of ALE's brick colours) and points of brick row r, top row first
+__device__ __forceinline__ float brk_row_level(int r) {
+  return r == 0 ? 200.0f : (r == 1 ? 198.0f : (r == 2 ? 180.0f : (r == 3 ? 162.0f : (r == 4 ? 72.0f : 66.0f))));
+}
+__device__ __forceinline__ int brk_row_points(int r) { return r < 2 ? 7 : (r < 4 ? 4 : 1); }
+__device__ __forceinline__ int brk_row_mask(const BrkWorld& w, int r) {
+  return r == 0 ? w.rows[0] : (r == 1 ? w.rows[1] : (r == 2 ? w.rows[2] : (r == 3 ? w.rows[3] : (r == 4 ? w.rows[4] : w.rows[5]))));
+}
+// the hit table: off = ball x + 1 - paddle x in 0..8 -> vx = {-2,-2,-1,-1,s,1,1,2,2}[off], s = +-1 with the sign vx had
+__device__ __forceinline__ int brk_hit_vx(int off, int vx) {
+  return off <= 1 ? -2 : (off <= 3 ? -1 : (off == 4 ? (vx > 0 ? 1 : -1) : (off <= 6 ? 1 : 2)));
+}
+
+__device__ __forceinline__ void brk_serve(BrkWorld& w, uint32_t d) {
+  w.bx = SERVE_X0 + (int)(d % (uint32_t)SERVE_SPAN); w.by = SERVE_Y;
+  w.vx = ((d >> 8) & 1u) ? 1 : -1;
+  w.vy = -1;
+}
+
+__device__ __forceinline__ void brk_new_episode(BrkWorld& w, uint32_t seed, uint32_t env, int lives, uint32_t& draws,
+                                                int& ep_steps) {
+#pragma unroll
+  for (int r = 0; r < BRICK_ROWS; ++r) w.rows[r] = FULL_ROW;
+  w.left = N_BRICKS;
+  w.lives = lives;
+  w.px = PADDLE_START_X;
+  ep_steps = 0;
+  brk_serve(w, pong_hash(seed, env, draws++));
+}
+
+// the prepped frame row: BRK_HW floats as float4 stores, the 4 pixels of one brick column in one row each
+__device__ __forceinline__ void brk_write_frame(const BrkWorld& w, float* __restrict__ frame, int lane) {
+  float4* f4 = reinterpret_cast<float4*>(frame);
+  for (int q = lane; q < BRK_HW / 4; q += 64) {
+    const int y = q / BRICK_COLS, c = q - y * BRICK_COLS, x0 = BRICK_W * c;
+    float base = 0.0f;
+    if (y >= BRICK_TOP && y < BRICK_BOTTOM) {
+      const int r = (y - BRICK_TOP) / BRICK_H;
+      if ((brk_row_mask(w, r) >> c) & 1) base = brk_row_level(r);
+    }
+    const bool ball_row = y >= w.by && y < w.by + BALL, paddle_row = y >= PADDLE_Y && y < PADDLE_Y + PADDLE_H;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int x = x0 + j;
+      const bool on = (ball_row && x >= w.bx && x < w.bx + BALL) || (paddle_row && x >= w.px && x < w.px + PADDLE_W);
+      v[j] = on ? LEVEL : base;
+    }
+    f4[q] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+template <bool STEP>
+__global__ __launch_bounds__(64) void breakout_kernel(int32_t* __restrict__ state, const int64_t* __restrict__ actions,
+                                                      int64_t act_stride, int action_shift, int env_id0, uint32_t seed,
+                                                      int lives, int max_episode_steps, float* __restrict__ frames,
+                                                      int64_t frame_ld, float* __restrict__ rew, float* __restrict__ done,
+                                                      float* __restrict__ reset, int32_t* __restrict__ ep_count,
+                                                      int32_t* __restrict__ ep_rew_sum) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  const uint32_t env = (uint32_t)(env_id0 + e);
+  int32_t* st = state + (int64_t)e * BRK_WORDS;
+  BrkWorld w;
+  uint32_t draws = 0u;
+  int steps = 0, ep_steps = 0, ep_rew = 0;
+  if (STEP) {
+    w.px = st[0]; w.bx = st[1]; w.by = st[2]; w.vx = st[3]; w.vy = st[4]; w.lives = st[5]; w.left = st[6];
+    draws = (uint32_t)st[7]; steps = st[8]; ep_steps = st[9]; ep_rew = st[10];
+#pragma unroll
+    for (int r = 0; r < BRICK_ROWS; ++r) w.rows[r] = st[11 + r] & FULL_ROW;
+    const int64_t a64 = (actions[(int64_t)e * act_stride] + (int64_t)action_shift) % 4;
+    const int a = (int)(a64 < 0 ? a64 + 4 : a64);
+    ++steps;
+    ++ep_steps;
+    // 1. the paddle (0 and 1, ALE's FIRE, leave it where it is)
+    w.px = brk_clamp(w.px + (a == 2 ? PADDLE_SPEED : (a == 3 ? -PADDLE_SPEED : 0)), 0, PADDLE_MAX_X);
+    // 2. the ball, the side walls, the ceiling
+    const int y0 = w.by;
+    int x = w.bx + w.vx, y = y0 + w.vy;
+    if (x < 0) { x = -x; w.vx = -w.vx; }
+    else if (x > BALL_MAX_X) { x = 2 * BALL_MAX_X - x; w.vx = -w.vx; }
+    if (y < 0) { y = -y; w.vy = -w.vy; }
+    // 3. the brick under the leading corner of the new position
+    int r = 0;
+    const int lx = x + (w.vx > 0 ? 1 : 0), ly = y + (w.vy > 0 ? 1 : 0);
+    if (ly >= BRICK_TOP && ly < BRICK_BOTTOM) {
+      const int br = (ly - BRICK_TOP) / BRICK_H, bc = lx / BRICK_W;      // 0 <= lx <= 71: bc in 0..17
+      if ((brk_row_mask(w, br) >> bc) & 1) {
+#pragma unroll
+        for (int k = 0; k < BRICK_ROWS; ++k) w.rows[k] &= ~(k == br ? (1 << bc) : 0);
+        --w.left;
+        r = brk_row_points(br);
+        y = y0;
+        w.vy = -w.vy;
+        if (br < 3) w.vy = w.vy > 0 ? 2 : -2;
+      }
+    }
+    // 4. the paddle
+    if (w.vy > 0 && y0 + 1 < PADDLE_Y && y + 1 >= PADDLE_Y && x >= w.px - 1 && x <= w.px + PADDLE_W - 1) {
+      const int off = x + 1 - w.px;
+      y = PADDLE_Y - BALL;
+      w.vy = -w.vy;
+      w.vx = brk_hit_vx(off, w.vx);
+    }
+    w.bx = x; w.by = y;
+    // 5. a life
+    const bool lost = y > LOST_Y;
+    if (lost) --w.lives;
+    // 6. the end of the episode, or the serve
+    const bool over = w.lives == 0 || w.left == 0 || ep_steps >= max_episode_steps;
+    ep_rew += r;
+    if (over) {
+      if (lane == 0) {
+        if (ep_count != nullptr) atomicAdd(ep_count, 1);
+        if (ep_rew_sum != nullptr) atomicAdd(ep_rew_sum, ep_rew);
+      }
+      ep_rew = 0;
+      brk_new_episode(w, seed, env, lives, draws, ep_steps);
+    } else if (lost) {
+      brk_serve(w, pong_hash(seed, env, draws++));
+    }
+    if (lane == 0) {
+      rew[e] = (float)r;
+      done[e] = over ? 1.0f : 0.0f;
+      reset[e] = over ? 1.0f : 0.0f;
+    }
+  } else {
+    brk_new_episode(w, seed, env, lives, draws, ep_steps);
+  }
+  if (lane < BRK_WORDS) {
+    const int hv = lane == 0 ? w.px : lane == 1 ? w.bx : lane == 2 ? w.by : lane == 3 ? w.vx : lane == 4 ? w.vy
+                 : lane == 5 ? w.lives : lane == 6 ? w.left : lane == 7 ? (int)draws : lane == 8 ? steps
+                 : lane == 9 ? ep_steps : lane == 10 ? ep_rew : lane < 11 + BRICK_ROWS ? brk_row_mask(w, lane - 11) : 0;
+    st[lane] = hv;
+  }
+  brk_write_frame(w, frames + (int64_t)e * frame_ld, lane);
+}
+
+bool brk_world_ok(int lives, int max_episode_steps) {
+  return lives >= 1 && lives <= MAX_LIVES && max_episode_steps >= 1 && max_episode_steps <= MAX_EPISODE_STEPS;
+}
+
+bool brk_frames_ok(const float* frames, int64_t frame_ld) {
+  return frames != nullptr && ((uintptr_t)frames & 15u) == 0 && frame_ld >= BRK_HW && frame_ld % 4 == 0;
+}
+
+}  // namespace
+
+extern "C" size_t a2c_breakout_state_bytes(int lives) {
+  if (lives < 1 || lives > MAX_LIVES) return 0;
+  return sizeof(int32_t) * (size_t)BRK_WORDS;
+}
+
+extern "C" int a2c_breakout_reset(int32_t* state, int B, int env_id0, uint32_t seed, int lives, int max_episode_steps,
+                                  float* frames, int64_t frame_ld, a2c_stream_t stream) {
+  if (B <= 0 || env_id0 < 0 || !brk_world_ok(lives, max_episode_steps)) return A2C_ERR_ARG;
+  if (state == nullptr || !brk_frames_ok(frames, frame_ld)) return A2C_ERR_ARG;
+  hipLaunchKernelGGL(breakout_kernel<false>, dim3(B), dim3(64), 0, a2c_s(stream), state, (const int64_t*)nullptr, (int64_t)0,
+                     0, env_id0, seed, lives, max_episode_steps, frames, frame_ld, (float*)nullptr, (float*)nullptr,
+                     (float*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+extern "C" int a2c_breakout_step(int32_t* state, const int64_t* actions, int64_t act_stride, int action_shift, int B,
+                                 int env_id0, uint32_t seed, int lives, int max_episode_steps, float* frames,
+                                 int64_t frame_ld, float* rew, float* done, float* reset, int32_t* ep_count,
+                                 int32_t* ep_rew_sum, a2c_stream_t stream) {
+  if (B <= 0 || env_id0 < 0 || act_stride < 0 || !brk_world_ok(lives, max_episode_steps)) return A2C_ERR_ARG;
+  if (state == nullptr || actions == nullptr || rew == nullptr || done == nullptr || reset == nullptr ||
+      !brk_frames_ok(frames, frame_ld))
+    return A2C_ERR_ARG;
+  hipLaunchKernelGGL(breakout_kernel<true>, dim3(B), dim3(64), 0, a2c_s(stream), state, actions, act_stride, action_shift,
+                     env_id0, seed, lives, max_episode_steps, frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
