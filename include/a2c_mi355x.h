@@ -948,6 +948,53 @@ int a2c_breakout_step(int32_t *state, const int64_t *actions, int64_t act_stride
                       uint32_t seed, int lives, int max_episode_steps, float *frames, int64_t frame_ld, float *rew,
                       float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, a2c_stream_t stream);
 
+/* ------------------------------------------------------------------ world step + bookkeeping + frame stack in ONE launch
+ * a2c_<world>_step_post(<the arguments of a2c_<world>_step>, post, stream) equals, on the same stream and in this order,
+ *   1. a2c_<world>_step;
+ *   2. the bookkeeping of env step `t` of slots slot0 .. slot0+B-1 (runner.py:212-232): e = (slot0 + b) * T + t,
+ *      rewards[e] = rew[b], dones[e] = done[b] (1 as well when `pong` and rew[b] != 0), done_eff_out[b] = dones[e] (may be
+ *      NULL), deltas[e-1] = rewards[e-1] + gamma * val[b * val_stride] * (1 - dones[e-1]) - val_prev[b] when t > 0 (left to
+ *      right, every operation rounded: what a2c_rollout_record and a2c_rollout_post both compute), val_prev[b] = val[..];
+ *   3. when h != NULL: rows b of h (hdim floats each) with dones[e] != 0 are zeroed, as a2c_rollout_record does;
+ *   4. a2c_frame_stack_push: out[b] = reset[b] ? [0, .., 0, frame] : [prev[b][1:], frame] over C planes of the world's HW
+ *      floats, rows prev_stride / out_stride floats apart --
+ * with every output bit-identical to that sequence.  `frames` may be NULL here: the new frame is then rendered into plane
+ * C - 1 of `out` only (rew / done / reset are still written).  One workgroup of 4 wavefronts per env: every wave recomputes
+ * the (wave-uniform, deterministic) step, wave 0 alone stores the state words, rew / done / reset, the bookkeeping row and
+ * the episode counters, and the C - 1 planes and the rendered frame are split over the 256 lanes as 16-byte loads / stores.
+ * A2C_ERR_ARG without a launch: everything a2c_<world>_step rejects (a NULL `frames` excepted), a NULL post / val /
+ * val_prev / rewards / dones / deltas / prev / out, T < 1, t outside 0 .. T-1, C < 1, prev_stride or out_stride not a
+ * multiple of 4 or below C * HW, out or prev not 16-byte aligned, out == prev, h != NULL with hdim < 1.                   */
+typedef struct {
+  const float *val;            /* value of the state the action was sampled from: val[b * val_stride]               */
+  int64_t val_stride;
+  float *val_prev;             /* B floats: the value of the previous step's state, replaced by val                 */
+  float *rewards, *dones, *deltas;   /* the rollout buffer's rows, indexed (slot0 + b) * T + t                      */
+  int64_t T, t, slot0;
+  float gamma;
+  int pong;                    /* the "Pong" done override: a non-zero reward closes the step                       */
+  const float *prev;           /* state the step was taken from: B rows of C * HW floats, prev_stride floats apart  */
+  int64_t prev_stride;
+  float *out;                  /* the next state, out_stride floats apart                                           */
+  int64_t out_stride;
+  int C;                       /* planes of a state (n_frame_stack)                                                 */
+  float *done_eff_out;         /* B floats or NULL                                                                  */
+  float *h;                    /* recurrent nets: B rows of hdim floats, or NULL                                    */
+  int hdim;
+} a2c_world_post;
+
+int a2c_snake_step_post(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                        uint32_t seed, int G, int unit, int n_foods, float *rew, float *done, float *reset, float *frames,
+                        uint8_t *rgb, int32_t *ep_stats, const a2c_world_post *post, a2c_stream_t stream);
+int a2c_pong_step_post(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                       uint32_t seed, int points_to_win, int max_episode_steps, int opp_skill_num, int opp_skill_den,
+                       float *frames, int64_t frame_ld, float *rew, float *done, float *reset, int32_t *ep_count,
+                       int32_t *ep_rew_sum, const a2c_world_post *post, a2c_stream_t stream);
+int a2c_breakout_step_post(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                           uint32_t seed, int lives, int max_episode_steps, float *frames, int64_t frame_ld, float *rew,
+                           float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_post *post,
+                           a2c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

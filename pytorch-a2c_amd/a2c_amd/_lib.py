@@ -52,8 +52,17 @@ class A3CRolloutArgs(Structure):
                 ("a2_maskbit_rows", P)]
 
 
+class WorldPost(Structure):
+    """a2c_world_post"""
+    _fields_ = [("val", P), ("val_stride", c_int64), ("val_prev", P), ("rewards", P), ("dones", P), ("deltas", P),
+                ("T", c_int64), ("t", c_int64), ("slot0", c_int64), ("gamma", c_float), ("pong", c_int),
+                ("prev", P), ("prev_stride", c_int64), ("out", P), ("out_stride", c_int64), ("C", c_int),
+                ("done_eff_out", P), ("h", P), ("hdim", c_int)]
+
+
 PS = POINTER(A3CStepArgs)
 PR = POINTER(A3CRolloutArgs)
+PW = POINTER(WorldPost)
 
 # name -> (restype, argtypes); one entry per prototype in include/a2c_mi355x.h
 SIGNATURES = {
@@ -193,13 +202,18 @@ SIGNATURES = {
     "a2c_snake_state_bytes": (c_size_t, [c_int, c_int]),
     "a2c_snake_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, c_int, c_int, P, P, P]),
     "a2c_snake_step": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, c_int, P, P, P, P, P, P, P]),
+    "a2c_snake_step_post": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, c_int, P, P, P, P, P, P, PW, P]),
     "a2c_pong_state_bytes": (c_size_t, [c_int]),
     "a2c_pong_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, c_int, c_int, c_int, P, c_int64, P]),
     "a2c_pong_step": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, c_int, c_int, P, c_int64, P, P, P, P,
                               P, P]),
+    "a2c_pong_step_post": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, c_int, c_int, P, c_int64, P, P, P,
+                                   P, P, PW, P]),
     "a2c_breakout_state_bytes": (c_size_t, [c_int]),
     "a2c_breakout_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P]),
     "a2c_breakout_step": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P, P, P]),
+    "a2c_breakout_step_post": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P, P, PW,
+                                       P]),
 }
 
 _lib = None

@@ -313,6 +313,21 @@ class DeviceBreakoutPool:
             raise ValueError("DeviceBreakoutPool.device_step needs actions=(address, stride)")
         return self.step(actions[0], actions[1], env0, B)
 
+    def device_step_post(self, t, env0, B, actions, post, frames=False):
+        """``device_step`` + the bookkeeping of env step ``t`` + the frame stack in ONE launch (a2c_breakout_step_post): ``post`` is
+        an ``ops.world_post`` block.  The new frame goes into plane C - 1 of ``post.out``; ``self.frames`` is written as
+        well only with ``frames=True`` (the Runner does not read it).  -> (rew, done, reset)"""
+        from . import ops
+        if not self.started:
+            raise RuntimeError("DeviceBreakoutPool: reset_all() / start(runner) first")
+        if env0 < 0 or B < 1 or env0 + B > self.B:
+            raise ValueError("DeviceBreakoutPool: env range outside the pool")
+        sl = slice(env0, env0 + B)
+        ops.breakout_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, env0, self.seed, *self.world,
+                               self.frames[sl] if frames else None, self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl],
+                               post, self.ep_stats[0:1], self.ep_stats[1:2])
+        return self.rew[sl], self.done[sl], self.reset_mask[sl]
+
     def episode_stats(self):
         """(episodes finished, sum of their rewards) since the last call; one device read"""
         n, s = (int(v) for v in self.ep_stats.tolist())

@@ -1291,3 +1291,53 @@ def breakout_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed
     check(lib().a2c_breakout_step(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
                                   max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
                                   _p(ep_rew_sum), _st(st)), "a2c_breakout_step")
+
+
+# ---------------------------------------------------------------- world step + bookkeeping + frame stack in one launch
+def world_post(val_ptr, val_stride, val_prev, rewards, dones, deltas, T, t, slot0, gamma, pong, prev_ptr, prev_stride, out_ptr,
+               out_stride, C, done_eff=None, h=None):
+    """the a2c_world_post block of a2c_<world>_step_post: the arguments of rollout_post / rollout_record + frame_stack_push
+    that the world's own step does not already have (``h``: the (B, hdim) hidden rows of a recurrent net, else None)"""
+    for x, name in ((val_prev, "val_prev"), (rewards, "rewards"), (dones, "dones"), (deltas, "deltas"),
+                    (done_eff, "done_eff"), (h, "h")):
+        _chk(x, name)
+    return _lib.WorldPost(val=val_ptr, val_stride=val_stride, val_prev=_p(val_prev), rewards=_p(rewards), dones=_p(dones),
+                          deltas=_p(deltas), T=T, t=t, slot0=slot0, gamma=float(gamma), pong=int(bool(pong)), prev=prev_ptr,
+                          prev_stride=prev_stride, out=out_ptr, out_stride=out_stride, C=C, done_eff_out=_p(done_eff),
+                          h=_p(h), hdim=0 if h is None else h.shape[-1])
+
+
+def _post_ref(post):
+    return ctypes.byref(post) if post is not None else None
+
+
+def snake_step_post(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, G, unit, n_foods, rew, done, reset, frames,
+                    post, rgb=None, ep_stats=None, st=None):
+    """snake_step + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rgb, "rgb", torch.uint8)
+    _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset"); _chk(ep_stats, "ep_stats", torch.int32)
+    check(lib().a2c_snake_step_post(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, G, unit, n_foods,
+                                          _p(rew), _p(done), _p(reset), _p(frames), _p(rgb), _p(ep_stats), _post_ref(post),
+                                          _st(st)), "a2c_snake_step_post")
+
+
+def pong_step_post(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win, max_episode_steps,
+                   opp_skill_num, opp_skill_den, frames, frame_ld, rew, done, reset, post, ep_count=None, ep_rew_sum=None,
+                   st=None):
+    """pong_step + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
+    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    check(lib().a2c_pong_step_post(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
+                                         max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew),
+                                         _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum), _post_ref(post), _st(st)),
+          "a2c_pong_step_post")
+
+
+def breakout_step_post(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames,
+                       frame_ld, rew, done, reset, post, ep_count=None, ep_rew_sum=None, st=None):
+    """breakout_step + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
+    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    check(lib().a2c_breakout_step_post(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
+                                             max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset),
+                                             _p(ep_count), _p(ep_rew_sum), _post_ref(post), _st(st)), "a2c_breakout_step_post")

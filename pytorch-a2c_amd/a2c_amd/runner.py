@@ -25,7 +25,10 @@ Env pools (``env_pool=``):
     single host synchronisation and can be captured into one hipGraph.  ``device_step(t, env0, B)``
     returns (frames (B, HW) fp32, rew, done, reset) device tensors; a pool whose class sets
     ``needs_actions = True`` is called as ``device_step(t, env0, B, actions=(address, stride))`` with
-    the int64 actions the sampler just wrote, and one with ``episode_stats()`` feeds ``rew_q``.
+    the int64 actions the sampler just wrote, and one with ``episode_stats()`` feeds ``rew_q``.  A pool that also has
+    ``device_step_post(t, env0, B, actions, post)`` (the Snake / Pong / Breakout worlds: step, bookkeeping and next state
+    in one launch) is played as ONE hipGraph per slot when ``hyps['rollout_graphs']`` (default true) and the ``actions``
+    buffer is device resident: first rollout eager, second captured, then replayed (``_rollout_block_device``).
 """
 import os
 import queue
@@ -496,6 +499,10 @@ class Runner:
         # opt-in (A2C_SIDE_STREAM=1).
         if not self.device_pool and os.environ.get("A2C_NO_STEP_GRAPHS") != "1":
             return self._rollout_block_segmented(net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h, acts_host_out)
+        if (self.device_pool and hasattr(pool, "device_step_post") and not self.cont and acts_host_out is None
+                and try_key(hyps, "rollout_graphs", True) and os.environ.get("A2C_NO_SLOT_GRAPH") != "1"
+                and os.environ.get("A2C_SIDE_STREAM") != "1"):
+            return self._rollout_block_device(net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h)
         self._fstore_ok = False          # this slot is played by a path that does not keep the frame store: it goes stale
         main = torch.cuda.current_stream()
         side = None
@@ -558,7 +565,7 @@ class Runner:
         ops.rollout_bootstrap(out["vals"].data_ptr(), out["vals"].stride(0), val_prev, rewards, dones, deltas, B, T,
                               slot0, gamma, st)
 
-    def _rollout_block_fused(self, net, slot0, env0, B, hyps, sp, bm, val_prev, acts_host_out, st):
+    def _rollout_block_fused(self, net, slot0, env0, B, hyps, sp, bm, val_prev, acts_host_out, st, ub=None):
         """The same slot with ONE launch per step (a2c_a3c_step): launch t writes state t (frame
         stack of the frame env step t-1 returned), records env step t-1, runs the policy and samples
         action t; launch T records step T-1, leaves the bookmark and bootstraps (runner.py:174-248)."""
@@ -591,7 +598,7 @@ class Runner:
             if t == T:
                 net._step(B, st, bootstrap=1, **kw)
                 break
-            u = self._uniforms(t, B, env0)
+            u = self._uniforms(t, B, env0) if ub is None else ub[t, env0:env0 + B]      # ub: the slot's persistent uniforms
             act = self.act_dev[env0:env0 + B]
             if acts_host_out is None:
                 a_ptr, a_stride = D["actions"].data_ptr() + 8 * (slot0 * T + t), T
@@ -601,6 +608,92 @@ class Runner:
             fr, rew, done, reset = self._env_step(pool, act, a_ptr, a_stride, env0, B, t, slot0, T, shift, acts_host_out, pong)
             for name, x in (("rew", rew), ("done", done), ("reset", reset)):
                 ops._chk(x, name)
+
+    # ------------------------------------------------------------------ device pools: the slot as one hipGraph
+    def _rollout_block_device(self, net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h):
+        """Device env pools with ``device_step_post`` (the Snake / Pong / Breakout worlds): nothing happens on the host between
+        the env steps, so the WHOLE slot -- T steps and the bootstrap -- is ONE hipGraph, like the relay branch of
+        _rollout_block_segmented: the slot's uniforms live in the persistent (T, n_envs) buffer and are filled before the
+        slot, outside the graph; the first rollout of a key runs eagerly (the conv tile tuners measure on eager calls), the
+        second is captured, later ones replay it; a failed capture issues the same launches eagerly, for good.  Called with
+        the stream already capturing (a caller's own graph), the block issues the same launches into that capture and
+        leaves its warm / graph state alone.  ``rollout_graphs=False`` (or A2C_NO_SLOT_GRAPH=1) is _rollout_block's eager
+        loop, which plays the same steps bit for bit."""
+        D, pool = self.datas, self.env_pool
+        T = int(hyps["n_tsteps"])
+        dev = net._dev
+        self._fstore_ok = False          # this slot does not keep the frame store: it goes stale
+        if getattr(self, "_u_buf", None) is None or self._u_buf.shape != (T, self.B):
+            self._u_buf = torch.zeros((T, self.B), dtype=torch.float32, device=dev)
+        ub = self._u_buf
+        if self.uniform_fn is not None:
+            for t in range(T):
+                ub[t, env0:env0 + B].copy_(self.uniform_fn(t, B, env0).reshape(B))
+        else:
+            ub[:, env0:env0 + B] = torch.rand((T, B), device=dev, dtype=torch.float32)
+        fused = h is None and getattr(net, "_step_supported", lambda: False)()
+        stash = self._stash_bufs if fused else None
+        self._stash_used = stash is not None
+
+        def body():
+            st = ops.stream()      # (a capture runs on a stream of its own: not the one the caller was on)
+            if fused:       # a2c_a3c_step records, stacks, runs the policy and samples; the world's plain step feeds it
+                self._rollout_block_fused(net, slot0, env0, B, hyps, sp, bm, val_prev, None, st, ub=ub)
+            else:
+                self._device_slot(net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h, st, ub)
+        if torch.cuda.is_current_stream_capturing():
+            return body()
+        stash_ptrs = None if stash is None else tuple(x.data_ptr() for x in stash if hasattr(x, "data_ptr"))
+        key = (id(net), id(pool), slot0, env0, B, T, float(hyps["gamma"]), "Pong" in hyps["env_type"], fused, stash_ptrs,
+               tuple(D[k].data_ptr() for k in sorted(D) if D[k].is_cuda))
+        cache = self.__dict__.setdefault("_dev_graphs", {})
+        g = cache.get(key)
+        if g is None:
+            cache[key] = "warm"
+            return body()
+        if g == "warm":
+            try:
+                g = torch.cuda.CUDAGraph()
+                with ops.graph_capture(g):
+                    body()
+                cache[key] = g
+            except Exception:      # noqa: BLE001 -- capture not possible here: this key is played eagerly from now on
+                torch.cuda.synchronize()
+                g = cache[key] = False
+        if g:
+            g.replay()
+        else:
+            body()
+
+    def _device_slot(self, net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h, st, ub):
+        """the launches of one slot on a device pool, nets without the one-launch step kernel: per env step the h_states row
+        (recurrent nets), the forward with its sampler, and ONE launch for the world's step, the bookkeeping and the next
+        state (a2c_<world>_step_post); then the bootstrap.  Only enqueues, reads its uniforms from ``ub``: safe to capture."""
+        D, pool = self.datas, self.env_pool
+        T, S, C = int(hyps["n_tsteps"]), self.S, self.C
+        gamma, pong = hyps["gamma"], "Pong" in hyps["env_type"]
+        rewards, dones, deltas = D["rewards"], D["dones"], D["deltas"]
+        ops.copy_rows(bm.data_ptr(), S, sp(0), T * S, B, S, st)          # state 0 = the bookmark (runner.py:190)
+        for t in range(T):
+            if h is not None:                                              # h_states[e] = h (runner.py:201)
+                hd = h.shape[1]
+                ops.copy_rows(h.data_ptr(), hd, D["h_states"].data_ptr() + 4 * (slot0 * T + t) * hd, T * hd, B, hd, st)
+            u = ub[t, env0:env0 + B]
+            a_ptr, a_stride = self._act_row(slot0, T, t)
+            out = self._forward(net, sp(t), T * S, B, env0, st, sampler=(u, a_ptr, a_stride))
+            vals = out["vals"]
+            if not out.get("sampled", False):
+                self._sample(net, out["logits"], u, None, a_ptr, a_stride, B, st)
+            if h is not None and out["h"].data_ptr() != h.data_ptr():      # (the GRU models update h in place)
+                ops.copy_rows(out["h"].data_ptr(), h.shape[1], h.data_ptr(), h.shape[1], B, h.shape[1], st)
+            nxt_ptr, nxt_stride = (sp(t + 1), T * S) if t + 1 < T else (bm.data_ptr(), S)
+            # (done_eff is written for recurrent nets only, as the eager loop's a2c_rollout_record does)
+            post = ops.world_post(vals.data_ptr(), vals.stride(0), val_prev, rewards, dones, deltas, T, t, slot0, gamma, pong,
+                                  sp(t), T * S, nxt_ptr, nxt_stride, C, done_eff=None if h is None else done_eff, h=h)
+            pool.device_step_post(t, env0, B, (a_ptr, a_stride), post)
+        out = self._forward(net, bm.data_ptr(), S, B, env0, st)            # bootstrap (runner.py:236-245)
+        ops.rollout_bootstrap(out["vals"].data_ptr(), out["vals"].stride(0), val_prev, rewards, dones, deltas, B, T, slot0,
+                              gamma, st)
 
     # ------------------------------------------------------------------ host pools: one hipGraph per time step
     def _rollout_block_segmented(self, net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h, acts_host_out):

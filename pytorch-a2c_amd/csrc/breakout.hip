@@ -1,4 +1,4 @@
-// Breakout worlds in device memory: a2c_breakout_reset / a2c_breakout_step (rules: DESIGN.md section 6d; host twin:
+// Breakout worlds in device memory: a2c_breakout_reset / a2c_breakout_step / a2c_breakout_step_post (rules: DESIGN.md section 6d; host twin:
 // a2c_amd/breakout.py).
 //
 // One wavefront per env.  The state of an env is BRK_WORDS int32 words in HBM; a step is a short, loop-free, wave-uniform
@@ -62,10 +62,13 @@ __device__ __forceinline__ void brk_new_episode(BrkWorld& w, uint32_t seed, uint
   brk_serve(w, pong_hash(seed, env, draws++));
 }
 
-// the prepped frame row: BRK_HW floats as float4 stores, the 4 pixels of one brick column in one row each
-__device__ __forceinline__ void brk_write_frame(const BrkWorld& w, float* __restrict__ frame, int lane) {
+// the prepped frame row: BRK_HW floats as float4 stores, the 4 pixels of one brick column in one row each, by `nthreads`
+// lanes, to `frame` and / or `frame2` (either may be null)
+__device__ __forceinline__ void brk_write_frame(const BrkWorld& w, float* __restrict__ frame, float* __restrict__ frame2,
+                                                int tid, int nthreads) {
   float4* f4 = reinterpret_cast<float4*>(frame);
-  for (int q = lane; q < BRK_HW / 4; q += 64) {
+  float4* g4 = reinterpret_cast<float4*>(frame2);
+  for (int q = tid; q < BRK_HW / 4; q += nthreads) {
     const int y = q / BRICK_COLS, c = q - y * BRICK_COLS, x0 = BRICK_W * c;
     float base = 0.0f;
     if (y >= BRICK_TOP && y < BRICK_BOTTOM) {
@@ -80,8 +83,101 @@ __device__ __forceinline__ void brk_write_frame(const BrkWorld& w, float* __rest
       const bool on = (ball_row && x >= w.bx && x < w.bx + BALL) || (paddle_row && x >= w.px && x < w.px + PADDLE_W);
       v[j] = on ? LEVEL : base;
     }
-    f4[q] = make_float4(v[0], v[1], v[2], v[3]);
+    if (f4 != nullptr) f4[q] = make_float4(v[0], v[1], v[2], v[3]);
+    if (g4 != nullptr) g4[q] = make_float4(v[0], v[1], v[2], v[3]);
   }
+}
+
+// the counters of an env beside its world
+struct BrkCount {
+  uint32_t draws;
+  int steps, ep_steps, ep_rew;
+};
+
+__device__ __forceinline__ void brk_load(const int32_t* st, BrkWorld& w, BrkCount& c) {
+  w.px = st[0]; w.bx = st[1]; w.by = st[2]; w.vx = st[3]; w.vy = st[4]; w.lives = st[5]; w.left = st[6];
+  c.draws = (uint32_t)st[7]; c.steps = st[8]; c.ep_steps = st[9]; c.ep_rew = st[10];
+#pragma unroll
+  for (int r = 0; r < BRICK_ROWS; ++r) w.rows[r] = st[11 + r] & FULL_ROW;
+}
+
+__device__ __forceinline__ void brk_store(int32_t* st, const BrkWorld& w, const BrkCount& c, int lane) {
+  if (lane < BRK_WORDS) {
+    const int hv = lane == 0 ? w.px : lane == 1 ? w.bx : lane == 2 ? w.by : lane == 3 ? w.vx : lane == 4 ? w.vy
+                 : lane == 5 ? w.lives : lane == 6 ? w.left : lane == 7 ? (int)c.draws : lane == 8 ? c.steps
+                 : lane == 9 ? c.ep_steps : lane == 10 ? c.ep_rew : lane < 11 + BRICK_ROWS ? brk_row_mask(w, lane - 11) : 0;
+    st[lane] = hv;
+  }
+}
+
+__device__ __forceinline__ int brk_action(const int64_t* actions, int64_t act_stride, int action_shift, int e) {
+  const int64_t a64 = (actions[(int64_t)e * act_stride] + (int64_t)action_shift) % 4;
+  return (int)(a64 < 0 ? a64 + 4 : a64);
+}
+
+// One step of one world, in registers (wave-uniform; no memory access).  -> the reward; over: the episode ended and the
+// world has been restarted; over_rew: the episode's reward, what such a step adds to ep_rew_sum
+__device__ __forceinline__ int brk_advance(BrkWorld& w, BrkCount& c, int a, uint32_t seed, uint32_t env, int lives,
+                                           int max_episode_steps, bool& over, int& over_rew) {
+  ++c.steps;
+  ++c.ep_steps;
+  // 1. the paddle (0 and 1, ALE's FIRE, leave it where it is)
+  w.px = brk_clamp(w.px + (a == 2 ? PADDLE_SPEED : (a == 3 ? -PADDLE_SPEED : 0)), 0, PADDLE_MAX_X);
+  // 2. the ball, the side walls, the ceiling
+  const int y0 = w.by;
+  int x = w.bx + w.vx, y = y0 + w.vy;
+  if (x < 0) { x = -x; w.vx = -w.vx; }
+  else if (x > BALL_MAX_X) { x = 2 * BALL_MAX_X - x; w.vx = -w.vx; }
+  if (y < 0) { y = -y; w.vy = -w.vy; }
+  // 3. the brick under the leading corner of the new position
+  int r = 0;
+  const int lx = x + (w.vx > 0 ? 1 : 0), ly = y + (w.vy > 0 ? 1 : 0);
+  if (ly >= BRICK_TOP && ly < BRICK_BOTTOM) {
+    const int br = (ly - BRICK_TOP) / BRICK_H, bc = lx / BRICK_W;      // 0 <= lx <= 71: bc in 0..17
+    if ((brk_row_mask(w, br) >> bc) & 1) {
+#pragma unroll
+      for (int k = 0; k < BRICK_ROWS; ++k) w.rows[k] &= ~(k == br ? (1 << bc) : 0);
+      --w.left;
+      r = brk_row_points(br);
+      y = y0;
+      w.vy = -w.vy;
+      if (br < 3) w.vy = w.vy > 0 ? 2 : -2;
+    }
+  }
+  // 4. the paddle
+  if (w.vy > 0 && y0 + 1 < PADDLE_Y && y + 1 >= PADDLE_Y && x >= w.px - 1 && x <= w.px + PADDLE_W - 1) {
+    const int off = x + 1 - w.px;
+    y = PADDLE_Y - BALL;
+    w.vy = -w.vy;
+    w.vx = brk_hit_vx(off, w.vx);
+  }
+  w.bx = x; w.by = y;
+  // 5. a life
+  const bool lost = y > LOST_Y;
+  if (lost) --w.lives;
+  // 6. the end of the episode, or the serve
+  over = w.lives == 0 || w.left == 0 || c.ep_steps >= max_episode_steps;
+  c.ep_rew += r;
+  over_rew = c.ep_rew;
+  if (over) {
+    c.ep_rew = 0;
+    brk_new_episode(w, seed, env, lives, c.draws, c.ep_steps);
+  } else if (lost) {
+    brk_serve(w, pong_hash(seed, env, c.draws++));
+  }
+  return r;
+}
+
+// lane 0 of the wave that owns the env: what a step leaves beside the state words
+__device__ __forceinline__ void brk_publish(int e, int r, bool over, int over_rew, float* rew, float* done, float* reset,
+                                            int32_t* ep_count, int32_t* ep_rew_sum) {
+  if (over) {
+    if (ep_count != nullptr) atomicAdd(ep_count, 1);
+    if (ep_rew_sum != nullptr) atomicAdd(ep_rew_sum, over_rew);
+  }
+  rew[e] = (float)r;
+  done[e] = over ? 1.0f : 0.0f;
+  reset[e] = over ? 1.0f : 0.0f;
 }
 
 template <bool STEP>
@@ -95,79 +191,47 @@ __global__ __launch_bounds__(64) void breakout_kernel(int32_t* __restrict__ stat
   const uint32_t env = (uint32_t)(env_id0 + e);
   int32_t* st = state + (int64_t)e * BRK_WORDS;
   BrkWorld w;
-  uint32_t draws = 0u;
-  int steps = 0, ep_steps = 0, ep_rew = 0;
+  BrkCount c = {0u, 0, 0, 0};
   if (STEP) {
-    w.px = st[0]; w.bx = st[1]; w.by = st[2]; w.vx = st[3]; w.vy = st[4]; w.lives = st[5]; w.left = st[6];
-    draws = (uint32_t)st[7]; steps = st[8]; ep_steps = st[9]; ep_rew = st[10];
-#pragma unroll
-    for (int r = 0; r < BRICK_ROWS; ++r) w.rows[r] = st[11 + r] & FULL_ROW;
-    const int64_t a64 = (actions[(int64_t)e * act_stride] + (int64_t)action_shift) % 4;
-    const int a = (int)(a64 < 0 ? a64 + 4 : a64);
-    ++steps;
-    ++ep_steps;
-    // 1. the paddle (0 and 1, ALE's FIRE, leave it where it is)
-    w.px = brk_clamp(w.px + (a == 2 ? PADDLE_SPEED : (a == 3 ? -PADDLE_SPEED : 0)), 0, PADDLE_MAX_X);
-    // 2. the ball, the side walls, the ceiling
-    const int y0 = w.by;
-    int x = w.bx + w.vx, y = y0 + w.vy;
-    if (x < 0) { x = -x; w.vx = -w.vx; }
-    else if (x > BALL_MAX_X) { x = 2 * BALL_MAX_X - x; w.vx = -w.vx; }
-    if (y < 0) { y = -y; w.vy = -w.vy; }
-    // 3. the brick under the leading corner of the new position
-    int r = 0;
-    const int lx = x + (w.vx > 0 ? 1 : 0), ly = y + (w.vy > 0 ? 1 : 0);
-    if (ly >= BRICK_TOP && ly < BRICK_BOTTOM) {
-      const int br = (ly - BRICK_TOP) / BRICK_H, bc = lx / BRICK_W;      // 0 <= lx <= 71: bc in 0..17
-      if ((brk_row_mask(w, br) >> bc) & 1) {
-#pragma unroll
-        for (int k = 0; k < BRICK_ROWS; ++k) w.rows[k] &= ~(k == br ? (1 << bc) : 0);
-        --w.left;
-        r = brk_row_points(br);
-        y = y0;
-        w.vy = -w.vy;
-        if (br < 3) w.vy = w.vy > 0 ? 2 : -2;
-      }
-    }
-    // 4. the paddle
-    if (w.vy > 0 && y0 + 1 < PADDLE_Y && y + 1 >= PADDLE_Y && x >= w.px - 1 && x <= w.px + PADDLE_W - 1) {
-      const int off = x + 1 - w.px;
-      y = PADDLE_Y - BALL;
-      w.vy = -w.vy;
-      w.vx = brk_hit_vx(off, w.vx);
-    }
-    w.bx = x; w.by = y;
-    // 5. a life
-    const bool lost = y > LOST_Y;
-    if (lost) --w.lives;
-    // 6. the end of the episode, or the serve
-    const bool over = w.lives == 0 || w.left == 0 || ep_steps >= max_episode_steps;
-    ep_rew += r;
-    if (over) {
-      if (lane == 0) {
-        if (ep_count != nullptr) atomicAdd(ep_count, 1);
-        if (ep_rew_sum != nullptr) atomicAdd(ep_rew_sum, ep_rew);
-      }
-      ep_rew = 0;
-      brk_new_episode(w, seed, env, lives, draws, ep_steps);
-    } else if (lost) {
-      brk_serve(w, pong_hash(seed, env, draws++));
-    }
-    if (lane == 0) {
-      rew[e] = (float)r;
-      done[e] = over ? 1.0f : 0.0f;
-      reset[e] = over ? 1.0f : 0.0f;
-    }
+    brk_load(st, w, c);
+    bool over;
+    int over_rew;
+    const int r = brk_advance(w, c, brk_action(actions, act_stride, action_shift, e), seed, env, lives, max_episode_steps,
+                              over, over_rew);
+    if (lane == 0) brk_publish(e, r, over, over_rew, rew, done, reset, ep_count, ep_rew_sum);
   } else {
-    brk_new_episode(w, seed, env, lives, draws, ep_steps);
+    brk_new_episode(w, seed, env, lives, c.draws, c.ep_steps);
   }
-  if (lane < BRK_WORDS) {
-    const int hv = lane == 0 ? w.px : lane == 1 ? w.bx : lane == 2 ? w.by : lane == 3 ? w.vx : lane == 4 ? w.vy
-                 : lane == 5 ? w.lives : lane == 6 ? w.left : lane == 7 ? (int)draws : lane == 8 ? steps
-                 : lane == 9 ? ep_steps : lane == 10 ? ep_rew : lane < 11 + BRICK_ROWS ? brk_row_mask(w, lane - 11) : 0;
-    st[lane] = hv;
+  brk_store(st, w, c, lane);
+  brk_write_frame(w, frames + (int64_t)e * frame_ld, nullptr, lane, 64);
+}
+
+// a2c_breakout_step_post: breakout_kernel<true> + the step's bookkeeping + the frame stack, WORLD_POST_WAVES waves per env.
+// Every wave loads the state words and computes the same step; the barrier keeps wave 0's stores behind every wave's loads.
+__global__ __launch_bounds__(WORLD_POST_THREADS) void breakout_post_kernel(
+    int32_t* __restrict__ state, const int64_t* __restrict__ actions, int64_t act_stride, int action_shift, int env_id0,
+    uint32_t seed, int lives, int max_episode_steps, float* __restrict__ frames, int64_t frame_ld, float* __restrict__ rew,
+    float* __restrict__ done, float* __restrict__ reset, int32_t* __restrict__ ep_count, int32_t* __restrict__ ep_rew_sum,
+    const a2c_world_post post) {
+  const int e = blockIdx.x, tid = threadIdx.x;
+  const uint32_t env = (uint32_t)(env_id0 + e);
+  int32_t* st = state + (int64_t)e * BRK_WORDS;
+  BrkWorld w;
+  BrkCount c;
+  brk_load(st, w, c);
+  const int a = brk_action(actions, act_stride, action_shift, e);
+  __syncthreads();
+  bool over;
+  int over_rew;
+  const int r = brk_advance(w, c, a, seed, env, lives, max_episode_steps, over, over_rew);
+  const float d = world_post_done(post, (float)r, over ? 1.0f : 0.0f);
+  if (tid == 0) {
+    brk_publish(e, r, over, over_rew, rew, done, reset, ep_count, ep_rew_sum);
+    world_post_book(post, e, (float)r, d);
   }
-  brk_write_frame(w, frames + (int64_t)e * frame_ld, lane);
+  if (tid < 64) brk_store(st, w, c, tid);
+  float* top = world_post_planes(post, e, d, over, BRK_HW, tid);
+  brk_write_frame(w, top, frames == nullptr ? nullptr : frames + (int64_t)e * frame_ld, tid, WORLD_POST_THREADS);
 }
 
 bool brk_world_ok(int lives, int max_episode_steps) {
@@ -206,6 +270,21 @@ extern "C" int a2c_breakout_step(int32_t* state, const int64_t* actions, int64_t
     return A2C_ERR_ARG;
   hipLaunchKernelGGL(breakout_kernel<true>, dim3(B), dim3(64), 0, a2c_s(stream), state, actions, act_stride, action_shift,
                      env_id0, seed, lives, max_episode_steps, frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+extern "C" int a2c_breakout_step_post(int32_t* state, const int64_t* actions, int64_t act_stride, int action_shift, int B,
+                                      int env_id0, uint32_t seed, int lives, int max_episode_steps, float* frames,
+                                      int64_t frame_ld, float* rew, float* done, float* reset, int32_t* ep_count,
+                                      int32_t* ep_rew_sum, const a2c_world_post* post, a2c_stream_t stream) {
+  if (B <= 0 || env_id0 < 0 || act_stride < 0 || !brk_world_ok(lives, max_episode_steps)) return A2C_ERR_ARG;
+  if (state == nullptr || actions == nullptr || rew == nullptr || done == nullptr || reset == nullptr ||
+      (frames != nullptr && !brk_frames_ok(frames, frame_ld)) || !a2c_world_post_ok(post, BRK_HW))
+    return A2C_ERR_ARG;
+  hipLaunchKernelGGL(breakout_post_kernel, dim3(B), dim3(WORLD_POST_THREADS), 0, a2c_s(stream), state, actions, act_stride,
+                     action_shift, env_id0, seed, lives, max_episode_steps, frames, frame_ld, rew, done, reset, ep_count,
+                     ep_rew_sum, *post);
   A2C_CHECK_LAUNCH();
   return A2C_OK;
 }

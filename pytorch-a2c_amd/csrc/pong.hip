@@ -1,4 +1,4 @@
-// Pong worlds in device memory: a2c_pong_reset / a2c_pong_step (rules: DESIGN.md section 6c; host twin: a2c_amd/pong.py).
+// Pong worlds in device memory: a2c_pong_reset / a2c_pong_step / a2c_pong_step_post (rules: DESIGN.md section 6c; host twin: a2c_amd/pong.py).
 //
 // One wavefront per env.  The state of an env is PONG_WORDS int32 words in HBM; a step is a short, loop-free, wave-uniform
 // integer computation (every lane computes the same values from the same words), after which lanes 0..PONG_WORDS-1 store
@@ -47,10 +47,13 @@ __device__ __forceinline__ bool pong_in(int x, int y, int rx, int ry, int rw, in
   return x >= rx && x < rx + rw && y >= ry && y < ry + rh;
 }
 
-// the prepped frame row: PONG_HW floats as float4 stores, 4 pixels of one row each (PW % 4 == 0)
-__device__ __forceinline__ void pong_write_frame(const PongWorld& w, float* __restrict__ frame, int lane) {
+// the prepped frame row: PONG_HW floats as float4 stores, 4 pixels of one row each (PW % 4 == 0), by `nthreads` lanes, to
+// `frame` and / or `frame2` (either may be null)
+__device__ __forceinline__ void pong_write_frame(const PongWorld& w, float* __restrict__ frame, float* __restrict__ frame2,
+                                                 int tid, int nthreads) {
   float4* f4 = reinterpret_cast<float4*>(frame);
-  for (int q = lane; q < PONG_HW / 4; q += 64) {
+  float4* g4 = reinterpret_cast<float4*>(frame2);
+  for (int q = tid; q < PONG_HW / 4; q += nthreads) {
     const int y = q / (PW / 4), x0 = 4 * (q - y * (PW / 4));
     float v[4];
 #pragma unroll
@@ -60,8 +63,90 @@ __device__ __forceinline__ void pong_write_frame(const PongWorld& w, float* __re
                       pong_in(x, y, w.bx, w.by, BALL, BALL);
       v[j] = on ? 1.0f : 0.0f;
     }
-    f4[q] = make_float4(v[0], v[1], v[2], v[3]);
+    if (f4 != nullptr) f4[q] = make_float4(v[0], v[1], v[2], v[3]);
+    if (g4 != nullptr) g4[q] = make_float4(v[0], v[1], v[2], v[3]);
   }
+}
+
+// the counters of an env beside its world
+struct PongCount {
+  uint32_t draws;
+  int steps, ep_steps, ep_rew;
+};
+
+__device__ __forceinline__ void pong_load(const int32_t* st, PongWorld& w, PongCount& c) {
+  w.ay = st[0]; w.oy = st[1]; w.bx = st[2]; w.by = st[3]; w.vx = st[4]; w.vy = st[5]; w.sa = st[6]; w.so = st[7];
+  c.draws = (uint32_t)st[8]; c.steps = st[9]; c.ep_steps = st[10]; c.ep_rew = st[11];
+}
+
+__device__ __forceinline__ void pong_store(int32_t* st, const PongWorld& w, const PongCount& c, int lane) {
+  if (lane < PONG_WORDS) {
+    const int hv = lane == 0 ? w.ay : lane == 1 ? w.oy : lane == 2 ? w.bx : lane == 3 ? w.by : lane == 4 ? w.vx
+                 : lane == 5 ? w.vy : lane == 6 ? w.sa : lane == 7 ? w.so : lane == 8 ? (int)c.draws : lane == 9 ? c.steps
+                 : lane == 10 ? c.ep_steps : lane == 11 ? c.ep_rew : 0;
+    st[lane] = hv;
+  }
+}
+
+// One step of one world, in registers (wave-uniform; no memory access).  -> the reward; over: the episode ended and the
+// world has been restarted; closed: the `done` of a "Pong" env type (runner.py:212-214); closed_rew: the reward since the
+// last done, what a closed step adds to ep_rew_sum
+__device__ __forceinline__ int pong_advance(PongWorld& w, PongCount& c, int a, uint32_t seed, uint32_t env, int points_to_win,
+                                            int max_episode_steps, int skill_num, int skill_den, bool& over, bool& closed,
+                                            int& closed_rew) {
+  ++c.steps;
+  ++c.ep_steps;
+  // 1. the agent's paddle
+  w.ay = pong_clamp(w.ay + (a == 1 ? -2 : (a == 2 ? 2 : 0)), 0, PADDLE_MAX_Y);
+  // 2. the opponent's paddle: towards the ball's centre, on the steps the draw allows
+  if ((int)(pong_hash(seed, env, c.draws++) % (uint32_t)skill_den) < skill_num) {
+    const int cb = w.by + 1, cp = w.oy + PADDLE_H / 2;
+    w.oy = pong_clamp(w.oy + (cb < cp ? -1 : (cb > cp ? 1 : 0)), 0, PADDLE_MAX_Y);
+  }
+  // 3. the ball, the walls
+  const int x0 = w.bx;
+  int x = x0 + w.vx, y = w.by + w.vy;
+  if (y < 0) { y = -y; w.vy = -w.vy; }
+  else if (y > BALL_MAX_Y) { y = 2 * BALL_MAX_Y - y; w.vy = -w.vy; }
+  // 4. the paddles
+  if (w.vx > 0 && x0 + 1 < AGENT_X && x + 1 >= AGENT_X && y >= w.ay - 1 && y <= w.ay + PADDLE_H - 1) {
+    const int off = y + 1 - w.ay;
+    x = AGENT_X - BALL; w.vx = -pong_hit_speed(off); w.vy = pong_hit_vy(off);
+  } else if (w.vx < 0 && x0 > OPP_X + 1 && x <= OPP_X + 1 && y >= w.oy - 1 && y <= w.oy + PADDLE_H - 1) {
+    const int off = y + 1 - w.oy;
+    x = OPP_X + PADDLE_W; w.vx = pong_hit_speed(off); w.vy = pong_hit_vy(off);
+  }
+  w.bx = x; w.by = y;
+  // 5. a point
+  int r = 0;
+  if (x >= MISS_RIGHT) { r = -1; ++w.so; }
+  else if (x <= MISS_LEFT) { r = 1; ++w.sa; }
+  // 6. the end of the episode, or the serve
+  over = w.sa >= points_to_win || w.so >= points_to_win || c.ep_steps >= max_episode_steps;
+  closed = over || r != 0;
+  c.ep_rew += r;
+  closed_rew = c.ep_rew;
+  if (closed) c.ep_rew = 0;
+  if (over) pong_new_episode(w, seed, env, c.draws, c.ep_steps);
+  else if (r != 0) pong_serve(w, pong_hash(seed, env, c.draws++), r < 0);
+  return r;
+}
+
+__device__ __forceinline__ int pong_action(const int64_t* actions, int64_t act_stride, int action_shift, int e) {
+  const int64_t a64 = (actions[(int64_t)e * act_stride] + (int64_t)action_shift) % 3;
+  return (int)(a64 < 0 ? a64 + 3 : a64);
+}
+
+// lane 0 of the wave that owns the env: what a step leaves beside the state words
+__device__ __forceinline__ void pong_publish(int e, int r, bool over, bool closed, int closed_rew, float* rew, float* done,
+                                             float* reset, int32_t* ep_count, int32_t* ep_rew_sum) {
+  if (closed) {
+    if (ep_count != nullptr) atomicAdd(ep_count, 1);
+    if (ep_rew_sum != nullptr) atomicAdd(ep_rew_sum, closed_rew);
+  }
+  rew[e] = (float)r;
+  done[e] = closed ? 1.0f : 0.0f;
+  reset[e] = over ? 1.0f : 0.0f;
 }
 
 template <bool STEP>
@@ -75,68 +160,48 @@ __global__ __launch_bounds__(64) void pong_kernel(int32_t* __restrict__ state, c
   const uint32_t env = (uint32_t)(env_id0 + e);
   int32_t* st = state + (int64_t)e * PONG_WORDS;
   PongWorld w;
-  uint32_t draws = 0u;
-  int steps = 0, ep_steps = 0, ep_rew = 0;
+  PongCount c = {0u, 0, 0, 0};
   if (STEP) {
-    w.ay = st[0]; w.oy = st[1]; w.bx = st[2]; w.by = st[3]; w.vx = st[4]; w.vy = st[5]; w.sa = st[6]; w.so = st[7];
-    draws = (uint32_t)st[8]; steps = st[9]; ep_steps = st[10]; ep_rew = st[11];
-    const int64_t a64 = (actions[(int64_t)e * act_stride] + (int64_t)action_shift) % 3;
-    const int a = (int)(a64 < 0 ? a64 + 3 : a64);
-    ++steps;
-    ++ep_steps;
-    // 1. the agent's paddle
-    w.ay = pong_clamp(w.ay + (a == 1 ? -2 : (a == 2 ? 2 : 0)), 0, PADDLE_MAX_Y);
-    // 2. the opponent's paddle: towards the ball's centre, on the steps the draw allows
-    if ((int)(pong_hash(seed, env, draws++) % (uint32_t)skill_den) < skill_num) {
-      const int cb = w.by + 1, cp = w.oy + PADDLE_H / 2;
-      w.oy = pong_clamp(w.oy + (cb < cp ? -1 : (cb > cp ? 1 : 0)), 0, PADDLE_MAX_Y);
-    }
-    // 3. the ball, the walls
-    const int x0 = w.bx;
-    int x = x0 + w.vx, y = w.by + w.vy;
-    if (y < 0) { y = -y; w.vy = -w.vy; }
-    else if (y > BALL_MAX_Y) { y = 2 * BALL_MAX_Y - y; w.vy = -w.vy; }
-    // 4. the paddles
-    if (w.vx > 0 && x0 + 1 < AGENT_X && x + 1 >= AGENT_X && y >= w.ay - 1 && y <= w.ay + PADDLE_H - 1) {
-      const int off = y + 1 - w.ay;
-      x = AGENT_X - BALL; w.vx = -pong_hit_speed(off); w.vy = pong_hit_vy(off);
-    } else if (w.vx < 0 && x0 > OPP_X + 1 && x <= OPP_X + 1 && y >= w.oy - 1 && y <= w.oy + PADDLE_H - 1) {
-      const int off = y + 1 - w.oy;
-      x = OPP_X + PADDLE_W; w.vx = pong_hit_speed(off); w.vy = pong_hit_vy(off);
-    }
-    w.bx = x; w.by = y;
-    // 5. a point
-    int r = 0;
-    if (x >= MISS_RIGHT) { r = -1; ++w.so; }
-    else if (x <= MISS_LEFT) { r = 1; ++w.sa; }
-    // 6. the end of the episode, or the serve
-    const bool over = w.sa >= points_to_win || w.so >= points_to_win || ep_steps >= max_episode_steps;
-    const bool closed = over || r != 0;          // the `done` of a "Pong" env type (runner.py:212-214)
-    ep_rew += r;
-    if (closed) {
-      if (lane == 0) {
-        if (ep_count != nullptr) atomicAdd(ep_count, 1);
-        if (ep_rew_sum != nullptr) atomicAdd(ep_rew_sum, ep_rew);
-      }
-      ep_rew = 0;
-    }
-    if (over) pong_new_episode(w, seed, env, draws, ep_steps);
-    else if (r != 0) pong_serve(w, pong_hash(seed, env, draws++), r < 0);
-    if (lane == 0) {
-      rew[e] = (float)r;
-      done[e] = closed ? 1.0f : 0.0f;
-      reset[e] = over ? 1.0f : 0.0f;
-    }
+    pong_load(st, w, c);
+    bool over, closed;
+    int closed_rew;
+    const int r = pong_advance(w, c, pong_action(actions, act_stride, action_shift, e), seed, env, points_to_win,
+                               max_episode_steps, skill_num, skill_den, over, closed, closed_rew);
+    if (lane == 0) pong_publish(e, r, over, closed, closed_rew, rew, done, reset, ep_count, ep_rew_sum);
   } else {
-    pong_new_episode(w, seed, env, draws, ep_steps);
+    pong_new_episode(w, seed, env, c.draws, c.ep_steps);
   }
-  if (lane < PONG_WORDS) {
-    const int hv = lane == 0 ? w.ay : lane == 1 ? w.oy : lane == 2 ? w.bx : lane == 3 ? w.by : lane == 4 ? w.vx
-                 : lane == 5 ? w.vy : lane == 6 ? w.sa : lane == 7 ? w.so : lane == 8 ? (int)draws : lane == 9 ? steps
-                 : lane == 10 ? ep_steps : lane == 11 ? ep_rew : 0;
-    st[lane] = hv;
+  pong_store(st, w, c, lane);
+  pong_write_frame(w, frames + (int64_t)e * frame_ld, nullptr, lane, 64);
+}
+
+// a2c_pong_step_post: pong_kernel<true> + the step's bookkeeping + the frame stack, WORLD_POST_WAVES waves per env.  Every
+// wave loads the state words and computes the same step; the barrier keeps wave 0's stores behind every wave's loads.
+__global__ __launch_bounds__(WORLD_POST_THREADS) void pong_post_kernel(
+    int32_t* __restrict__ state, const int64_t* __restrict__ actions, int64_t act_stride, int action_shift, int env_id0,
+    uint32_t seed, int points_to_win, int max_episode_steps, int skill_num, int skill_den, float* __restrict__ frames,
+    int64_t frame_ld, float* __restrict__ rew, float* __restrict__ done, float* __restrict__ reset,
+    int32_t* __restrict__ ep_count, int32_t* __restrict__ ep_rew_sum, const a2c_world_post post) {
+  const int e = blockIdx.x, tid = threadIdx.x;
+  const uint32_t env = (uint32_t)(env_id0 + e);
+  int32_t* st = state + (int64_t)e * PONG_WORDS;
+  PongWorld w;
+  PongCount c;
+  pong_load(st, w, c);
+  const int a = pong_action(actions, act_stride, action_shift, e);
+  __syncthreads();
+  bool over, closed;
+  int closed_rew;
+  const int r = pong_advance(w, c, a, seed, env, points_to_win, max_episode_steps, skill_num, skill_den, over, closed,
+                             closed_rew);
+  const float d = world_post_done(post, (float)r, closed ? 1.0f : 0.0f);
+  if (tid == 0) {
+    pong_publish(e, r, over, closed, closed_rew, rew, done, reset, ep_count, ep_rew_sum);
+    world_post_book(post, e, (float)r, d);
   }
-  pong_write_frame(w, frames + (int64_t)e * frame_ld, lane);
+  if (tid < 64) pong_store(st, w, c, tid);
+  float* top = world_post_planes(post, e, d, over, PONG_HW, tid);
+  pong_write_frame(w, top, frames == nullptr ? nullptr : frames + (int64_t)e * frame_ld, tid, WORLD_POST_THREADS);
 }
 
 bool pong_world_ok(int points_to_win, int max_episode_steps, int skill_num, int skill_den) {
@@ -179,6 +244,22 @@ extern "C" int a2c_pong_step(int32_t* state, const int64_t* actions, int64_t act
   hipLaunchKernelGGL(pong_kernel<true>, dim3(B), dim3(64), 0, a2c_s(stream), state, actions, act_stride, action_shift, env_id0,
                      seed, points_to_win, max_episode_steps, opp_skill_num, opp_skill_den, frames, frame_ld, rew, done, reset,
                      ep_count, ep_rew_sum);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+extern "C" int a2c_pong_step_post(int32_t* state, const int64_t* actions, int64_t act_stride, int action_shift, int B,
+                                  int env_id0, uint32_t seed, int points_to_win, int max_episode_steps, int opp_skill_num,
+                                  int opp_skill_den, float* frames, int64_t frame_ld, float* rew, float* done, float* reset,
+                                  int32_t* ep_count, int32_t* ep_rew_sum, const a2c_world_post* post, a2c_stream_t stream) {
+  if (B <= 0 || env_id0 < 0 || act_stride < 0 || !pong_world_ok(points_to_win, max_episode_steps, opp_skill_num, opp_skill_den))
+    return A2C_ERR_ARG;
+  if (state == nullptr || actions == nullptr || rew == nullptr || done == nullptr || reset == nullptr ||
+      (frames != nullptr && !pong_frames_ok(frames, frame_ld)) || !a2c_world_post_ok(post, PONG_HW))
+    return A2C_ERR_ARG;
+  hipLaunchKernelGGL(pong_post_kernel, dim3(B), dim3(WORLD_POST_THREADS), 0, a2c_s(stream), state, actions, act_stride,
+                     action_shift, env_id0, seed, points_to_win, max_episode_steps, opp_skill_num, opp_skill_den, frames,
+                     frame_ld, rew, done, reset, ep_count, ep_rew_sum, *post);
   A2C_CHECK_LAUNCH();
   return A2C_OK;
 }

@@ -97,12 +97,7 @@ __global__ __launch_bounds__(256) void record_kernel(const float* __restrict__ r
   dones[e] = d;
   if (done_eff_out) done_eff_out[b] = d;
   const float v = val[b * vstride];
-  if (t > 0) {
-    // delta = prev_rew + gamma*val*(1-prev_done) - prev_val, left to right, each op rounded
-    const float pr = rewards[e - 1], pd = dones[e - 1];
-    const float gv = __fmul_rn(gamma, v);
-    deltas[e - 1] = __fsub_rn(__fadd_rn(pr, __fmul_rn(gv, __fsub_rn(1.f, pd))), val_prev[b]);
-  }
+  if (t > 0) deltas[e - 1] = a2c_td_delta(rewards[e - 1], dones[e - 1], gamma, v, val_prev[b]);
   val_prev[b] = v;
 }
 
@@ -144,11 +139,7 @@ __global__ __launch_bounds__(256) void post_kernel(const float* __restrict__ rew
     dones[e] = d;
     if (done_eff_out) done_eff_out[b] = d;
     const float v = val[b * vstride];
-    if (t > 0) {
-      const float pr = rewards[e - 1], pd = dones[e - 1];
-      const float gv = gamma * v;
-      deltas[e - 1] = (pr + gv * (1.f - pd)) - val_prev[b];
-    }
+    if (t > 0) deltas[e - 1] = a2c_td_delta(rewards[e - 1], dones[e - 1], gamma, v, val_prev[b]);
     if (nv_carry) {      // single-frame store: how many planes of the NEXT state are real frames (utils.py:37-42: a reset
       const int nv = done[b] != 0.f ? 1 : min(nv_carry[b] + 1, 4);      // leaves the reset frame behind zeros)
       nv_carry[b] = nv;

@@ -1,4 +1,4 @@
-// Snake worlds in device memory: a2c_snake_reset / a2c_snake_step (rules: DESIGN.md "Snake"; host twin: a2c_amd/snake.py).
+// Snake worlds in device memory: a2c_snake_reset / a2c_snake_step / a2c_snake_step_post (rules: DESIGN.md "Snake"; host twin: a2c_amd/snake.py).
 //
 // One wavefront per env.  The G x G grid is a time-to-live map (0 free, -1 food, n > 0: occupied for n more steps, the
 // head holds the length), kept in HBM between launches and worked on in LDS: a step is one pass over the cells, a food
@@ -65,23 +65,27 @@ __device__ __forceinline__ float snake_prep_value(int v, int len) {
   return v == 0 ? 0.0f : (v < 0 ? 0.33f : (v == len ? 1.5f : 1.0f));
 }
 
-// frame row (HW floats, HW % 4 == 0) as float4 stores; raw RGB (3*HW bytes) as 4-byte words
+// frame row (HW floats, HW % 4 == 0) as float4 stores to `frame` and / or `frame2` (either may be null); raw RGB (3*HW
+// bytes) as 4-byte words; by `nthreads` lanes
 __device__ __forceinline__ void snake_write_frames(const int* s, int G, int unit, int len, float* __restrict__ frame,
-                                                   uint8_t* __restrict__ rgb, int lane) {
+                                                   float* __restrict__ frame2, uint8_t* __restrict__ rgb, int tid,
+                                                   int nthreads) {
   const int W = G * unit, HW = W * W;
   float4* f4 = reinterpret_cast<float4*>(frame);
-  for (int q = lane; q < HW / 4; q += 64) {
+  float4* g4 = reinterpret_cast<float4*>(frame2);
+  for (int q = tid; q < HW / 4; q += nthreads) {
     float v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int p = 4 * q + j;
       v[j] = snake_prep_value(s[((p / W) / unit) * G + (p % W) / unit], len);
     }
-    f4[q] = make_float4(v[0], v[1], v[2], v[3]);
+    if (f4 != nullptr) f4[q] = make_float4(v[0], v[1], v[2], v[3]);
+    if (g4 != nullptr) g4[q] = make_float4(v[0], v[1], v[2], v[3]);
   }
   if (rgb != nullptr) {
     uint32_t* w4 = reinterpret_cast<uint32_t*>(rgb);
-    for (int q = lane; q < 3 * HW / 4; q += 64) {
+    for (int q = tid; q < 3 * HW / 4; q += nthreads) {
       uint32_t word = 0u;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -96,6 +100,85 @@ __device__ __forceinline__ void snake_write_frames(const int* s, int G, int unit
   }
 }
 
+// the header words of an env
+struct SnakeHead {
+  int hr, hc, len;
+  uint32_t draws;
+  int steps, ep_rew;
+};
+
+__device__ __forceinline__ void snake_load_head(const int32_t* st, SnakeHead& h) {
+  h.hr = st[0]; h.hc = st[1]; h.len = st[2];
+  h.draws = (uint32_t)st[3];
+  h.steps = st[4]; h.ep_rew = st[5];
+}
+
+// One step of one world by one wave: the cells come from `st` into this wave's LDS copy `s`, the header is in registers.
+// Every wave of the workgroup must call it (it holds barriers), each with an `s` of its own.  -> the reward; over: the
+// episode ended and the world has been restarted; over_rew: the episode's reward, what such a step adds to ep_stats[1]
+__device__ __forceinline__ float snake_advance(int* s, const int32_t* st, SnakeHead& h, int a, uint32_t seed, uint32_t env,
+                                               int G, int NC, int n_foods, int lane, bool& over, int& over_rew) {
+  for (int i = lane; i < NC; i += 64) s[i] = st[SNAKE_HDR + i];
+  __syncthreads();
+  const int nr = h.hr + (a == 0 ? -1 : (a == 2 ? 1 : 0)), nc = h.hc + (a == 1 ? 1 : (a == 3 ? -1 : 0));
+  const bool inside = nr >= 0 && nr < G && nc >= 0 && nc < G;
+  const int v = inside ? s[nr * G + nc] : 1;
+  __syncthreads();
+  float r = 0.0f;
+  over = false;
+  ++h.steps;
+  if (v > 0) {                       // wall, or a body cell (neck and tail cell included)
+    r = -1.0f;
+    over = true;
+  } else if (v < 0) {                // food: grow by one, nothing is vacated
+    r = 1.0f;
+    ++h.len;
+    h.hr = nr; h.hc = nc;
+    if (lane == 0) s[nr * G + nc] = h.len;
+    __syncthreads();
+    const int n_free = NC - h.len - (n_foods - 1);
+    if (n_free == 0) over = true;    // the grid is full
+    else snake_place_food(s, NC, snake_hash(seed, env, h.draws++) % (uint32_t)n_free, lane);
+  } else {                           // plain move: every occupied cell ages, the tail cell is vacated
+    for (int i = lane; i < NC; i += 64) {
+      const int c = s[i];
+      if (c > 0) s[i] = c - 1;
+    }
+    __syncthreads();
+    h.hr = nr; h.hc = nc;
+    if (lane == 0) s[nr * G + nc] = h.len;
+    __syncthreads();
+  }
+  h.ep_rew += (int)r;
+  over_rew = h.ep_rew;
+  if (over) {
+    h.ep_rew = 0;
+    snake_new_episode(s, G, NC, n_foods, seed, env, h.draws, h.hr, h.hc, h.len, lane);
+  }
+  return r;
+}
+
+// lane 0 of the wave that owns the env: what a step leaves beside the state words
+__device__ __forceinline__ void snake_publish(int e, float r, bool over, int over_rew, float* rew, float* done, float* reset,
+                                              int32_t* ep_stats) {
+  if (over && ep_stats != nullptr) {
+    atomicAdd(&ep_stats[0], 1);
+    atomicAdd(&ep_stats[1], over_rew);
+  }
+  rew[e] = r;
+  done[e] = over ? 1.0f : 0.0f;
+  reset[e] = over ? 1.0f : 0.0f;
+}
+
+__device__ __forceinline__ void snake_store(int32_t* st, const int* s, const SnakeHead& h, int NC, int lane) {
+  for (int i = lane; i < NC; i += 64) st[SNAKE_HDR + i] = s[i];
+  if (lane < SNAKE_HDR) {
+    const int hv = lane == 0 ? h.hr : lane == 1 ? h.hc : lane == 2 ? h.len : lane == 3 ? (int)h.draws : lane == 4 ? h.steps
+                 : lane == 5 ? h.ep_rew : 0;
+    st[lane] = hv;
+  }
+}
+
 template <bool STEP>
 __global__ __launch_bounds__(64) void snake_kernel(int32_t* __restrict__ state, int words, const int64_t* __restrict__ actions,
                                                    int64_t act_stride, int action_shift, int env_id0, uint32_t seed, int G,
@@ -107,69 +190,56 @@ __global__ __launch_bounds__(64) void snake_kernel(int32_t* __restrict__ state, 
   const int NC = G * G;
   const uint32_t env = (uint32_t)(env_id0 + e);
   int32_t* st = state + (int64_t)e * words;
-  int hr = st[0], hc = st[1], len = st[2];
-  uint32_t draws = (uint32_t)st[3];
-  int steps = st[4], ep_rew = st[5];
+  SnakeHead h;
+  snake_load_head(st, h);
   const int HW = G * unit * G * unit;
   if (STEP) {
-    for (int i = lane; i < NC; i += 64) s[i] = st[SNAKE_HDR + i];
-    __syncthreads();
     const int a = (int)((actions[(int64_t)e * act_stride] + (int64_t)action_shift) & 3);
-    const int nr = hr + (a == 0 ? -1 : (a == 2 ? 1 : 0)), nc = hc + (a == 1 ? 1 : (a == 3 ? -1 : 0));
-    const bool inside = nr >= 0 && nr < G && nc >= 0 && nc < G;
-    const int v = inside ? s[nr * G + nc] : 1;
-    __syncthreads();
-    float r = 0.0f;
-    bool over = false;
-    ++steps;
-    if (v > 0) {                       // wall, or a body cell (neck and tail cell included)
-      r = -1.0f;
-      over = true;
-    } else if (v < 0) {                // food: grow by one, nothing is vacated
-      r = 1.0f;
-      ++len;
-      hr = nr; hc = nc;
-      if (lane == 0) s[nr * G + nc] = len;
-      __syncthreads();
-      const int n_free = NC - len - (n_foods - 1);
-      if (n_free == 0) over = true;    // the grid is full
-      else snake_place_food(s, NC, snake_hash(seed, env, draws++) % (uint32_t)n_free, lane);
-    } else {                           // plain move: every occupied cell ages, the tail cell is vacated
-      for (int i = lane; i < NC; i += 64) {
-        const int c = s[i];
-        if (c > 0) s[i] = c - 1;
-      }
-      __syncthreads();
-      hr = nr; hc = nc;
-      if (lane == 0) s[nr * G + nc] = len;
-      __syncthreads();
-    }
-    ep_rew += (int)r;
-    if (over) {
-      if (lane == 0 && ep_stats != nullptr) {
-        atomicAdd(&ep_stats[0], 1);
-        atomicAdd(&ep_stats[1], ep_rew);
-      }
-      ep_rew = 0;
-      snake_new_episode(s, G, NC, n_foods, seed, env, draws, hr, hc, len, lane);
-    }
-    if (lane == 0) {
-      rew[e] = r;
-      done[e] = over ? 1.0f : 0.0f;
-      reset[e] = over ? 1.0f : 0.0f;
-    }
+    bool over;
+    int over_rew;
+    const float r = snake_advance(s, st, h, a, seed, env, G, NC, n_foods, lane, over, over_rew);
+    if (lane == 0) snake_publish(e, r, over, over_rew, rew, done, reset, ep_stats);
   } else {
-    draws = 0u; steps = 0; ep_rew = 0;
-    snake_new_episode(s, G, NC, n_foods, seed, env, draws, hr, hc, len, lane);
+    h.draws = 0u; h.steps = 0; h.ep_rew = 0;
+    snake_new_episode(s, G, NC, n_foods, seed, env, h.draws, h.hr, h.hc, h.len, lane);
   }
   __syncthreads();
-  for (int i = lane; i < NC; i += 64) st[SNAKE_HDR + i] = s[i];
-  if (lane < SNAKE_HDR) {
-    const int hv = lane == 0 ? hr : lane == 1 ? hc : lane == 2 ? len : lane == 3 ? (int)draws : lane == 4 ? steps
-                 : lane == 5 ? ep_rew : 0;
-    st[lane] = hv;
+  snake_store(st, s, h, NC, lane);
+  snake_write_frames(s, G, unit, h.len, frames + (int64_t)e * HW, nullptr, rgb == nullptr ? nullptr : rgb + (int64_t)e * 3 * HW,
+                     lane, 64);
+}
+
+// a2c_snake_step_post: snake_kernel<true> + the step's bookkeeping + the frame stack, WORLD_POST_WAVES waves per env.  Every
+// wave plays the same step on an LDS copy of the cells of its own (the step's barriers are the workgroup's: the first one,
+// behind the loads of the cells, also keeps wave 0's stores behind every wave's loads); all lanes then render from theirs.
+__global__ __launch_bounds__(WORLD_POST_THREADS) void snake_post_kernel(
+    int32_t* __restrict__ state, int words, const int64_t* __restrict__ actions, int64_t act_stride, int action_shift,
+    int env_id0, uint32_t seed, int G, int unit, int n_foods, float* __restrict__ rew, float* __restrict__ done,
+    float* __restrict__ reset, float* __restrict__ frames, uint8_t* __restrict__ rgb, int32_t* __restrict__ ep_stats,
+    const a2c_world_post post) {
+  __shared__ int s_all[WORLD_POST_WAVES][SNAKE_MAX_CELLS];
+  const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  int* s = s_all[tid >> 6];
+  const int NC = G * G;
+  const uint32_t env = (uint32_t)(env_id0 + e);
+  int32_t* st = state + (int64_t)e * words;
+  SnakeHead h;
+  snake_load_head(st, h);
+  const int HW = G * unit * G * unit;
+  const int a = (int)((actions[(int64_t)e * act_stride] + (int64_t)action_shift) & 3);
+  bool over;
+  int over_rew;
+  const float r = snake_advance(s, st, h, a, seed, env, G, NC, n_foods, lane, over, over_rew);
+  const float d = world_post_done(post, r, over ? 1.0f : 0.0f);
+  if (tid == 0) {
+    snake_publish(e, r, over, over_rew, rew, done, reset, ep_stats);
+    world_post_book(post, e, r, d);
   }
-  snake_write_frames(s, G, unit, len, frames + (int64_t)e * HW, rgb == nullptr ? nullptr : rgb + (int64_t)e * 3 * HW, lane);
+  __syncthreads();
+  if (tid < 64) snake_store(st, s, h, NC, tid);
+  float* top = world_post_planes(post, e, d, over, HW, tid);
+  snake_write_frames(s, G, unit, h.len, top, frames == nullptr ? nullptr : frames + (int64_t)e * HW,
+                     rgb == nullptr ? nullptr : rgb + (int64_t)e * 3 * HW, tid, WORLD_POST_THREADS);
 }
 
 bool snake_world_ok(int G, int unit, int n_foods) {
@@ -206,6 +276,21 @@ extern "C" int a2c_snake_step(int32_t* state, const int64_t* actions, int64_t ac
     return A2C_ERR_ARG;
   hipLaunchKernelGGL(snake_kernel<true>, dim3(B), dim3(64), 0, a2c_s(stream), state, SNAKE_HDR + G * G, actions, act_stride,
                      action_shift, env_id0, seed, G, unit, n_foods, rew, done, reset, frames, rgb, ep_stats);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+extern "C" int a2c_snake_step_post(int32_t* state, const int64_t* actions, int64_t act_stride, int action_shift, int B,
+                                   int env_id0, uint32_t seed, int G, int unit, int n_foods, float* rew, float* done,
+                                   float* reset, float* frames, uint8_t* rgb, int32_t* ep_stats, const a2c_world_post* post,
+                                   a2c_stream_t stream) {
+  if (B < 0 || env_id0 < 0 || act_stride < 0 || !snake_world_ok(G, unit, n_foods)) return A2C_ERR_ARG;
+  if (!a2c_world_post_ok(post, (int64_t)(G * unit) * (G * unit))) return A2C_ERR_ARG;
+  if (B == 0) return A2C_OK;
+  if (state == nullptr || actions == nullptr || rew == nullptr || done == nullptr || reset == nullptr) return A2C_ERR_ARG;
+  if (frames != nullptr && ((uintptr_t)frames & 15u) != 0) return A2C_ERR_ARG;
+  hipLaunchKernelGGL(snake_post_kernel, dim3(B), dim3(WORLD_POST_THREADS), 0, a2c_s(stream), state, SNAKE_HDR + G * G, actions,
+                     act_stride, action_shift, env_id0, seed, G, unit, n_foods, rew, done, reset, frames, rgb, ep_stats, *post);
   A2C_CHECK_LAUNCH();
   return A2C_OK;
 }

@@ -4,6 +4,11 @@
   * a2c_breakout_step: microseconds per launch at B = 32, 256, 2048;
   * env-steps/s of a full epoch (rollout + update, RMSprop) with DeviceBreakoutPool for FCModel and A3CModel (80 x 72 frames:
     the generic conv route), and how many launches Python issues per epoch through the ctypes binding;
+  * a2c_breakout_step + a2c_rollout_post against a2c_breakout_step_post (the same work in one launch): GPU microseconds per env
+    step at B = 32, 256, 2048, timed INSIDE a replayed hipGraph of 200 steps, so that the figure is kernel time and not the
+    rate at which the binding issues launches;
+  * --graphs on|off: the epochs with the Runner's one-graph device slot (the default of hyps["rollout_graphs"]) or with
+    its eager loop;
   * with --learn N: a learning sanity run -- N epochs on 64 device worlds with the reference's coefficients, then the
     sampled policy's reward per step on fresh device worlds against the uniform-random policy's on the host twins of the
     same worlds, with the standard error of the difference (envs are the independent units).
@@ -13,7 +18,7 @@ Method: everything that allocates or tunes runs in a warm-up; a sample times `--
 sees them; `--repeats` samples, the median is reported with min and max beside it.  Actions of the kernel timing are
 pre-drawn uniform ones.  One JSON line on stdout.
 
-    python tools/breakout_bench.py [--iters 2000] [--epochs 30] [--repeats 5] [--n-envs 256] [--learn 0]
+    python tools/breakout_bench.py [--iters 2000] [--epochs 30] [--repeats 5] [--n-envs 256] [--graphs on|off] [--learn 0]
 """
 import argparse
 import json
@@ -64,6 +69,45 @@ def bench_step(B, iters, repeats):
     return dict(us=round(1e3 * med / iters, 3), us_min=round(1e3 * lo / iters, 3), us_max=round(1e3 * hi / iters, 3))
 
 
+def bench_step_post(B, repeats, steps=200, C=4):
+    """GPU microseconds per env step of [a2c_breakout_step + a2c_rollout_post] and of a2c_breakout_step_post: `steps` steps captured
+    into one hipGraph each (states ping-pong between two (B, C*HW) buffers), the replay timed between two HIP events"""
+    from a2c_amd import ops
+    from a2c_amd.breakout import DeviceBreakoutPool
+    g = torch.Generator(device="cuda").manual_seed(3)
+    acts = torch.randint(0, N_ACT, (64, B), device="cuda", generator=g)
+    out = {}
+    for name in ("step_then_post", "step_post"):
+        pool = DeviceBreakoutPool(B, "cuda", seed=1)
+        pool.reset_all()
+        HW = pool.HW
+        S = C * HW
+        x = [torch.zeros((B, S), device="cuda") for _ in range(2)]
+        rewards, dones, deltas = (torch.zeros(2 * B, device="cuda") for _ in range(3))
+        val, val_prev = torch.rand(B, device="cuda"), torch.zeros(B, device="cuda")
+
+        def play():
+            for i in range(steps):
+                a, prev, nxt = acts[i & 63].data_ptr(), x[i & 1].data_ptr(), x[1 - (i & 1)].data_ptr()
+                if name == "step_post":
+                    post = ops.world_post(val.data_ptr(), 1, val_prev, rewards, dones, deltas, 2, 1, 0, .99, False, prev, S, nxt, S, C)
+                    pool.device_step_post(1, 0, B, (a, 1), post)
+                else:
+                    fr, rew, done, reset = pool.device_step(1, 0, B, actions=(a, 1))
+                    ops.rollout_post(rew, done, val.data_ptr(), 1, val_prev, rewards, dones, deltas, 2, 1, 0, .99, False, fr, reset,
+                                     prev, S, nxt, S, B, C, HW)
+        play()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with ops.graph_capture(graph):
+            play()
+        for _ in range(3):
+            graph.replay()
+        med, lo, hi = timed(graph.replay, 1, repeats)
+        out[name] = dict(us=round(1e3 * med / steps, 3), us_min=round(1e3 * lo / steps, 3), us_max=round(1e3 * hi / steps, 3))
+    return out
+
+
 def hyps_for(n_envs, T, n_frame_stack=4):
     return dict(gamma=.99, lambda_=.98, n_tsteps=T, n_rollouts=n_envs, n_envs=n_envs, n_frame_stack=n_frame_stack,
                 action_shift=0, render=False, env_type="Breakout-device", use_bptt=False, use_nstep_rets=False, norm_advs=True,
@@ -94,14 +138,14 @@ class CountedLib:
         return counted
 
 
-def bench_epoch(model, n_envs, T, epochs, repeats):
+def bench_epoch(model, n_envs, T, epochs, repeats, graphs=True):
     import a2c_amd
     from a2c_amd import ops
     from a2c_amd.breakout import DeviceBreakoutPool
     from a2c_amd.runner import Runner
     from a2c_amd.updater import Updater
     ss = (4,) + FRAME
-    hyps = hyps_for(n_envs, T)
+    hyps = dict(hyps_for(n_envs, T), rollout_graphs=graphs)
     torch.manual_seed(0)
     net = getattr(a2c_amd.models, model)(list(ss), N_ACT, h_size=256)
     N = n_envs * T
@@ -126,7 +170,7 @@ def bench_epoch(model, n_envs, T, epochs, repeats):
     finally:
         ops.lib = real
     f = lambda ms: round(N * epochs / (ms * 1e-3))
-    return dict(model=model, n_envs=n_envs, n_tsteps=T, ms_per_epoch=round(med / epochs, 3), env_steps_per_s=f(med),
+    return dict(model=model, n_envs=n_envs, n_tsteps=T, rollout_graphs=graphs, ms_per_epoch=round(med / epochs, 3), env_steps_per_s=f(med),
                 env_steps_per_s_min=f(hi), env_steps_per_s_max=f(lo), launches_issued_per_epoch=counted.n)
 
 
@@ -188,15 +232,19 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--n-envs", type=int, default=256)
     ap.add_argument("--n-tsteps", type=int, default=16)
+    ap.add_argument("--graphs", choices=("on", "off"), default="on", help="the Runner's one-graph device slot, or its eager loop")
     ap.add_argument("--learn", type=int, default=0, help="epochs of the learning sanity run (0: skip it)")
     ap.add_argument("--learn-model", default="FCModel")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "breakout_bench needs the MI355X"
-    res = dict(device=torch.cuda.get_device_name(0), iters=args.iters, repeats=args.repeats, step={}, epoch={})
+    from a2c_amd.breakout import DeviceBreakoutPool as DevicePool
+    res = dict(device=torch.cuda.get_device_name(0), iters=args.iters, repeats=args.repeats, graphs=args.graphs, step={}, epoch={})
     for B in (32, 256, 2048):
         res["step"][f"B{B}"] = bench_step(B, args.iters, args.repeats)
+    if hasattr(DevicePool, "device_step_post"):
+        res["step_post_in_graph"] = {f"B{B}": bench_step_post(B, args.repeats) for B in (32, 256, 2048)}
     for model in ("FCModel", "A3CModel"):
-        res["epoch"][model] = bench_epoch(model, args.n_envs, args.n_tsteps, args.epochs, args.repeats)
+        res["epoch"][model] = bench_epoch(model, args.n_envs, args.n_tsteps, args.epochs, args.repeats, args.graphs == "on")
     if args.learn:
         res["learn"] = learn(args.learn_model, args.learn)
     print(json.dumps(res))
