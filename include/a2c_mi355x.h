@@ -246,6 +246,15 @@ int a2c_rollout_post_rec(const float *rew, const float *done, const float *val, 
 int a2c_rollout_bootstrap(const float *val_boot, int64_t val_stride, const float *val_prev, float *rewards,
                           float *dones, float *deltas, int B, int64_t T, int64_t slot0,
                           float gamma, a2c_stream_t stream);
+/* Evaluation on a device env pool: the FIRST episode of every env, out of the rows a rollout slot left.  Env e (< E) owns
+ * rewards / dones [e*T .. e*T + K) (K steps played, rows T >= K apart; dones as the record kernels wrote them, Pong
+ * override included).  While active[e] != 0 and t0 + t < max_steps, for t = 0 .. K-1 in order:
+ * ep_rew[e] = ep_rew[e] + rewards[e*T+t] (fp32, in step order), ep_len[e] += 1, and a nonzero dones[e*T+t] sets
+ * active[e] = 0 -- what the restarted world does afterwards is ignored.  t0 = the global index of step 0 of this chunk.
+ * *n_active = the number of envs whose active is still nonzero: overwritten, not added to.  One workgroup, no atomics:
+ * deterministic.  An env that enters with active[e] == 0 is not written.                                          */
+int a2c_eval_scan(const float *rewards, const float *dones, int64_t T, int64_t K, int E, int64_t t0, int64_t max_steps,
+                  float *ep_rew, int32_t *ep_len, int32_t *active, int32_t *n_active, a2c_stream_t stream);
 /* One whole rollout step of the A3CModel-shaped policy (models.py:60-90: conv 8x8/s4 -> 16,
  * conv 4x4/s2 -> 32, proj_matrx WITHOUT activation, pi/value heads) in ONE launch, one workgroup
  * per env; replaces, per step of Runner.rollout (runner.py:190-232):

@@ -17,7 +17,7 @@ _SUBMODULES = ("_lib", "ops", "utils", "models", "optim", "parallel", "preproces
 _NAMES = {
     "A3CModel": "models", "ConvModel": "models", "FCModel": "models", "GRU": "models", "GRUFCModel": "models",
     "GRUModel": "models",
-    "Runner": "runner", "StatsRunner": "runner", "SequentialEnvironment": "runner", "HostEnvPool": "runner",
+    "Runner": "runner", "StatsRunner": "runner", "DeviceStatsRunner": "runner", "SequentialEnvironment": "runner", "HostEnvPool": "runner",
     "ProcessEnvPool": "hostpool",
     "Updater": "updater",
     "discount": "utils", "sample_action": "utils", "next_state": "utils", "cuda_if": "utils", "try_key": "utils",

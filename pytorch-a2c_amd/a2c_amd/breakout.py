@@ -35,7 +35,7 @@ serves with one draw.  Randomness is counter based: draw i of env e is ``hash32(
 Snake and Pong worlds; the only draws are serves."""
 import numpy as np
 
-from .snake import hash32
+from .snake import _env_id0, hash32
 
 N_ACTIONS = 4
 W, H = 72, 80
@@ -254,18 +254,19 @@ class BreakoutFactory:
 
 class DeviceBreakoutPool:
     """``n_envs`` Breakout worlds in device memory (the Runner's device-pool protocol).  Env j is the world
-    ``BreakoutEnv(seed, env_id=j, ...)``: same draws, same frames.  ``device_step`` returns ``done`` and ``reset`` as two
+    ``BreakoutEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames.  ``device_step`` returns ``done`` and ``reset`` as two
     tensors holding the same values, the real done.  ``episode_stats`` counts the finished episodes and sums their rewards."""
     needs_actions = True
     frame_shape = (1, H, W)
 
-    def __init__(self, n_envs, device="cuda", seed=0, lives=5, max_episode_steps=10000):
+    def __init__(self, n_envs, device="cuda", seed=0, lives=5, max_episode_steps=10000, env_id0=0):
         import torch
         from . import ops
         self.world = check_world(lives, max_episode_steps)
         self.B, self.seed, self.device = int(n_envs), int(seed) & _M, torch.device(device)
         if self.B < 1:
             raise ValueError("DeviceBreakoutPool: n_envs >= 1")
+        self.env_id0 = _env_id0(env_id0, self.B)
         self.HW = H * W
         self.words = ops.breakout_state_bytes(self.world[0]) // 4
         dev = self.device
@@ -279,10 +280,13 @@ class DeviceBreakoutPool:
     def __len__(self):
         return self.B
 
-    def reset_all(self):
-        """(re)starts every world: counters to 0, then the serve draw; state and frames of the reset positions"""
+    def reset_all(self, env_id0=None):
+        """(re)starts every world: counters to 0, then the serve draw; state and frames of the reset positions.  ``env_id0``
+        re-bases the pool first: env j becomes world ``env_id0 + j``"""
         from . import ops
-        ops.breakout_reset(self.state, self.B, 0, self.seed, *self.world, self.frames, self.HW)
+        if env_id0 is not None:
+            self.env_id0 = _env_id0(env_id0, self.B)
+        ops.breakout_reset(self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
         self.started = True
 
     def start(self, runner):
@@ -303,9 +307,9 @@ class DeviceBreakoutPool:
         if env0 < 0 or B < 1 or env0 + B > self.B:
             raise ValueError("DeviceBreakoutPool: env range outside the pool")
         sl = slice(env0, env0 + B)
-        ops.breakout_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, env0, self.seed, *self.world,
-                          self.frames[sl], self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl], self.ep_stats[0:1],
-                          self.ep_stats[1:2])
+        ops.breakout_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
+                          self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl],
+                          self.ep_stats[0:1], self.ep_stats[1:2])
         return self.frames[sl], self.rew[sl], self.done[sl], self.reset_mask[sl]
 
     def device_step(self, t, env0, B, actions=None):
@@ -323,9 +327,9 @@ class DeviceBreakoutPool:
         if env0 < 0 or B < 1 or env0 + B > self.B:
             raise ValueError("DeviceBreakoutPool: env range outside the pool")
         sl = slice(env0, env0 + B)
-        ops.breakout_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, env0, self.seed, *self.world,
-                               self.frames[sl] if frames else None, self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl],
-                               post, self.ep_stats[0:1], self.ep_stats[1:2])
+        ops.breakout_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
+                               self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl],
+                               self.done[sl], self.reset_mask[sl], post, self.ep_stats[0:1], self.ep_stats[1:2])
         return self.rew[sl], self.done[sl], self.reset_mask[sl]
 
     def episode_stats(self):

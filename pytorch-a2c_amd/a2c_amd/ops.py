@@ -667,6 +667,19 @@ def rollout_bootstrap(val_ptr, val_stride, val_prev, rewards, dones, deltas, B, 
                                       float(gamma), st if st is not None else stream()), "a2c_rollout_bootstrap")
 
 
+def eval_scan(rewards, dones, T, K, E, t0, max_steps, ep_rew, ep_len, active, n_active, st=None):
+    """first-episode scan of a rollout slot's rows (a2c_eval_scan): rewards / dones rows T apart, K steps played, chunk
+    starting at global step t0; ep_rew (E,) fp32, ep_len / active (E,) and n_active (1,) int32 are updated in place"""
+    _chk(rewards, "rewards"); _chk(dones, "dones"); _chk(ep_rew, "ep_rew")
+    for n, x in (("ep_len", ep_len), ("active", active), ("n_active", n_active)):
+        _chk(x, n, torch.int32)
+    if rewards.numel() < (E - 1) * T + K or dones.numel() < (E - 1) * T + K or min(ep_rew.numel(), ep_len.numel(),
+                                                                                  active.numel()) < E or n_active.numel() < 1:
+        raise ValueError("eval_scan: a buffer is shorter than E rows of T")
+    check(lib().a2c_eval_scan(_p(rewards), _p(dones), T, K, E, t0, max_steps, _p(ep_rew), _p(ep_len), _p(active), _p(n_active),
+                              _st(st)), "a2c_eval_scan")
+
+
 def copy_rows(src_ptr, src_stride, dst_ptr, dst_stride, B, n, st=None):
     check(lib().a2c_copy_rows(src_ptr, src_stride, dst_ptr, dst_stride, B, n, st if st is not None else stream()),
           "a2c_copy_rows")

@@ -29,7 +29,7 @@ from ``d & 1`` (1: towards the agent), vy as above.  Randomness is counter based
 ``hash32(seed, e, i)``, the mixing function of the Snake worlds."""
 import numpy as np
 
-from .snake import hash32
+from .snake import _env_id0, hash32
 
 N_ACTIONS = 3
 W = H = 80
@@ -212,20 +212,21 @@ class PongFactory:
 
 class DevicePongPool:
     """``n_envs`` Pong worlds in device memory (the Runner's device-pool protocol).  Env j is the world
-    ``PongEnv(seed, env_id=j, ...)``: same draws, same frames.  ``device_step`` returns ``done = (rew != 0) or real
+    ``PongEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames.  ``device_step`` returns ``done = (rew != 0) or real
     done`` (the Pong override of the reference's runner) and ``reset = real done`` as two tensors.  ``episode_stats``
     counts what the Runner's ``rew_q`` counts for a "Pong" env type: every ``done``, with the reward since the last one."""
     needs_actions = True
     frame_shape = (1, H, W)
 
     def __init__(self, n_envs, device="cuda", seed=0, points_to_win=21, max_episode_steps=10000, opp_skill_num=3,
-                 opp_skill_den=4):
+                 opp_skill_den=4, env_id0=0):
         import torch
         from . import ops
         self.world = check_world(points_to_win, max_episode_steps, opp_skill_num, opp_skill_den)
         self.B, self.seed, self.device = int(n_envs), int(seed) & _M, torch.device(device)
         if self.B < 1:
             raise ValueError("DevicePongPool: n_envs >= 1")
+        self.env_id0 = _env_id0(env_id0, self.B)
         self.HW = H * W
         self.words = ops.pong_state_bytes(self.world[0]) // 4
         dev = self.device
@@ -239,10 +240,13 @@ class DevicePongPool:
     def __len__(self):
         return self.B
 
-    def reset_all(self):
-        """(re)starts every world: counters to 0, then the reset draw; state and frames of the reset positions"""
+    def reset_all(self, env_id0=None):
+        """(re)starts every world: counters to 0, then the reset draw; state and frames of the reset positions.  ``env_id0``
+        re-bases the pool first: env j becomes world ``env_id0 + j``"""
         from . import ops
-        ops.pong_reset(self.state, self.B, 0, self.seed, *self.world, self.frames, self.HW)
+        if env_id0 is not None:
+            self.env_id0 = _env_id0(env_id0, self.B)
+        ops.pong_reset(self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
         self.started = True
 
     def start(self, runner):
@@ -263,9 +267,9 @@ class DevicePongPool:
         if env0 < 0 or B < 1 or env0 + B > self.B:
             raise ValueError("DevicePongPool: env range outside the pool")
         sl = slice(env0, env0 + B)
-        ops.pong_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, env0, self.seed, *self.world,
-                      self.frames[sl], self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl], self.ep_stats[0:1],
-                      self.ep_stats[1:2])
+        ops.pong_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
+                      self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl],
+                      self.ep_stats[0:1], self.ep_stats[1:2])
         return self.frames[sl], self.rew[sl], self.done[sl], self.reset_mask[sl]
 
     def device_step(self, t, env0, B, actions=None):
@@ -283,9 +287,9 @@ class DevicePongPool:
         if env0 < 0 or B < 1 or env0 + B > self.B:
             raise ValueError("DevicePongPool: env range outside the pool")
         sl = slice(env0, env0 + B)
-        ops.pong_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, env0, self.seed, *self.world,
-                           self.frames[sl] if frames else None, self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl],
-                           post, self.ep_stats[0:1], self.ep_stats[1:2])
+        ops.pong_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
+                           self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl], self.done[sl],
+                           self.reset_mask[sl], post, self.ep_stats[0:1], self.ep_stats[1:2])
         return self.rew[sl], self.done[sl], self.reset_mask[sl]
 
     def episode_stats(self):

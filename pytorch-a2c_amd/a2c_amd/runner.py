@@ -29,6 +29,9 @@ Env pools (``env_pool=``):
     ``device_step_post(t, env0, B, actions, post)`` (the Snake / Pong / Breakout worlds: step, bookkeeping and next state
     in one launch) is played as ONE hipGraph per slot when ``hyps['rollout_graphs']`` (default true) and the ``actions``
     buffer is device resident: first rollout eager, second captured, then replayed (``_rollout_block_device``).
+
+``DeviceStatsRunner`` evaluates such a pool on the device (``train()``: ``hyps['eval_pool'] = 'device'``): a private Runner
+plays ``n_test_eps`` worlds in chunks, a2c_eval_scan keeps every env's first episode.
 """
 import os
 import queue
@@ -132,8 +135,13 @@ class Runner:
     runner.py:110).  ``datas`` tensors should live on the device (``cuda_if`` them like
     training.py:94-101); ``actions`` may stay a host LongTensor like the reference's."""
 
-    def __init__(self, datas, hyps, gate_q, stop_q, rew_q, env_pool=None, uniform_fn=None, ingest=None, normal_fn=None):
+    def __init__(self, datas, hyps, gate_q, stop_q, rew_q, env_pool=None, uniform_fn=None, ingest=None, normal_fn=None,
+                 stash=True, bootstrap=True):
         self.hyps, self.datas = hyps, datas
+        # an evaluation's Runner (DeviceStatsRunner) plays a net between a training rollout and its update: stash=False leaves
+        # what that rollout stashed in the net for the update alone; bootstrap=False leaves the last step's rewards / dones
+        # rows as the env returned them (no runner.py:236-245) -- device pools with ``device_step_post`` only
+        self.stash, self.bootstrap = bool(stash), bool(bootstrap)
         self.gate_q, self.stop_q, self.rew_q = gate_q, stop_q, rew_q
         self.obs_deque = deque(maxlen=hyps["n_frame_stack"])     # kept for API parity (single-env helpers)
         self.env_pool = env_pool
@@ -189,6 +197,8 @@ class Runner:
         self.S = C * self.HW
         self.device_pool = hasattr(pool, "device_step")
         self.proc_pool = hasattr(pool, "post_actions")
+        if not self.bootstrap and not hasattr(pool, "device_step_post"):
+            raise ValueError("a2c_amd.Runner: bootstrap=False needs a device env pool with device_step_post")
         # continuous nets (is_discrete=False): actions are float rows of n, sampled by a2c_gauss_head
         self.cont = not getattr(net, "is_discrete", True)
         self.n_act = int(net.output_space)
@@ -366,17 +376,18 @@ class Runner:
             else:
                 self.materialize_states()
         # whatever an earlier rollout stashed in the net describes states this call overwrites
-        net._stash = None
-        net._stash_frames = None
-        net._stash_lm = False
+        if self.stash:
+            net._stash = None
+            net._stash_frames = None
+            net._stash_lm = False
+            if hasattr(net, "_cells_done"):
+                net._cells_done = -1
         self._lm_written = False
-        if hasattr(net, "_cells_done"):
-            net._cells_done = -1
         # a call that fills EVERY row of the rollout buffer: the step kernels may stash the conv activations
         # of each state for the update that follows (same weights, same states)
         self._stash_bufs = None
         self._frames_written = None
-        if idxs == list(range(N // T_)) and N % T_ == 0:
+        if self.stash and idxs == list(range(N // T_)) and N % T_ == 0:
             self._stash_bufs = net.stash_rows(self.datas["states"], N, T=T_)
         stash_all = self._stash_bufs is not None
         seqs = self.env_pool.seq_env if self.proc_pool else None
@@ -560,6 +571,8 @@ class Runner:
                 ops.frame_stack_push(_Ptr(fr.ptr32), reset, sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
             if side is not None:
                 main.wait_stream(side)     # join before the next forward overwrites the heads buffer
+        if not self.bootstrap:
+            return
         # bootstrap (runner.py:236-245): value of the state after the last step
         out = self._forward(net, bm.data_ptr(), S, B, env0, st)
         ops.rollout_bootstrap(out["vals"].data_ptr(), out["vals"].stride(0), val_prev, rewards, dones, deltas, B, T,
@@ -596,7 +609,7 @@ class Runner:
                 else:
                     kw.update(frame_new=fr.ptr32)
             if t == T:
-                net._step(B, st, bootstrap=1, **kw)
+                net._step(B, st, bootstrap=int(self.bootstrap), **kw)
                 break
             u = self._uniforms(t, B, env0) if ub is None else ub[t, env0:env0 + B]      # ub: the slot's persistent uniforms
             act = self.act_dev[env0:env0 + B]
@@ -644,8 +657,9 @@ class Runner:
         if torch.cuda.is_current_stream_capturing():
             return body()
         stash_ptrs = None if stash is None else tuple(x.data_ptr() for x in stash if hasattr(x, "data_ptr"))
-        key = (id(net), id(pool), slot0, env0, B, T, float(hyps["gamma"]), "Pong" in hyps["env_type"], fused, stash_ptrs,
-               tuple(D[k].data_ptr() for k in sorted(D) if D[k].is_cuda))
+        # (the worlds' launches carry their env ids: a re-based pool is another key)
+        key = (id(net), id(pool), int(getattr(pool, "env_id0", 0)), slot0, env0, B, T, float(hyps["gamma"]),
+               "Pong" in hyps["env_type"], fused, stash_ptrs, tuple(D[k].data_ptr() for k in sorted(D) if D[k].is_cuda))
         cache = self.__dict__.setdefault("_dev_graphs", {})
         g = cache.get(key)
         if g is None:
@@ -691,6 +705,8 @@ class Runner:
             post = ops.world_post(vals.data_ptr(), vals.stride(0), val_prev, rewards, dones, deltas, T, t, slot0, gamma, pong,
                                   sp(t), T * S, nxt_ptr, nxt_stride, C, done_eff=None if h is None else done_eff, h=h)
             pool.device_step_post(t, env0, B, (a_ptr, a_stride), post)
+        if not self.bootstrap:
+            return
         out = self._forward(net, bm.data_ptr(), S, B, env0, st)            # bootstrap (runner.py:236-245)
         ops.rollout_bootstrap(out["vals"].data_ptr(), out["vals"].stride(0), val_prev, rewards, dones, deltas, B, T, slot0,
                               gamma, st)
@@ -1395,3 +1411,119 @@ class StatsRunner:
                         h = cuda_if(torch.zeros(1, net.h_size))
                 state = next_state(self.env, self.obs_deque, obs=obs, reset=reset)
         return ep_rew / ep_count
+
+
+class DeviceStatsRunner:
+    """``StatsRunner`` for the device-resident worlds (``snake.DeviceSnakePool``, ``pong.DevicePongPool``,
+    ``breakout.DeviceBreakoutPool``): ``pool`` holds E = n_test_eps worlds, each plays exactly ONE episode per ``rollout(net)``
+    and the result is (sum of the episode rewards) / E, as ``StatsRunner._rollout_batched`` -- with nothing on the host.
+
+    There is no second rollout loop: a private ``Runner`` plays the E worlds in chunks of K = ``hyps['eval_chunk']`` (default
+    32) lock-step steps with the launches of the training path (a chunk is one slot graph: first chunk of a call eager, second
+    captured, later ones replayed), a2c_eval_scan closes every env at its first done out of the chunk's rewards / dones rows,
+    and ONE 4-byte read per chunk tells the host whether an env is still playing.  ``hyps['max_eval_steps']`` (default 10**6)
+    caps the episode; the cap may fall inside a chunk.
+
+    Every call plays fresh, reproducible worlds: call c re-bases the pool to env ids 10007 + c*E .. (the first call: the
+    ids of ``train()``'s host twins).  The world kernels take the env id as a launch argument, so a re-based pool needs its
+    chunk graph captured again: one capture per ``rollout(net)``.
+
+    The private Runner neither stashes activations nor bootstraps (the scan reads the last step's rows as the env left
+    them), and plays through a "roll" workspace of its own: what a training rollout left in the net for its update, and the
+    buffers its captured graphs point at, are as they were.  ``uniform_fn(t, E, 0)`` sees the GLOBAL step index t."""
+
+    ENV_ID0 = 10007
+
+    def __init__(self, hyps, pool, uniform_fn=None, keep_actions=False):
+        if not hasattr(pool, "device_step_post"):
+            raise ValueError("DeviceStatsRunner: a device env pool with device_step_post (Snake / Pong / Breakout worlds)")
+        self.pool, self.uniform_fn, self.keep_actions = pool, uniform_fn, bool(keep_actions)
+        self.E = len(pool)
+        self.K = int(try_key(hyps, "eval_chunk", None) or 32)
+        self.max_steps = int(try_key(hyps, "max_eval_steps", None) or 10 ** 6)
+        if self.K < 1 or self.max_steps < 1:
+            raise ValueError("DeviceStatsRunner: eval_chunk >= 1 and max_eval_steps >= 1")
+        self.hyps = dict(hyps, n_envs=self.E, n_rollouts=self.E, n_tsteps=self.K)
+        self.calls, self.last = 0, None
+        self.runner = self.datas = None
+        self._chunk = 0
+
+    def _uniforms(self, t, B, env0):
+        return self.uniform_fn(self._chunk * self.K + t, B, env0)
+
+    def _setup(self, net):
+        E, K, dev = self.E, self.K, net._dev
+        C = int(self.hyps["n_frame_stack"])
+        n = E * K
+        f32 = dict(dtype=torch.float32, device=dev)
+        D = dict(states=torch.zeros((n, C) + tuple(self.pool.frame_shape[1:]), **f32), deltas=torch.zeros(n, **f32),
+                 rewards=torch.zeros(n, **f32), dones=torch.zeros(n, **f32),
+                 actions=torch.zeros(n, dtype=torch.int64, device=dev))
+        if net.is_recurrent:
+            D["h_states"] = torch.zeros((n, net.h_size), **f32)
+        self.datas = D
+        self.runner = Runner(D, self.hyps, None, None, None, env_pool=self.pool,
+                             uniform_fn=None if self.uniform_fn is None else self._uniforms, stash=False, bootstrap=False)
+        self.ep_rew = torch.zeros(E, **f32)
+        self.ep_len, self.active = (torch.zeros(E, dtype=torch.int32, device=dev) for _ in range(2))
+        self.n_active = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._ones = torch.ones(E, **f32)
+        self._ws = ops.Workspace(dev)
+
+    def _restart(self, net):
+        """fresh worlds for this call, and the Runner's carried state as ``pool.start(runner)`` leaves it"""
+        pool, r = self.pool, self.runner
+        if not r._ready:
+            r.start(net)
+        r.__dict__.get("_dev_graphs", {}).clear()          # (graphs of the ids the pool leaves: never replayed again)
+        (pool.reset_all if hasattr(pool, "reset_all") else pool.reset)(env_id0=self.ENV_ID0 + self.calls * self.E)
+        ops.frame_stack_push(pool.frames, self._ones, r.bookmark.data_ptr(), r.S, r.bookmark.data_ptr(), r.S, self.E, r.C, r.HW)
+        r.val_prev.zero_()
+        r.done_eff.zero_()
+        if r.h is not None:
+            r.h.zero_()
+        self.ep_rew.zero_()
+        self.ep_len.zero_()
+        self.active.fill_(1)
+
+    def rollout(self, net):
+        if not getattr(net, "is_discrete", True):
+            raise ValueError("DeviceStatsRunner: the device worlds take discrete actions; the net is continuous")
+        net._ensure_device()
+        if self.runner is None:
+            self._setup(net)
+        E, K, D = self.E, self.K, self.datas
+        slots = list(range(E))
+        kept = dict(actions=[], rewards=[], dones=[])
+        # the evaluation's forwards run through a "roll" workspace of their own: the training rollout's buffers (its graphs
+        # hold their addresses) neither move nor change
+        roll = net._ws.get("roll")
+        net._ws["roll"] = self._ws
+        try:
+            self._restart(net)
+            chunk = 0
+            while True:
+                self._chunk = chunk
+                self.runner.rollout(net, slots, self.hyps)
+                ops.eval_scan(D["rewards"], D["dones"], K, K, E, chunk * K, self.max_steps, self.ep_rew, self.ep_len,
+                              self.active, self.n_active)
+                if self.keep_actions:
+                    for k in kept:
+                        kept[k].append(D[k].view(E, K).t().clone())
+                left = int(self.n_active.item())               # the one host read of the chunk
+                chunk += 1
+                if left == 0 or chunk * K >= self.max_steps:
+                    break
+        finally:
+            if roll is None:
+                net._ws.pop("roll", None)
+            else:
+                net._ws["roll"] = roll
+        self.calls += 1
+        steps = min(chunk * K, self.max_steps)
+        ep_rew = self.ep_rew.cpu()
+        self.last = dict(ep_rew=ep_rew, ep_len=self.ep_len.cpu(), active=self.active.cpu(), steps=steps, chunks=chunk)
+        for k, v in kept.items():
+            if self.keep_actions:
+                self.last[k] = torch.cat(v)[:steps].cpu()
+        return float(ep_rew.double().sum()) / E

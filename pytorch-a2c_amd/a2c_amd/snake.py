@@ -170,17 +170,26 @@ class SnakeFactory:
         return SnakeEnv(**self.kw)
 
 
+def _env_id0(env_id0, B):
+    """first env id of a pool of B worlds: the kernels take ids as non-negative C ints"""
+    v = int(env_id0)
+    if v < 0 or v + int(B) > 0x7FFFFFFF:
+        raise ValueError(f"env_id0={env_id0}: env ids are 0 .. 2^31 - 1")
+    return v
+
+
 class DeviceSnakePool:
     """``n_envs`` Snake worlds in device memory (the Runner's device-pool protocol).  Env j is the world
-    ``SnakeEnv(seed, env_id=j, ...)``: same draws, same frames.  ``needs_actions``: the Runner hands ``device_step`` the
+    ``SnakeEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames.  ``needs_actions``: the Runner hands ``device_step`` the
     address and stride of the int64 actions the sampler just wrote."""
     needs_actions = True
 
-    def __init__(self, n_envs, device="cuda", seed=0, grid_size=15, unit_size=4, n_foods=2, raw_frames=False):
+    def __init__(self, n_envs, device="cuda", seed=0, grid_size=15, unit_size=4, n_foods=2, raw_frames=False, env_id0=0):
         import torch
         from . import ops
         self.G, self.u, self.n_foods = check_world(grid_size, unit_size, n_foods)
         self.B, self.seed, self.device = int(n_envs), int(seed) & _M, torch.device(device)
+        self.env_id0 = _env_id0(env_id0, self.B)
         side = self.G * self.u
         self.frame_shape = (1, side, side)
         self.HW = side * side
@@ -197,10 +206,13 @@ class DeviceSnakePool:
     def __len__(self):
         return self.B
 
-    def reset(self):
-        """(re)starts every world: state, frames (and raw frames) of the reset positions"""
+    def reset(self, env_id0=None):
+        """(re)starts every world: state, frames (and raw frames) of the reset positions.  ``env_id0`` re-bases the pool
+        first: env j becomes world ``env_id0 + j``"""
         from . import ops
-        ops.snake_reset(self.state, self.B, 0, self.seed, self.G, self.u, self.n_foods, self.frames, self.rgb)
+        if env_id0 is not None:
+            self.env_id0 = _env_id0(env_id0, self.B)
+        ops.snake_reset(self.state, self.B, self.env_id0, self.seed, self.G, self.u, self.n_foods, self.frames, self.rgb)
         self.started = True
 
     def start(self, runner):
@@ -221,9 +233,9 @@ class DeviceSnakePool:
         if env0 < 0 or B < 1 or env0 + B > self.B:
             raise ValueError("DeviceSnakePool: env range outside the pool")
         sl = slice(env0, env0 + B)
-        ops.snake_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, env0, self.seed, self.G, self.u,
-                       self.n_foods, self.rew[sl], self.done[sl], self.reset_mask[sl], self.frames[sl],
-                       None if self.rgb is None else self.rgb[sl], self.ep_stats)
+        ops.snake_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
+                       self.seed, self.G, self.u, self.n_foods, self.rew[sl], self.done[sl], self.reset_mask[sl],
+                       self.frames[sl], None if self.rgb is None else self.rgb[sl], self.ep_stats)
         return self.frames[sl], self.rew[sl], self.done[sl], self.reset_mask[sl]
 
     def device_step(self, t, env0, B, actions=None):
@@ -241,9 +253,10 @@ class DeviceSnakePool:
         if env0 < 0 or B < 1 or env0 + B > self.B:
             raise ValueError("DeviceSnakePool: env range outside the pool")
         sl = slice(env0, env0 + B)
-        ops.snake_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, env0, self.seed, self.G, self.u,
-                            self.n_foods, self.rew[sl], self.done[sl], self.reset_mask[sl], self.frames[sl] if frames else None,
-                            post, None if self.rgb is None else self.rgb[sl], self.ep_stats)
+        ops.snake_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
+                            self.seed, self.G, self.u, self.n_foods, self.rew[sl], self.done[sl], self.reset_mask[sl],
+                            self.frames[sl] if frames else None, post, None if self.rgb is None else self.rgb[sl],
+                            self.ep_stats)
         return self.rew[sl], self.done[sl], self.reset_mask[sl]
 
     def episode_stats(self):

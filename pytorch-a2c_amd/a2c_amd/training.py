@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import models, preprocessing
-from .runner import HostEnvPool, Runner, SequentialEnvironment, StatsRunner
+from .runner import DeviceStatsRunner, HostEnvPool, Runner, SequentialEnvironment, StatsRunner
 from .updater import Updater
 from .utils import cuda_if, deque_maxmin, try_key
 
@@ -78,8 +78,18 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     0..255 on the uint8 transport; with ``hyps["device_prep"] = "breakout_prep"`` the process pool carries the RAW frames
     and the device preps them); 4 actions, ``action_shift`` 0 unless given, real dones only, evaluation on host
     ``BreakoutEnv``s.
+    ``hyps["eval_pool"] = "device"`` (the three ``*-device`` env types, no ``eval_env``) evaluates on the device instead: a
+    second pool of ``n_test_eps`` worlds behind a ``DeviceStatsRunner`` (keys ``eval_chunk``, ``max_eval_steps``); the default
+    ``"host"`` is the host twins.
     Returns the best evaluation reward."""
     hyps = dict(DEFAULTS, **hyps)
+    eval_pool = try_key(hyps, "eval_pool", None) or "host"
+    if eval_pool not in ("host", "device"):
+        raise ValueError(f"a2c_amd: hyps['eval_pool'] is 'host' or 'device', not {eval_pool!r}")
+    if eval_pool == "device" and (eval_env is not None or env_fn is not None or hyps.get("env_type") not in (
+            "Snake-device", "Pong-device", "Breakout-device")):
+        raise ValueError("a2c_amd: hyps['eval_pool'] = 'device' evaluates the device worlds (env_type 'Snake-device', "
+                         "'Pong-device' or 'Breakout-device') and takes no eval_env / env_fn")
     if hyps["n_rollouts"] is None:
         hyps["n_rollouts"] = hyps["n_envs"]
     hyps["main_path"] = try_key(hyps, "main_path", "./")
@@ -267,7 +277,12 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     for i in range(n_rollouts):
         gate_q.put(i)
     # evaluation: the caller's single env (reference loop), else n_test_eps gym envs in lock-step on the device
-    if eval_env is not None:
+    if eval_pool == "device":
+        # a second pool of the training pool's kind: same world and seed, n_test_eps worlds (DeviceStatsRunner gives them the
+        # env ids of the host twins below, and fresh ones on every later call)
+        stats_runner = DeviceStatsRunner(hyps, type(pool)(try_key(hyps, "n_test_eps", 15), device=pool.device, **world),
+                                         uniform_fn=uniform_fn)
+    elif eval_env is not None:
         stats_runner = StatsRunner(hyps, env=eval_env)
     elif snake_world is not None or pong_world is not None or breakout_world is not None:
         # host twins of worlds the training pool does not play (env ids from 10007 on)

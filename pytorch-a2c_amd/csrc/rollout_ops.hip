@@ -402,6 +402,36 @@ __global__ __launch_bounds__(256) void frame_store_begin_kernel(uint8_t* __restr
     reinterpret_cast<unsigned int*>(fr)[i] = reinterpret_cast<const unsigned int*>(fr + T * HW)[i];
   if (blockIdx.x == 0 && threadIdx.x == 0) nv_rows[(long)b * T] = nv_carry[b];
 }
+// evaluation: the first episode of every env out of a slot's rewards / dones rows (DeviceStatsRunner).  One lane per env walks
+// its K steps in order (fp32 sum in step order, like the discount scan); ONE workgroup grid-strides over the envs and counts
+// the ones still playing through the waves and LDS, so *n_active is overwritten by a plain store: no atomics, no zeroing launch
+__global__ __launch_bounds__(256) void eval_scan_kernel(const float* __restrict__ rewards, const float* __restrict__ dones, long T,
+                                                        long K, int E, long t0, long max_steps, float* __restrict__ ep_rew,
+                                                        int* __restrict__ ep_len, int* __restrict__ active,
+                                                        int* __restrict__ n_active) {
+  __shared__ int sm[4];
+  int alive = 0;
+  for (int e = threadIdx.x; e < E; e += 256) {
+    int a = active[e];
+    if (a != 0) {
+      float r = ep_rew[e];
+      int n = ep_len[e];
+      const float* __restrict__ rw = rewards + (long)e * T;
+      const float* __restrict__ dn = dones + (long)e * T;
+      for (long t = 0; t < K && a != 0 && t0 + t < max_steps; ++t) {
+        r = __fadd_rn(r, rw[t]);
+        ++n;
+        if (dn[t] != 0.f) a = 0;
+      }
+      ep_rew[e] = r;
+      ep_len[e] = n;
+      if (a == 0) active[e] = 0;
+      alive += a != 0;
+    }
+  }
+  const int total = block_sum_256(alive, sm);
+  if (threadIdx.x == 0) *n_active = total;
+}
 }  // namespace
 
 extern "C" {
@@ -730,6 +760,16 @@ int a2c_rollout_post_frames(const float* rew, const float* done, const float* va
                      deltas, (long)T, (long)t, (long)slot0, gamma, pong, (const float*)nullptr, (const uint8_t*)nullptr, 0L,
                      (const float*)nullptr, (const float*)nullptr, 0L, (float*)nullptr, 0L, B, 0, 0, done_eff, h, hdim, h_rows,
                      (long)h_rows_stride, h_src ? h_src : h, nvalid_rows, nvalid_carry);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+int a2c_eval_scan(const float* rewards, const float* dones, int64_t T, int64_t K, int E, int64_t t0, int64_t max_steps,
+                  float* ep_rew, int32_t* ep_len, int32_t* active, int32_t* n_active, a2c_stream_t stream) {
+  if (!rewards || !dones || !ep_rew || !ep_len || !active || !n_active || E < 1 || K < 1 || T < K || t0 < 0 || max_steps < 1)
+    return A2C_ERR_ARG;
+  hipLaunchKernelGGL(eval_scan_kernel, dim3(1), dim3(256), 0, a2c_s(stream), rewards, dones, (long)T, (long)K, E, (long)t0,
+                     (long)max_steps, ep_rew, (int*)ep_len, (int*)active, (int*)n_active);
   A2C_CHECK_LAUNCH();
   return A2C_OK;
 }
