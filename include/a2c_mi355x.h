@@ -911,8 +911,8 @@ int a2c_snake_step(int32_t *state, const int64_t *actions, int64_t act_stride, i
  * frames not 16-byte aligned, frame_ld < 6400 or not a multiple of 4.  Env e of a launch is world env_id0 + e of `seed`:
  * draw i of a world is hash32(seed, env_id, i).  The state of one env is 16 int32 words: agent paddle y, opponent paddle
  * y, ball x, ball y, vx, vy, agent score, opponent score, draw counter, step counter, episode-step counter, reward since
- * the last done, 4 spare.  The kernels advance the counters in device memory: a captured launch plays new steps at each
- * replay.
+ * the last done, the action of the previous game frame (sticky actions, a2c_pong_step_skip; 0 without them), 3 spare.  The
+ * kernels advance the counters in device memory: a captured launch plays new steps at each replay.
  * a2c_pong_state_bytes: bytes of ONE env's state, 0 for an unsupported points_to_win.                                  */
 size_t a2c_pong_state_bytes(int points_to_win);
 /* starts B worlds (counters to 0, scores to 0, paddles centred, then the serve draw): state (B rows of 16 words) and
@@ -928,6 +928,20 @@ int a2c_pong_step(int32_t *state, const int64_t *actions, int64_t act_stride, in
                   uint32_t seed, int points_to_win, int max_episode_steps, int opp_skill_num, int opp_skill_den,
                   float *frames, int64_t frame_ld, float *rew, float *done, float *reset, int32_t *ep_count,
                   int32_t *ep_rew_sum, a2c_stream_t stream);
+/* a2c_pong_step with frame skip and sticky actions: one AGENT step is frame_skip game frames, each
+ * the step above.  With a = (action + action_shift) mod 3, game frame s = 0 .. frame_skip-1 runs x = a; when
+ * sticky_num > 0 one draw d is taken first (before the frame's opponent draw) and x = the action of the previous game
+ * frame (state word 12) if d mod sticky_den < sticky_num; word 12 = x; with sticky_num == 0 no draw is taken and word 12
+ * stays 0.  An episode end restarts the world, zeroes word 12 and DROPS the remaining frames.  rew = the sum over the
+ * frames run (|rew| <= 1: after a serve the ball needs at least 33 frames to reach a goal line), reset = the episode
+ * ended, done = reset or rew != 0, `frames` = the world as the last frame run left it (after an end: the reset frame).  The
+ * step and episode-step words, and max_episode_steps, count GAME frames; ep_count / ep_rew_sum count agent-step dones.
+ * (1, 0, 1) is a2c_pong_step itself.  A2C_ERR_ARG without a launch, besides what a2c_pong_step rejects: frame_skip outside
+ * 1..8, sticky_den outside 1..2^16, sticky_num outside 0..sticky_den.                                                    */
+int a2c_pong_step_skip(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                       uint32_t seed, int points_to_win, int max_episode_steps, int opp_skill_num, int opp_skill_den,
+                       float *frames, int64_t frame_ld, float *rew, float *done, float *reset, int32_t *ep_count,
+                       int32_t *ep_rew_sum, int frame_skip, int sticky_num, int sticky_den, a2c_stream_t stream);
 
 /* ------------------------------------------------------------------ Breakout worlds in device memory (csrc/breakout.hip)
  * The env of the reference's Breakout runs (preprocessing.py:19-23 breakout_prep: grey frames with more than two levels,
@@ -940,7 +954,8 @@ int a2c_pong_step(int32_t *state, const int64_t *actions, int64_t act_stride, in
  * rew / done / reset, frames not 16-byte aligned, frame_ld < 5760 or not a multiple of 4.  Env e of a launch is world
  * env_id0 + e of `seed`: draw i of a world is hash32(seed, env_id, i); the only draws are serves.  The state of one env is
  * 24 int32 words: paddle x, ball x, ball y, vx, vy, lives left, bricks left, draw counter, step counter, episode-step
- * counter, reward since the last done, the six brick rows' masks (bit c = brick column c alive, top row first), 7 spare.
+ * counter, reward since the last done, the six brick rows' masks (bit c = brick column c alive, top row first), the action
+ * of the previous game frame (sticky actions, a2c_breakout_step_skip; 0 without them), 6 spare.
  * The kernels advance the counters in device memory: a captured launch plays new steps at each replay.
  * a2c_breakout_state_bytes: bytes of ONE env's state, 0 for an unsupported lives.                                        */
 size_t a2c_breakout_state_bytes(int lives);
@@ -956,6 +971,14 @@ int a2c_breakout_reset(int32_t *state, int B, int env_id0, uint32_t seed, int li
 int a2c_breakout_step(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
                       uint32_t seed, int lives, int max_episode_steps, float *frames, int64_t frame_ld, float *rew,
                       float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, a2c_stream_t stream);
+/* a2c_breakout_step with frame skip and sticky actions, by the rules of a2c_pong_step_skip (the previous action is state
+ * word 17; the sticky draw comes before the frame): rew = the sum of the bricks' points over the frames run (several
+ * bricks may fall in one agent step), done == reset = the episode ended, which drops the remaining frames.  (1, 0, 1) is
+ * a2c_breakout_step itself.  A2C_ERR_ARG as there.                                                                        */
+int a2c_breakout_step_skip(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                           uint32_t seed, int lives, int max_episode_steps, float *frames, int64_t frame_ld, float *rew,
+                           float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, int frame_skip, int sticky_num,
+                           int sticky_den, a2c_stream_t stream);
 
 /* ------------------------------------------------------------------ world step + bookkeeping + frame stack in ONE launch
  * a2c_<world>_step_post(<the arguments of a2c_<world>_step>, post, stream) equals, on the same stream and in this order,
@@ -1003,6 +1026,17 @@ int a2c_breakout_step_post(int32_t *state, const int64_t *actions, int64_t act_s
                            uint32_t seed, int lives, int max_episode_steps, float *frames, int64_t frame_ld, float *rew,
                            float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_post *post,
                            a2c_stream_t stream);
+/* the same around a2c_<world>_step_skip: every wave recomputes the whole agent step, so the break at an episode end is
+ * uniform over the workgroup; the planes are copied and the frame is rendered once per agent step.                        */
+int a2c_pong_step_post_skip(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                            uint32_t seed, int points_to_win, int max_episode_steps, int opp_skill_num, int opp_skill_den,
+                            float *frames, int64_t frame_ld, float *rew, float *done, float *reset, int32_t *ep_count,
+                            int32_t *ep_rew_sum, int frame_skip, int sticky_num, int sticky_den, const a2c_world_post *post,
+                            a2c_stream_t stream);
+int a2c_breakout_step_post_skip(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B,
+                                int env_id0, uint32_t seed, int lives, int max_episode_steps, float *frames, int64_t frame_ld,
+                                float *rew, float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, int frame_skip,
+                                int sticky_num, int sticky_den, const a2c_world_post *post, a2c_stream_t stream);
 
 #ifdef __cplusplus
 }

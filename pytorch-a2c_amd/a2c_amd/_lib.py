@@ -210,11 +210,19 @@ SIGNATURES = {
                               P, P]),
     "a2c_pong_step_post": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, c_int, c_int, P, c_int64, P, P, P,
                                    P, P, PW, P]),
+    "a2c_pong_step_skip": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, c_int, c_int, P, c_int64, P, P, P,
+                                   P, P, c_int, c_int, c_int, P]),
+    "a2c_pong_step_post_skip": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, c_int, c_int, P, c_int64, P,
+                                        P, P, P, P, c_int, c_int, c_int, PW, P]),
     "a2c_breakout_state_bytes": (c_size_t, [c_int]),
     "a2c_breakout_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P]),
     "a2c_breakout_step": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P, P, P]),
     "a2c_breakout_step_post": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P, P, PW,
                                        P]),
+    "a2c_breakout_step_skip": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P, P,
+                                       c_int, c_int, c_int, P]),
+    "a2c_breakout_step_post_skip": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P,
+                                            P, c_int, c_int, c_int, PW, P]),
 }
 
 _lib = None

@@ -32,9 +32,20 @@ One step, in this order (every division below is between non-negative ints):
      vx = +1 if (d >> 8) & 1 else -1.
 A reset restores all 108 bricks and ``lives`` lives, zeroes the episode-step counter, puts the paddle at px = 32 and
 serves with one draw.  Randomness is counter based: draw i of env e is ``hash32(seed, e, i)``, the mixing function of the
-Snake and Pong worlds; the only draws are serves."""
+Snake and Pong worlds; the only draws are serves.
+
+Frame skip and sticky actions (``frame_skip`` 1..8, ``sticky_num`` / ``sticky_den`` with the bounds of
+Pong's ``opp_skill_*``): the step above is one GAME FRAME, and one AGENT step -- ``step(a)`` / ``advance(a)``, one launch
+of a2c_breakout_step_skip -- is ``frame_skip`` of them with the same requested action ``a``.  Game frame s = 0 .. k-1:
+x = a; when ``sticky_num > 0`` one draw ``d`` is taken BEFORE the frame and x = ``prev`` (the action the previous game
+frame executed, state word 17) if ``d mod sticky_den < sticky_num``; prev = x; the frame runs with x and its reward is
+added to the agent step's (several bricks may fall in one agent step).  A frame that ends the episode zeroes ``prev``
+and the remaining frames are DROPPED (``events["cut"]``).  ``steps``, ``ep_steps`` and ``max_episode_steps`` count game
+frames.  With ``sticky_num == 0`` no draw is taken and ``prev`` stays 0: k = 1 is the world above word for word, k > 1 is
+that world stepped k times with one action and cut at the done."""
 import numpy as np
 
+from .pong import check_repeat
 from .snake import _env_id0, hash32
 
 N_ACTIONS = 4
@@ -54,7 +65,9 @@ SERVE_Y, SERVE_X0, SERVE_SPAN = 40, 8, 56
 HIT_VX = (-2, -2, -1, -1, 0, 1, 1, 2, 2)                         # by off = ball x + 1 - paddle x; 0: keep the sign, |vx| = 1
 MAX_LIVES, MAX_EPISODE_STEPS = 5, 1 << 24
 STATE_WORDS = 24
-# the kernel's word layout (csrc/breakout.hip): words 11..16 are the brick rows' 18-bit masks, 17..23 spare
+# the kernel's word layout (csrc/breakout.hip): words 11..16 are the brick rows' 18-bit masks, 17 the action of the previous
+# game frame (PREV_WORD; 0 without sticky actions), 18..23 spare
+PREV_WORD = 17
 WORD_NAMES = ("paddle_x", "ball_x", "ball_y", "vx", "vy", "lives_left", "bricks_left", "draws", "steps", "ep_steps", "ep_rew")
 # raw frames (ALE's layout): the field is rows 35..194, columns 8..151 at 2 x scale
 RAW_H, RAW_W, RAW_TOP, RAW_LEFT, WALL_TOP = 210, 160, 35, 8, 17
@@ -62,9 +75,16 @@ WALL_RGB, OBJECT_RGB = (142, 142, 142), (200, 72, 72)
 _M = 0xFFFFFFFF
 
 
-def check_world(lives=5, max_episode_steps=10000):
-    """the bounds a2c_breakout_step enforces (A2C_ERR_ARG): same ones for the host twin"""
+def repeat_from_hyps(hyps):
+    """(frame_skip, sticky_num, sticky_den) from the hyps (1, 0, 1 where absent); ValueError outside the bounds"""
+    from .pong import repeat_from_hyps as from_hyps
+    return from_hyps(hyps, "Breakout")
+
+
+def check_world(lives=5, max_episode_steps=10000, frame_skip=1, sticky_num=0, sticky_den=1):
+    """the bounds a2c_breakout_step / a2c_breakout_step_skip enforce (A2C_ERR_ARG): same ones for the host twin"""
     n, m = int(lives), int(max_episode_steps)
+    check_repeat(frame_skip, sticky_num, sticky_den, "Breakout")
     if not (1 <= n <= MAX_LIVES and 1 <= m <= MAX_EPISODE_STEPS):
         raise ValueError(f"Breakout: unsupported world lives={n} max_episode_steps={m} (1 <= lives <= {MAX_LIVES}, "
                          f"1 <= max_episode_steps <= {MAX_EPISODE_STEPS})")
@@ -95,11 +115,15 @@ class BreakoutEnv:
     """One Breakout world on the host.  ``reset()`` -> raw (210, 160, 3) uint8 frame; ``step(a)`` -> (frame, reward, done,
     info) with the REAL done (no life left, no brick left, or the step limit).  Like a gym env it does not reset itself:
     the caller does -- the Runner does, which yields exactly what the device world returns.  ``events`` counts what
-    happened for tests that must see every rule at work."""
+    happened (with frame skip or sticky actions also ``cut``: episode ends that dropped game frames of their agent step, and
+    ``sticky``: game frames that kept an action other than the requested one) for tests that must see every rule at work.  ``step`` / ``advance`` are the AGENT
+    step: ``frame_skip`` game frames (module docstring)."""
     action_space = _ActionSpace()
 
-    def __init__(self, seed=0, env_id=0, lives=5, max_episode_steps=10000):
+    def __init__(self, seed=0, env_id=0, lives=5, max_episode_steps=10000, frame_skip=1, sticky_num=0, sticky_den=1):
         self.lives, self.max_episode_steps = check_world(lives, max_episode_steps)
+        self.frame_skip, self.sticky_num, self.sticky_den = check_repeat(frame_skip, sticky_num, sticky_den, "Breakout")
+        self.prev = 0
         self.seed_, self.env_id = int(seed) & _M, int(env_id)
         self.paddle_x = PADDLE_START_X
         self.ball_x, self.ball_y, self.vx, self.vy = SERVE_X0, SERVE_Y, 1, -1
@@ -107,6 +131,8 @@ class BreakoutEnv:
         self.draws = self.steps = self.ep_steps = self.ep_rew = 0
         self.over = True
         self.events = dict(side_wall=0, ceiling=0, brick=0, speed_up=0, paddle_hit=0, life_lost=0, cleared=0, episode_end=0)
+        if (self.frame_skip, self.sticky_num) != (1, 0):      # a plain world can neither cut nor keep an action
+            self.events.update(cut=0, sticky=0)
 
     def seed(self, seed):
         self.seed_ = int(seed) & _M
@@ -125,7 +151,7 @@ class BreakoutEnv:
     def new_episode(self):
         """the reset without its frame"""
         self.rows, self.bricks_left, self.lives_left = [FULL_ROW] * BRICK_ROWS, N_BRICKS, self.lives
-        self.ep_steps = self.ep_rew = 0
+        self.ep_steps = self.ep_rew = self.prev = 0
         self.paddle_x = PADDLE_START_X
         self._serve()
         self.over = False
@@ -135,10 +161,31 @@ class BreakoutEnv:
         return self.render_rgb(), rew, done, {}
 
     def advance(self, action):
-        """the step without its frame -> (reward, done)"""
+        """the agent step without its frame: ``frame_skip`` game frames -> (summed reward, done)"""
         if self.over:
             raise RuntimeError("BreakoutEnv.step() after done: call reset()")
         a = int(action) % 4
+        total, done = 0.0, False
+        for s in range(self.frame_skip):
+            x = a
+            if self.sticky_num > 0:
+                d = hash32(self.seed_, self.env_id, self.draws)
+                self.draws = (self.draws + 1) & _M
+                if d % self.sticky_den < self.sticky_num:
+                    x = self.prev
+                    self.events["sticky"] += x != a
+                self.prev = x
+            rew, done = self._frame(x)
+            total += rew
+            if done:
+                self.prev = 0
+                if s < self.frame_skip - 1:
+                    self.events["cut"] += 1
+                break
+        return total, done
+
+    def _frame(self, a):
+        """one game frame with action ``a`` in 0..3 -> (reward, done)"""
         self.steps += 1
         self.ep_steps += 1
         # 1. the paddle
@@ -231,6 +278,7 @@ class BreakoutEnv:
         w = np.zeros(STATE_WORDS, dtype=np.int32)
         w[:len(WORD_NAMES)] = [_i32(int(getattr(self, k))) for k in WORD_NAMES]
         w[len(WORD_NAMES):len(WORD_NAMES) + BRICK_ROWS] = self.rows
+        w[PREV_WORD] = self.prev
         return w
 
     def load_state_words(self, words):
@@ -239,6 +287,7 @@ class BreakoutEnv:
         for k, v in zip(WORD_NAMES, w):
             setattr(self, k, v & _M if k == "draws" else v)
         self.rows = [v & FULL_ROW for v in w[len(WORD_NAMES):len(WORD_NAMES) + BRICK_ROWS]]
+        self.prev = w[PREV_WORD]
         self.over = False
 
 
@@ -254,15 +303,19 @@ class BreakoutFactory:
 
 class DeviceBreakoutPool:
     """``n_envs`` Breakout worlds in device memory (the Runner's device-pool protocol).  Env j is the world
-    ``BreakoutEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames.  ``device_step`` returns ``done`` and ``reset`` as two
+    ``BreakoutEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames; with ``frame_skip`` / ``sticky_num`` /
+    ``sticky_den`` other than (1, 0, .) a step is an agent step of a2c_breakout_step_skip.  ``device_step`` returns ``done`` and ``reset`` as two
     tensors holding the same values, the real done.  ``episode_stats`` counts the finished episodes and sums their rewards."""
     needs_actions = True
     frame_shape = (1, H, W)
 
-    def __init__(self, n_envs, device="cuda", seed=0, lives=5, max_episode_steps=10000, env_id0=0):
+    def __init__(self, n_envs, device="cuda", seed=0, lives=5, max_episode_steps=10000, env_id0=0, frame_skip=1, sticky_num=0,
+                 sticky_den=1):
         import torch
         from . import ops
         self.world = check_world(lives, max_episode_steps)
+        self.repeat = check_repeat(frame_skip, sticky_num, sticky_den, "Breakout")
+        self.plain = self.repeat[:2] == (1, 0)      # today's world: the entry points without frame skip
         self.B, self.seed, self.device = int(n_envs), int(seed) & _M, torch.device(device)
         if self.B < 1:
             raise ValueError("DeviceBreakoutPool: n_envs >= 1")
@@ -307,9 +360,14 @@ class DeviceBreakoutPool:
         if env0 < 0 or B < 1 or env0 + B > self.B:
             raise ValueError("DeviceBreakoutPool: env range outside the pool")
         sl = slice(env0, env0 + B)
-        ops.breakout_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
-                          self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl],
-                          self.ep_stats[0:1], self.ep_stats[1:2])
+        if self.plain:
+            ops.breakout_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
+                              self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl],
+                              self.reset_mask[sl], self.ep_stats[0:1], self.ep_stats[1:2])
+        else:
+            ops.breakout_step_skip(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
+                                   self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl],
+                                   self.reset_mask[sl], *self.repeat, self.ep_stats[0:1], self.ep_stats[1:2])
         return self.frames[sl], self.rew[sl], self.done[sl], self.reset_mask[sl]
 
     def device_step(self, t, env0, B, actions=None):
@@ -327,9 +385,15 @@ class DeviceBreakoutPool:
         if env0 < 0 or B < 1 or env0 + B > self.B:
             raise ValueError("DeviceBreakoutPool: env range outside the pool")
         sl = slice(env0, env0 + B)
-        ops.breakout_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
-                               self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl],
-                               self.done[sl], self.reset_mask[sl], post, self.ep_stats[0:1], self.ep_stats[1:2])
+        if self.plain:
+            ops.breakout_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
+                                   self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl],
+                                   self.done[sl], self.reset_mask[sl], post, self.ep_stats[0:1], self.ep_stats[1:2])
+        else:
+            ops.breakout_step_post_skip(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
+                                        self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl],
+                                        self.done[sl], self.reset_mask[sl], *self.repeat, post, self.ep_stats[0:1],
+                                        self.ep_stats[1:2])
         return self.rew[sl], self.done[sl], self.reset_mask[sl]
 
     def episode_stats(self):

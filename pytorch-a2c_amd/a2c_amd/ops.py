@@ -1281,6 +1281,19 @@ def pong_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, po
                               _p(reset), _p(ep_count), _p(ep_rew_sum), _st(st)), "a2c_pong_step")
 
 
+def pong_step_skip(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win, max_episode_steps,
+                   opp_skill_num, opp_skill_den, frames, frame_ld, rew, done, reset, frame_skip, sticky_num, sticky_den,
+                   ep_count=None, ep_rew_sum=None, st=None):
+    """pong_step over ``frame_skip`` game frames, each keeping the previous frame's action with probability ``sticky_num`` /
+    ``sticky_den``; (1, 0, 1) is pong_step"""
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
+    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    check(lib().a2c_pong_step_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
+                                   max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew), _p(done),
+                                   _p(reset), _p(ep_count), _p(ep_rew_sum), frame_skip, sticky_num, sticky_den, _st(st)),
+          "a2c_pong_step_skip")
+
+
 # ---------------------------------------------------------------- Breakout worlds in device memory (csrc/breakout.hip)
 def breakout_state_bytes(lives=5):
     """bytes of one env's state; raises for a world the kernels do not support"""
@@ -1304,6 +1317,17 @@ def breakout_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed
     check(lib().a2c_breakout_step(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
                                   max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
                                   _p(ep_rew_sum), _st(st)), "a2c_breakout_step")
+
+
+def breakout_step_skip(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames,
+                       frame_ld, rew, done, reset, frame_skip, sticky_num, sticky_den, ep_count=None, ep_rew_sum=None, st=None):
+    """breakout_step over ``frame_skip`` game frames, each keeping the previous frame's action with probability
+    ``sticky_num`` / ``sticky_den``; (1, 0, 1) is breakout_step"""
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
+    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    check(lib().a2c_breakout_step_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
+                                       max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
+                                       _p(ep_rew_sum), frame_skip, sticky_num, sticky_den, _st(st)), "a2c_breakout_step_skip")
 
 
 # ---------------------------------------------------------------- world step + bookkeeping + frame stack in one launch
@@ -1354,3 +1378,27 @@ def breakout_step_post(state, actions_ptr, act_stride, action_shift, B, env_id0,
     check(lib().a2c_breakout_step_post(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
                                              max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset),
                                              _p(ep_count), _p(ep_rew_sum), _post_ref(post), _st(st)), "a2c_breakout_step_post")
+
+
+def pong_step_post_skip(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win, max_episode_steps,
+                        opp_skill_num, opp_skill_den, frames, frame_ld, rew, done, reset, frame_skip, sticky_num, sticky_den,
+                        post, ep_count=None, ep_rew_sum=None, st=None):
+    """pong_step_skip + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
+    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    check(lib().a2c_pong_step_post_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
+                                        max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew),
+                                        _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum), frame_skip, sticky_num, sticky_den,
+                                        _post_ref(post), _st(st)), "a2c_pong_step_post_skip")
+
+
+def breakout_step_post_skip(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames,
+                            frame_ld, rew, done, reset, frame_skip, sticky_num, sticky_den, post, ep_count=None,
+                            ep_rew_sum=None, st=None):
+    """breakout_step_skip + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
+    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    check(lib().a2c_breakout_step_post_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
+                                            max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset),
+                                            _p(ep_count), _p(ep_rew_sum), frame_skip, sticky_num, sticky_den, _post_ref(post),
+                                            _st(st)), "a2c_breakout_step_post_skip")

@@ -26,7 +26,18 @@ One step, in this order (every division below is between non-negative ints):
      towards the side that lost the point.
 A reset zeroes scores and the episode-step counter, centres both paddles (y = 36) and serves with one draw: direction
 from ``d & 1`` (1: towards the agent), vy as above.  Randomness is counter based: draw i of env e is
-``hash32(seed, e, i)``, the mixing function of the Snake worlds."""
+``hash32(seed, e, i)``, the mixing function of the Snake worlds.
+
+Frame skip and sticky actions (``frame_skip`` 1..8, ``sticky_num`` / ``sticky_den`` with the bounds of
+``opp_skill_*``): the step above is one GAME FRAME, and one AGENT step -- ``step(a)`` / ``advance(a)``, one launch of
+a2c_pong_step_skip -- is ``frame_skip`` of them with the same requested action ``a``.  Game frame s = 0 .. k-1: x = a; when
+``sticky_num > 0`` one draw ``d`` is taken BEFORE the frame's own draws and x = ``prev`` (the action the previous game frame
+executed) if ``d mod sticky_den < sticky_num``; prev = x; the frame runs with x and its reward is added to the agent
+step's.  A frame that ends the episode zeroes ``prev`` and the remaining frames are DROPPED (``events["cut"]``).  The
+agent step's done is the real done; the "Pong" done is that or a non-zero summed reward.  At most one point falls in an
+agent step (after a serve the ball needs at least 33 frames to reach a goal line, and k <= 8).  ``steps``, ``ep_steps`` and
+``max_episode_steps`` count game frames.  With ``sticky_num == 0`` no draw is taken and ``prev`` stays 0: k = 1 is the world
+above word for word, k > 1 is that world stepped k times with one action and cut at the real done."""
 import numpy as np
 
 from .snake import _env_id0, hash32
@@ -42,6 +53,7 @@ HIT_VY = (-2, -2, -1, -1, 0, 1, 1, 2, 2)         # by off = ball y + 1 - paddle 
 HIT_SPEED = (2, 2, 1, 1, 1, 1, 1, 2, 2)          # |vx| after the hit
 MISS_RIGHT, MISS_LEFT = AGENT_X + PADDLE_W, OPP_X - BALL      # ball x >= 72: agent missed; ball x <= 6: opponent missed
 MAX_POINTS, MAX_EPISODE_STEPS, MAX_SKILL_DEN = 21, 1 << 24, 1 << 16
+MAX_FRAME_SKIP, MAX_STICKY_DEN = 8, 1 << 16
 # raw frames (ALE's layout): the playfield is rows 35..194 at 2 x scale; channel 0 of the two background colours is what
 # pong_prep removes
 RAW_H, RAW_W, RAW_TOP = 210, 160, 35
@@ -50,9 +62,27 @@ OPP_RGB, AGENT_RGB, BALL_RGB = (213, 130, 74), (92, 186, 92), (236, 236, 236)
 _M = 0xFFFFFFFF
 
 
-def check_world(points_to_win=21, max_episode_steps=10000, opp_skill_num=3, opp_skill_den=4):
-    """the bounds a2c_pong_step enforces (A2C_ERR_ARG): same ones for the host twin"""
+def check_repeat(frame_skip=1, sticky_num=0, sticky_den=1, what="Pong"):
+    """the bounds a2c_<world>_step_skip enforces (A2C_ERR_ARG) on frame skip and sticky actions: same ones for the host
+    twins -> (frame_skip, sticky_num, sticky_den)"""
+    k, n, d = int(frame_skip), int(sticky_num), int(sticky_den)
+    if not (1 <= k <= MAX_FRAME_SKIP and 1 <= d <= MAX_STICKY_DEN and 0 <= n <= d):
+        raise ValueError(f"{what}: unsupported frame_skip={k} sticky={n}/{d} (1 <= frame_skip <= {MAX_FRAME_SKIP}, "
+                         f"1 <= sticky_den <= {MAX_STICKY_DEN}, 0 <= sticky_num <= sticky_den)")
+    return k, n, d
+
+
+def repeat_from_hyps(hyps, what="Pong"):
+    """(frame_skip, sticky_num, sticky_den) from the hyps (1, 0, 1 where absent); ValueError outside the bounds"""
+    get = lambda k, dflt: dflt if hyps.get(k) is None else hyps[k]
+    return check_repeat(get("frame_skip", 1), get("sticky_num", 0), get("sticky_den", 1), what)
+
+
+def check_world(points_to_win=21, max_episode_steps=10000, opp_skill_num=3, opp_skill_den=4, frame_skip=1, sticky_num=0,
+                sticky_den=1):
+    """the bounds a2c_pong_step / a2c_pong_step_skip enforce (A2C_ERR_ARG): same ones for the host twin"""
     p, m, n, d = int(points_to_win), int(max_episode_steps), int(opp_skill_num), int(opp_skill_den)
+    check_repeat(frame_skip, sticky_num, sticky_den)
     if not (1 <= p <= MAX_POINTS and 1 <= m <= MAX_EPISODE_STEPS and 1 <= d <= MAX_SKILL_DEN and 0 <= n <= d):
         raise ValueError(f"Pong: unsupported world points_to_win={p} max_episode_steps={m} opp_skill={n}/{d} (1 <= "
                          f"points_to_win <= {MAX_POINTS}, 1 <= max_episode_steps <= {MAX_EPISODE_STEPS}, 1 <= opp_skill_den "
@@ -79,12 +109,17 @@ class PongEnv:
     """One Pong world on the host.  ``reset()`` -> raw (210, 160, 3) uint8 frame; ``step(a)`` -> (frame, reward, done,
     info) with the REAL done (a score at ``points_to_win``, or the step limit).  Like a gym env it does not reset itself:
     the caller does -- the Runner does, which yields exactly what the device world returns.  ``events`` counts what
-    happened (wall bounces, paddle hits, points, episode ends) for tests that must see every rule at work."""
+    happened (wall bounces, paddle hits, points, episode ends; with frame skip or sticky actions also ``cut``: episode ends
+    that dropped game frames of their agent step, and ``sticky``: game frames that kept an action other than the requested one) for tests that must see every
+    rule at work.  ``step`` / ``advance`` are the AGENT step: ``frame_skip`` game frames (module docstring)."""
     action_space = _ActionSpace()
 
-    def __init__(self, seed=0, env_id=0, points_to_win=21, max_episode_steps=10000, opp_skill_num=3, opp_skill_den=4):
+    def __init__(self, seed=0, env_id=0, points_to_win=21, max_episode_steps=10000, opp_skill_num=3, opp_skill_den=4,
+                 frame_skip=1, sticky_num=0, sticky_den=1):
         self.points_to_win, self.max_episode_steps, self.skill_num, self.skill_den = check_world(
             points_to_win, max_episode_steps, opp_skill_num, opp_skill_den)
+        self.frame_skip, self.sticky_num, self.sticky_den = check_repeat(frame_skip, sticky_num, sticky_den)
+        self.prev = 0
         self.seed_, self.env_id = int(seed) & _M, int(env_id)
         self.agent_y = self.opp_y = PADDLE_START_Y
         self.ball_x, self.ball_y, self.vx, self.vy = SERVE_X, SERVE_Y, 1, 0
@@ -92,6 +127,8 @@ class PongEnv:
         self.draws = self.steps = self.ep_steps = 0
         self.over = True
         self.events = dict(wall=0, hit_agent=0, hit_opp=0, agent_point=0, opp_point=0, episode_end=0)
+        if (self.frame_skip, self.sticky_num) != (1, 0):      # a plain world can neither cut nor keep an action
+            self.events.update(cut=0, sticky=0)
 
     def seed(self, seed):
         self.seed_ = int(seed) & _M
@@ -113,7 +150,7 @@ class PongEnv:
     def new_episode(self):
         """the reset without its frame"""
         self.agent_y = self.opp_y = PADDLE_START_Y
-        self.score_agent = self.score_opp = self.ep_steps = 0
+        self.score_agent = self.score_opp = self.ep_steps = self.prev = 0
         d = self._draw()
         self._serve(d, bool(d & 1))
         self.over = False
@@ -123,10 +160,30 @@ class PongEnv:
         return self.render_rgb(), rew, done, {}
 
     def advance(self, action):
-        """the step without its frame -> (reward, done)"""
+        """the agent step without its frame: ``frame_skip`` game frames -> (summed reward, done)"""
         if self.over:
             raise RuntimeError("PongEnv.step() after done: call reset()")
         a = int(action) % 3
+        total, done = 0.0, False
+        for s in range(self.frame_skip):
+            x = a
+            if self.sticky_num > 0:
+                if self._draw() % self.sticky_den < self.sticky_num:
+                    x = self.prev
+                    self.events["sticky"] += x != a
+                self.prev = x
+            rew, done = self._frame(x)
+            total += rew
+            if done:
+                self.prev = 0
+                if s < self.frame_skip - 1:
+                    self.events["cut"] += 1
+                break
+        assert abs(total) <= 1, "more than one point in one agent step"
+        return total, done
+
+    def _frame(self, a):
+        """one game frame with action ``a`` in 0..2 -> (reward, done)"""
         self.steps += 1
         self.ep_steps += 1
         # 1. the agent's paddle
@@ -212,17 +269,20 @@ class PongFactory:
 
 class DevicePongPool:
     """``n_envs`` Pong worlds in device memory (the Runner's device-pool protocol).  Env j is the world
-    ``PongEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames.  ``device_step`` returns ``done = (rew != 0) or real
+    ``PongEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames; with ``frame_skip`` / ``sticky_num`` / ``sticky_den``
+    other than (1, 0, .) a step is an agent step of a2c_pong_step_skip.  ``device_step`` returns ``done = (rew != 0) or real
     done`` (the Pong override of the reference's runner) and ``reset = real done`` as two tensors.  ``episode_stats``
     counts what the Runner's ``rew_q`` counts for a "Pong" env type: every ``done``, with the reward since the last one."""
     needs_actions = True
     frame_shape = (1, H, W)
 
     def __init__(self, n_envs, device="cuda", seed=0, points_to_win=21, max_episode_steps=10000, opp_skill_num=3,
-                 opp_skill_den=4, env_id0=0):
+                 opp_skill_den=4, env_id0=0, frame_skip=1, sticky_num=0, sticky_den=1):
         import torch
         from . import ops
         self.world = check_world(points_to_win, max_episode_steps, opp_skill_num, opp_skill_den)
+        self.repeat = check_repeat(frame_skip, sticky_num, sticky_den)
+        self.plain = self.repeat[:2] == (1, 0)      # today's world: the entry points without frame skip
         self.B, self.seed, self.device = int(n_envs), int(seed) & _M, torch.device(device)
         if self.B < 1:
             raise ValueError("DevicePongPool: n_envs >= 1")
@@ -267,9 +327,14 @@ class DevicePongPool:
         if env0 < 0 or B < 1 or env0 + B > self.B:
             raise ValueError("DevicePongPool: env range outside the pool")
         sl = slice(env0, env0 + B)
-        ops.pong_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
-                      self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl],
-                      self.ep_stats[0:1], self.ep_stats[1:2])
+        if self.plain:
+            ops.pong_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
+                          self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl],
+                          self.ep_stats[0:1], self.ep_stats[1:2])
+        else:
+            ops.pong_step_skip(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
+                               self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl],
+                               self.reset_mask[sl], *self.repeat, self.ep_stats[0:1], self.ep_stats[1:2])
         return self.frames[sl], self.rew[sl], self.done[sl], self.reset_mask[sl]
 
     def device_step(self, t, env0, B, actions=None):
@@ -287,9 +352,15 @@ class DevicePongPool:
         if env0 < 0 or B < 1 or env0 + B > self.B:
             raise ValueError("DevicePongPool: env range outside the pool")
         sl = slice(env0, env0 + B)
-        ops.pong_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
-                           self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl], self.done[sl],
-                           self.reset_mask[sl], post, self.ep_stats[0:1], self.ep_stats[1:2])
+        if self.plain:
+            ops.pong_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
+                               self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl],
+                               self.done[sl], self.reset_mask[sl], post, self.ep_stats[0:1], self.ep_stats[1:2])
+        else:
+            ops.pong_step_post_skip(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
+                                    self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl],
+                                    self.done[sl], self.reset_mask[sl], *self.repeat, post, self.ep_stats[0:1],
+                                    self.ep_stats[1:2])
         return self.rew[sl], self.done[sl], self.reset_mask[sl]
 
     def episode_stats(self):

@@ -1422,7 +1422,8 @@ class DeviceStatsRunner:
     32) lock-step steps with the launches of the training path (a chunk is one slot graph: first chunk of a call eager, second
     captured, later ones replayed), a2c_eval_scan closes every env at its first done out of the chunk's rewards / dones rows,
     and ONE 4-byte read per chunk tells the host whether an env is still playing.  ``hyps['max_eval_steps']`` (default 10**6)
-    caps the episode; the cap may fall inside a chunk.
+    caps the episode; the cap may fall inside a chunk.  A step here is an AGENT step of the pool: on worlds with
+    ``frame_skip`` = k > 1 ``last["ep_len"]`` and ``max_eval_steps`` count agent steps, up to k game frames each.
 
     Every call plays fresh, reproducible worlds: call c re-bases the pool to env ids 10007 + c*E .. (the first call: the
     ids of ``train()``'s host twins).  The world kernels take the env id as a launch argument, so a re-based pool needs its

@@ -70,7 +70,9 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     gym: the first plays ``n_envs`` worlds in device memory (``DeviceSnakePool``), the second ``SnakeEnv``s behind the usual
     ``env_pool`` choices with ``prep_fxn="snake_prep"``; both are evaluated on host ``SnakeEnv``s.
     ``env_type`` "Pong-device" / "Pong-host" (a2c_amd/pong.py; keys ``points_to_win``, ``max_episode_steps``,
-    ``opp_skill_num``, ``opp_skill_den``) likewise: ``DevicePongPool``, or ``PongEnv``s behind the usual pools with
+    ``opp_skill_num``, ``opp_skill_den``; ``frame_skip``, ``sticky_num``, ``sticky_den``: game frames per step and sticky
+    actions, DESIGN.md section 6g, for the Pong and Breakout worlds, training pools and evaluation worlds alike)
+    likewise: ``DevicePongPool``, or ``PongEnv``s behind the usual pools with
     ``prep_fxn="pong_prep"`` (the process pool carries their {0, 1} frames packed, one bit per pixel); 3 actions,
     ``action_shift`` 0 unless given, the "Pong" done override applies, evaluation on host ``PongEnv``s.
     ``env_type`` "Breakout-device" / "Breakout-host" (a2c_amd/breakout.py; keys ``lives``, ``max_episode_steps``) likewise:
@@ -90,6 +92,11 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
             "Snake-device", "Pong-device", "Breakout-device")):
         raise ValueError("a2c_amd: hyps['eval_pool'] = 'device' evaluates the device worlds (env_type 'Snake-device', "
                          "'Pong-device' or 'Breakout-device') and takes no eval_env / env_fn")
+    if env_fn is None and hyps.get("env_type") in ("Snake-device", "Snake-host"):
+        from .pong import repeat_from_hyps
+        if repeat_from_hyps(hyps, "Snake")[:2] != (1, 0):
+            raise ValueError("a2c_amd: frame_skip / sticky_num are keys of the Pong and Breakout worlds: the Snake worlds "
+                             "play one game frame per step")
     if hyps["n_rollouts"] is None:
         hyps["n_rollouts"] = hyps["n_envs"]
     hyps["main_path"] = try_key(hyps, "main_path", "./")
@@ -137,6 +144,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
         hyps["max_eval_steps"] = try_key(hyps, "max_eval_steps", 2000)
         world = dict(zip(("points_to_win", "max_episode_steps", "opp_skill_num", "opp_skill_den"), pong_world),
                      seed=hyps["seed"])
+        world.update(zip(("frame_skip", "sticky_num", "sticky_den"), pong.repeat_from_hyps(hyps)))
         mk_env = lambda j: SequentialEnvironment(hyps["env_type"], preprocessing.pong_prep, seed=hyps["seed"],
                                                  env_fn=pong.PongFactory(env_id=j, **world))
         if hyps["env_type"] == "Pong-device":
@@ -164,6 +172,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
         hyps["is_discrete"], n_act = True, breakout.N_ACTIONS
         hyps["max_eval_steps"] = try_key(hyps, "max_eval_steps", 2000)
         world = dict(zip(("lives", "max_episode_steps"), breakout_world), seed=hyps["seed"])
+        world.update(zip(("frame_skip", "sticky_num", "sticky_den"), breakout.repeat_from_hyps(hyps)))
         mk_env = lambda j: SequentialEnvironment(hyps["env_type"], preprocessing.breakout_prep, seed=hyps["seed"],
                                                  env_fn=breakout.BreakoutFactory(env_id=j, **world))
         if hyps["env_type"] == "Breakout-device":

@@ -1,8 +1,9 @@
-// Breakout worlds in device memory: a2c_breakout_reset / a2c_breakout_step / a2c_breakout_step_post (rules: DESIGN.md section 6d; host twin:
-// a2c_amd/breakout.py).
+// Breakout worlds in device memory: a2c_breakout_reset / a2c_breakout_step / a2c_breakout_step_post and their _skip forms
+// (rules: DESIGN.md sections 6d and 6g; host twin: a2c_amd/breakout.py).
 //
-// One wavefront per env.  The state of an env is BRK_WORDS int32 words in HBM; a step is a short, loop-free, wave-uniform
-// integer computation (every lane computes the same values from the same words), after which lanes 0..BRK_WORDS-1 store
+// One wavefront per env.  The state of an env is BRK_WORDS int32 words in HBM; an agent step is frame_skip (1..8) game
+// frames, each a short, loop-free, wave-uniform integer computation (every lane computes the same values from the same
+// words; the loop over the frames and its break at an episode end are wave-uniform too), after which lanes 0..BRK_WORDS-1 store
 // one word each and all 64 lanes render the 80 x 72 prepped frame row (the grey levels breakout_prep hands on, as floats)
 // as 16-byte stores where the frame-stack kernels read it.  72 / 4 = 18 = the number of brick columns, so a 16-byte store
 // lies in one brick column of one row: its brick test is one shift of one row mask.  The draw, step and episode-step
@@ -13,7 +14,8 @@
 namespace {
 
 constexpr int BRK_WORDS = 24;       // paddle x, ball x, ball y, vx, vy, lives, bricks left, draws, steps, episode steps,
-                                    // reward since the last done, the 6 brick rows' 18-bit masks, 7 spare
+                                    // reward since the last done, the 6 brick rows' 18-bit masks, the action of the
+                                    // previous game frame (sticky actions; 0 without them), 6 spare
 constexpr int BW = 72, BH = 80, BRK_HW = BW * BH;
 constexpr int BRICK_ROWS = 6, BRICK_COLS = 18, BRICK_W = 4, BRICK_H = 3, BRICK_TOP = 11;
 constexpr int BRICK_BOTTOM = BRICK_TOP + BRICK_ROWS * BRICK_H;
@@ -22,6 +24,7 @@ constexpr int PADDLE_W = 8, PADDLE_H = 2, PADDLE_Y = 77, PADDLE_SPEED = 3, PADDL
 constexpr int BALL = 2, BALL_MAX_X = BW - BALL, LOST_Y = 78;
 constexpr int SERVE_Y = 40, SERVE_X0 = 8, SERVE_SPAN = 56;
 constexpr int MAX_LIVES = 5, MAX_EPISODE_STEPS = 1 << 24;
+constexpr int MAX_FRAME_SKIP = 8, MAX_STICKY_DEN = 1 << 16;
 constexpr float LEVEL = 200.0f;     // the paddle and the ball
 
 static_assert(BW == BRICK_COLS * BRICK_W && BRICK_W == 4, "one 16-byte store per brick column");
@@ -91,12 +94,12 @@ __device__ __forceinline__ void brk_write_frame(const BrkWorld& w, float* __rest
 // the counters of an env beside its world
 struct BrkCount {
   uint32_t draws;
-  int steps, ep_steps, ep_rew;
+  int steps, ep_steps, ep_rew, prev;
 };
 
 __device__ __forceinline__ void brk_load(const int32_t* st, BrkWorld& w, BrkCount& c) {
   w.px = st[0]; w.bx = st[1]; w.by = st[2]; w.vx = st[3]; w.vy = st[4]; w.lives = st[5]; w.left = st[6];
-  c.draws = (uint32_t)st[7]; c.steps = st[8]; c.ep_steps = st[9]; c.ep_rew = st[10];
+  c.draws = (uint32_t)st[7]; c.steps = st[8]; c.ep_steps = st[9]; c.ep_rew = st[10]; c.prev = st[11 + BRICK_ROWS];
 #pragma unroll
   for (int r = 0; r < BRICK_ROWS; ++r) w.rows[r] = st[11 + r] & FULL_ROW;
 }
@@ -105,7 +108,8 @@ __device__ __forceinline__ void brk_store(int32_t* st, const BrkWorld& w, const 
   if (lane < BRK_WORDS) {
     const int hv = lane == 0 ? w.px : lane == 1 ? w.bx : lane == 2 ? w.by : lane == 3 ? w.vx : lane == 4 ? w.vy
                  : lane == 5 ? w.lives : lane == 6 ? w.left : lane == 7 ? (int)c.draws : lane == 8 ? c.steps
-                 : lane == 9 ? c.ep_steps : lane == 10 ? c.ep_rew : lane < 11 + BRICK_ROWS ? brk_row_mask(w, lane - 11) : 0;
+                 : lane == 9 ? c.ep_steps : lane == 10 ? c.ep_rew : lane < 11 + BRICK_ROWS ? brk_row_mask(w, lane - 11)
+                 : lane == 11 + BRICK_ROWS ? c.prev : 0;
     st[lane] = hv;
   }
 }
@@ -115,7 +119,7 @@ __device__ __forceinline__ int brk_action(const int64_t* actions, int64_t act_st
   return (int)(a64 < 0 ? a64 + 4 : a64);
 }
 
-// One step of one world, in registers (wave-uniform; no memory access).  -> the reward; over: the episode ended and the
+// One game frame of one world, in registers (wave-uniform; no memory access).  -> the reward; over: the episode ended and the
 // world has been restarted; over_rew: the episode's reward, what such a step adds to ep_rew_sum
 __device__ __forceinline__ int brk_advance(BrkWorld& w, BrkCount& c, int a, uint32_t seed, uint32_t env, int lives,
                                            int max_episode_steps, bool& over, int& over_rew) {
@@ -168,6 +172,29 @@ __device__ __forceinline__ int brk_advance(BrkWorld& w, BrkCount& c, int a, uint
   return r;
 }
 
+// One agent step: frame_skip game frames with action a, each keeping the previous frame's action when its sticky draw (taken
+// BEFORE the frame itself; none with sticky_num == 0) mod sticky_den is below sticky_num; an episode end drops the
+// remaining frames.  -> the summed reward; over, over_rew: as brk_advance
+__device__ __forceinline__ int brk_agent_step(BrkWorld& w, BrkCount& c, int a, uint32_t seed, uint32_t env, int lives,
+                                              int max_episode_steps, int frame_skip, int sticky_num, int sticky_den, bool& over,
+                                              int& over_rew) {
+  int R = 0;
+  over = false;
+  for (int s = 0; s < frame_skip; ++s) {
+    int x = a;
+    if (sticky_num > 0) {
+      if ((int)(pong_hash(seed, env, c.draws++) % (uint32_t)sticky_den) < sticky_num) x = c.prev;
+      c.prev = x;
+    }
+    R += brk_advance(w, c, x, seed, env, lives, max_episode_steps, over, over_rew);
+    if (over) {
+      c.prev = 0;
+      break;
+    }
+  }
+  return R;
+}
+
 // lane 0 of the wave that owns the env: what a step leaves beside the state words
 __device__ __forceinline__ void brk_publish(int e, int r, bool over, int over_rew, float* rew, float* done, float* reset,
                                             int32_t* ep_count, int32_t* ep_rew_sum) {
@@ -180,10 +207,13 @@ __device__ __forceinline__ void brk_publish(int e, int r, bool over, int over_re
   reset[e] = over ? 1.0f : 0.0f;
 }
 
-template <bool STEP>
+// REPEAT == false is the (1, 0, .) world with its constants folded: one game frame, no loop, no sticky draw -- the kernel of
+// a2c_breakout_step as it was before frame skip (the loop with frame_skip = 1 at run time cost 0.15-0.35 us)
+template <bool STEP, bool REPEAT>
 __global__ __launch_bounds__(64) void breakout_kernel(int32_t* __restrict__ state, const int64_t* __restrict__ actions,
                                                       int64_t act_stride, int action_shift, int env_id0, uint32_t seed,
-                                                      int lives, int max_episode_steps, float* __restrict__ frames,
+                                                      int lives, int max_episode_steps, int frame_skip, int sticky_num,
+                                                      int sticky_den, float* __restrict__ frames,
                                                       int64_t frame_ld, float* __restrict__ rew, float* __restrict__ done,
                                                       float* __restrict__ reset, int32_t* __restrict__ ep_count,
                                                       int32_t* __restrict__ ep_rew_sum) {
@@ -191,13 +221,18 @@ __global__ __launch_bounds__(64) void breakout_kernel(int32_t* __restrict__ stat
   const uint32_t env = (uint32_t)(env_id0 + e);
   int32_t* st = state + (int64_t)e * BRK_WORDS;
   BrkWorld w;
-  BrkCount c = {0u, 0, 0, 0};
+  BrkCount c = {0u, 0, 0, 0, 0};
+  if (!REPEAT) {
+    frame_skip = 1;
+    sticky_num = 0;
+    sticky_den = 1;
+  }
   if (STEP) {
     brk_load(st, w, c);
     bool over;
     int over_rew;
-    const int r = brk_advance(w, c, brk_action(actions, act_stride, action_shift, e), seed, env, lives, max_episode_steps,
-                              over, over_rew);
+    const int r = brk_agent_step(w, c, brk_action(actions, act_stride, action_shift, e), seed, env, lives, max_episode_steps,
+                                 frame_skip, sticky_num, sticky_den, over, over_rew);
     if (lane == 0) brk_publish(e, r, over, over_rew, rew, done, reset, ep_count, ep_rew_sum);
   } else {
     brk_new_episode(w, seed, env, lives, c.draws, c.ep_steps);
@@ -207,12 +242,18 @@ __global__ __launch_bounds__(64) void breakout_kernel(int32_t* __restrict__ stat
 }
 
 // a2c_breakout_step_post: breakout_kernel<true> + the step's bookkeeping + the frame stack, WORLD_POST_WAVES waves per env.
-// Every wave loads the state words and computes the same step; the barrier keeps wave 0's stores behind every wave's loads.
+// Every wave loads the state words and computes the same agent step; the barrier keeps wave 0's stores behind every wave's loads.
+template <bool REPEAT>
 __global__ __launch_bounds__(WORLD_POST_THREADS) void breakout_post_kernel(
     int32_t* __restrict__ state, const int64_t* __restrict__ actions, int64_t act_stride, int action_shift, int env_id0,
-    uint32_t seed, int lives, int max_episode_steps, float* __restrict__ frames, int64_t frame_ld, float* __restrict__ rew,
-    float* __restrict__ done, float* __restrict__ reset, int32_t* __restrict__ ep_count, int32_t* __restrict__ ep_rew_sum,
+    uint32_t seed, int lives, int max_episode_steps, int frame_skip, int sticky_num, int sticky_den,
+    float* __restrict__ frames, int64_t frame_ld, float* __restrict__ rew, float* __restrict__ done, float* __restrict__ reset, int32_t* __restrict__ ep_count, int32_t* __restrict__ ep_rew_sum,
     const a2c_world_post post) {
+  if (!REPEAT) {
+    frame_skip = 1;
+    sticky_num = 0;
+    sticky_den = 1;
+  }
   const int e = blockIdx.x, tid = threadIdx.x;
   const uint32_t env = (uint32_t)(env_id0 + e);
   int32_t* st = state + (int64_t)e * BRK_WORDS;
@@ -223,7 +264,7 @@ __global__ __launch_bounds__(WORLD_POST_THREADS) void breakout_post_kernel(
   __syncthreads();
   bool over;
   int over_rew;
-  const int r = brk_advance(w, c, a, seed, env, lives, max_episode_steps, over, over_rew);
+  const int r = brk_agent_step(w, c, a, seed, env, lives, max_episode_steps, frame_skip, sticky_num, sticky_den, over, over_rew);
   const float d = world_post_done(post, (float)r, over ? 1.0f : 0.0f);
   if (tid == 0) {
     brk_publish(e, r, over, over_rew, rew, done, reset, ep_count, ep_rew_sum);
@@ -236,6 +277,11 @@ __global__ __launch_bounds__(WORLD_POST_THREADS) void breakout_post_kernel(
 
 bool brk_world_ok(int lives, int max_episode_steps) {
   return lives >= 1 && lives <= MAX_LIVES && max_episode_steps >= 1 && max_episode_steps <= MAX_EPISODE_STEPS;
+}
+
+bool brk_repeat_ok(int frame_skip, int sticky_num, int sticky_den) {
+  return frame_skip >= 1 && frame_skip <= MAX_FRAME_SKIP && sticky_den >= 1 && sticky_den <= MAX_STICKY_DEN && sticky_num >= 0 &&
+         sticky_num <= sticky_den;
 }
 
 bool brk_frames_ok(const float* frames, int64_t frame_ld) {
@@ -253,9 +299,27 @@ extern "C" int a2c_breakout_reset(int32_t* state, int B, int env_id0, uint32_t s
                                   float* frames, int64_t frame_ld, a2c_stream_t stream) {
   if (B <= 0 || env_id0 < 0 || !brk_world_ok(lives, max_episode_steps)) return A2C_ERR_ARG;
   if (state == nullptr || !brk_frames_ok(frames, frame_ld)) return A2C_ERR_ARG;
-  hipLaunchKernelGGL(breakout_kernel<false>, dim3(B), dim3(64), 0, a2c_s(stream), state, (const int64_t*)nullptr, (int64_t)0,
-                     0, env_id0, seed, lives, max_episode_steps, frames, frame_ld, (float*)nullptr, (float*)nullptr,
+  hipLaunchKernelGGL((breakout_kernel<false, false>), dim3(B), dim3(64), 0, a2c_s(stream), state, (const int64_t*)nullptr, (int64_t)0,
+                     0, env_id0, seed, lives, max_episode_steps, 1, 0, 1, frames, frame_ld, (float*)nullptr, (float*)nullptr,
                      (float*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+extern "C" int a2c_breakout_step_skip(int32_t* state, const int64_t* actions, int64_t act_stride, int action_shift, int B,
+                                      int env_id0, uint32_t seed, int lives, int max_episode_steps, float* frames,
+                                      int64_t frame_ld, float* rew, float* done, float* reset, int32_t* ep_count,
+                                      int32_t* ep_rew_sum, int frame_skip, int sticky_num, int sticky_den, a2c_stream_t stream) {
+  if (B <= 0 || env_id0 < 0 || act_stride < 0 || !brk_world_ok(lives, max_episode_steps) ||
+      !brk_repeat_ok(frame_skip, sticky_num, sticky_den))
+    return A2C_ERR_ARG;
+  if (state == nullptr || actions == nullptr || rew == nullptr || done == nullptr || reset == nullptr ||
+      !brk_frames_ok(frames, frame_ld))
+    return A2C_ERR_ARG;
+  const auto kernel = (frame_skip == 1 && sticky_num == 0) ? breakout_kernel<true, false> : breakout_kernel<true, true>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(64), 0, a2c_s(stream), state, actions, act_stride, action_shift,
+                     env_id0, seed, lives, max_episode_steps, frame_skip, sticky_num, sticky_den, frames, frame_ld, rew, done,
+                     reset, ep_count, ep_rew_sum);
   A2C_CHECK_LAUNCH();
   return A2C_OK;
 }
@@ -264,12 +328,25 @@ extern "C" int a2c_breakout_step(int32_t* state, const int64_t* actions, int64_t
                                  int env_id0, uint32_t seed, int lives, int max_episode_steps, float* frames,
                                  int64_t frame_ld, float* rew, float* done, float* reset, int32_t* ep_count,
                                  int32_t* ep_rew_sum, a2c_stream_t stream) {
-  if (B <= 0 || env_id0 < 0 || act_stride < 0 || !brk_world_ok(lives, max_episode_steps)) return A2C_ERR_ARG;
-  if (state == nullptr || actions == nullptr || rew == nullptr || done == nullptr || reset == nullptr ||
-      !brk_frames_ok(frames, frame_ld))
+  return a2c_breakout_step_skip(state, actions, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames,
+                                frame_ld, rew, done, reset, ep_count, ep_rew_sum, 1, 0, 1, stream);
+}
+
+extern "C" int a2c_breakout_step_post_skip(int32_t* state, const int64_t* actions, int64_t act_stride, int action_shift, int B,
+                                           int env_id0, uint32_t seed, int lives, int max_episode_steps, float* frames,
+                                           int64_t frame_ld, float* rew, float* done, float* reset, int32_t* ep_count,
+                                           int32_t* ep_rew_sum, int frame_skip, int sticky_num, int sticky_den,
+                                           const a2c_world_post* post, a2c_stream_t stream) {
+  if (B <= 0 || env_id0 < 0 || act_stride < 0 || !brk_world_ok(lives, max_episode_steps) ||
+      !brk_repeat_ok(frame_skip, sticky_num, sticky_den))
     return A2C_ERR_ARG;
-  hipLaunchKernelGGL(breakout_kernel<true>, dim3(B), dim3(64), 0, a2c_s(stream), state, actions, act_stride, action_shift,
-                     env_id0, seed, lives, max_episode_steps, frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum);
+  if (state == nullptr || actions == nullptr || rew == nullptr || done == nullptr || reset == nullptr ||
+      (frames != nullptr && !brk_frames_ok(frames, frame_ld)) || !a2c_world_post_ok(post, BRK_HW))
+    return A2C_ERR_ARG;
+  const auto kernel = (frame_skip == 1 && sticky_num == 0) ? breakout_post_kernel<false> : breakout_post_kernel<true>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(WORLD_POST_THREADS), 0, a2c_s(stream), state, actions, act_stride,
+                     action_shift, env_id0, seed, lives, max_episode_steps, frame_skip, sticky_num, sticky_den, frames, frame_ld,
+                     rew, done, reset, ep_count, ep_rew_sum, *post);
   A2C_CHECK_LAUNCH();
   return A2C_OK;
 }
@@ -278,13 +355,6 @@ extern "C" int a2c_breakout_step_post(int32_t* state, const int64_t* actions, in
                                       int env_id0, uint32_t seed, int lives, int max_episode_steps, float* frames,
                                       int64_t frame_ld, float* rew, float* done, float* reset, int32_t* ep_count,
                                       int32_t* ep_rew_sum, const a2c_world_post* post, a2c_stream_t stream) {
-  if (B <= 0 || env_id0 < 0 || act_stride < 0 || !brk_world_ok(lives, max_episode_steps)) return A2C_ERR_ARG;
-  if (state == nullptr || actions == nullptr || rew == nullptr || done == nullptr || reset == nullptr ||
-      (frames != nullptr && !brk_frames_ok(frames, frame_ld)) || !a2c_world_post_ok(post, BRK_HW))
-    return A2C_ERR_ARG;
-  hipLaunchKernelGGL(breakout_post_kernel, dim3(B), dim3(WORLD_POST_THREADS), 0, a2c_s(stream), state, actions, act_stride,
-                     action_shift, env_id0, seed, lives, max_episode_steps, frames, frame_ld, rew, done, reset, ep_count,
-                     ep_rew_sum, *post);
-  A2C_CHECK_LAUNCH();
-  return A2C_OK;
+  return a2c_breakout_step_post_skip(state, actions, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps,
+                                     frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, 1, 0, 1, post, stream);
 }

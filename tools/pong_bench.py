@@ -19,6 +19,10 @@ sees them; `--repeats` samples, the median is reported with min and max beside i
 pre-drawn uniform ones.  One JSON line on stdout.
 
     python tools/pong_bench.py [--iters 2000] [--epochs 30] [--repeats 5] [--n-envs 256] [--graphs on|off] [--learn 0]
+                               [--frame-skip 1] [--sticky 0/1]
+
+--frame-skip K / --sticky NUM/DEN measure worlds that play K game frames per env step with sticky actions (DESIGN.md section
+6g; the learning run keeps the plain world): the epochs then report game frames/s = K x env-steps/s beside env-steps/s.
 """
 import argparse
 import json
@@ -33,6 +37,9 @@ for p in (ROOT, os.path.join(ROOT, "pytorch-a2c_amd")):
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+
+REPEAT = {}      # --frame-skip / --sticky: the frame_skip, sticky_num and sticky_den of the measured pools
 
 
 def timed(fn, n, repeats):
@@ -52,7 +59,7 @@ def timed(fn, n, repeats):
 
 def bench_step(B, iters, repeats):
     from a2c_amd.pong import DevicePongPool
-    pool = DevicePongPool(B, "cuda", seed=1)
+    pool = DevicePongPool(B, "cuda", seed=1, **REPEAT)
     pool.reset_all()
     g = torch.Generator(device="cuda").manual_seed(3)
     acts = torch.randint(0, 3, (64, B), device="cuda", generator=g)
@@ -76,7 +83,7 @@ def bench_step_post(B, repeats, steps=200, C=4):
     acts = torch.randint(0, 3, (64, B), device="cuda", generator=g)
     out = {}
     for name in ("step_then_post", "step_post"):
-        pool = DevicePongPool(B, "cuda", seed=1)
+        pool = DevicePongPool(B, "cuda", seed=1, **REPEAT)
         pool.reset_all()
         HW = pool.HW
         S = C * HW
@@ -148,7 +155,7 @@ def bench_epoch(model, n_envs, T, epochs, repeats, graphs=True):
     net = getattr(a2c_amd.models, model)(list(ss), 3, h_size=256)
     N = n_envs * T
     D = datas(N, ss)
-    r = Runner(D, hyps, None, None, None, env_pool=DevicePongPool(n_envs, "cuda", seed=1))
+    r = Runner(D, hyps, None, None, None, env_pool=DevicePongPool(n_envs, "cuda", seed=1, **REPEAT))
     upd = Updater(net, hyps)
     slots = list(range(n_envs))
 
@@ -168,7 +175,9 @@ def bench_epoch(model, n_envs, T, epochs, repeats, graphs=True):
     finally:
         ops.lib = real
     f = lambda ms: round(N * epochs / (ms * 1e-3))
+    k = REPEAT.get("frame_skip", 1)
     return dict(model=model, n_envs=n_envs, n_tsteps=T, rollout_graphs=graphs, ms_per_epoch=round(med / epochs, 3), env_steps_per_s=f(med),
+                game_frames_per_s=k * f(med), game_frames_per_s_min=k * f(hi), game_frames_per_s_max=k * f(lo),
                 env_steps_per_s_min=f(hi), env_steps_per_s_max=f(lo), launches_issued_per_epoch=counted.n)
 
 
@@ -232,10 +241,16 @@ def main():
     ap.add_argument("--graphs", choices=("on", "off"), default="on", help="the Runner's one-graph device slot, or its eager loop")
     ap.add_argument("--learn", type=int, default=0, help="epochs of the learning sanity run (0: skip it)")
     ap.add_argument("--learn-model", default="FCModel")
+    ap.add_argument("--frame-skip", type=int, default=1, help="game frames per env step (DESIGN.md section 6g)")
+    ap.add_argument("--sticky", default="0/1", metavar="NUM/DEN", help="probability that a game frame keeps the previous action")
     args = ap.parse_args()
+    num, den = (int(v) for v in args.sticky.split("/"))
+    if (args.frame_skip, num) != (1, 0):
+        REPEAT.update(frame_skip=args.frame_skip, sticky_num=num, sticky_den=den)
     assert torch.cuda.is_available(), "pong_bench needs the MI355X"
     from a2c_amd.pong import DevicePongPool as DevicePool
-    res = dict(device=torch.cuda.get_device_name(0), iters=args.iters, repeats=args.repeats, graphs=args.graphs, step={}, epoch={})
+    res = dict(device=torch.cuda.get_device_name(0), iters=args.iters, repeats=args.repeats, graphs=args.graphs, frame_skip=args.frame_skip,
+               sticky=args.sticky, step={}, epoch={})
     for B in (32, 256, 2048):
         res["step"][f"B{B}"] = bench_step(B, args.iters, args.repeats)
     if hasattr(DevicePool, "device_step_post"):
