@@ -45,8 +45,8 @@ frames.  With ``sticky_num == 0`` no draw is taken and ``prev`` stays 0: k = 1 i
 that world stepped k times with one action and cut at the done."""
 import numpy as np
 
-from .pong import check_repeat
-from .snake import _env_id0, hash32
+from . import worlds
+from .worlds import _M, DeviceWorldPool, HostWorld, _clamp, _env_id0, _i32, check_repeat, factory_of, hash32  # noqa: F401
 
 N_ACTIONS = 4
 W, H = 72, 80
@@ -72,13 +72,11 @@ WORD_NAMES = ("paddle_x", "ball_x", "ball_y", "vx", "vy", "lives_left", "bricks_
 # raw frames (ALE's layout): the field is rows 35..194, columns 8..151 at 2 x scale
 RAW_H, RAW_W, RAW_TOP, RAW_LEFT, WALL_TOP = 210, 160, 35, 8, 17
 WALL_RGB, OBJECT_RGB = (142, 142, 142), (200, 72, 72)
-_M = 0xFFFFFFFF
 
 
 def repeat_from_hyps(hyps):
     """(frame_skip, sticky_num, sticky_den) from the hyps (1, 0, 1 where absent); ValueError outside the bounds"""
-    from .pong import repeat_from_hyps as from_hyps
-    return from_hyps(hyps, "Breakout")
+    return worlds.repeat_from_hyps(hyps, "Breakout")
 
 
 def check_world(lives=5, max_episode_steps=10000, frame_skip=1, sticky_num=0, sticky_den=1):
@@ -97,56 +95,33 @@ def world_from_hyps(hyps):
     return check_world(get("lives", 5), get("max_episode_steps", 10000))
 
 
-def _clamp(v, lo, hi):
-    return lo if v < lo else (hi if v > hi else v)
-
-
-def _i32(v):
-    """a 32-bit word as the signed int the device stores"""
-    v &= _M
-    return v - (1 << 32) if v >> 31 else v
-
-
 class _ActionSpace:
     n = N_ACTIONS
 
 
-class BreakoutEnv:
+class BreakoutEnv(HostWorld):
     """One Breakout world on the host.  ``reset()`` -> raw (210, 160, 3) uint8 frame; ``step(a)`` -> (frame, reward, done,
     info) with the REAL done (no life left, no brick left, or the step limit).  Like a gym env it does not reset itself:
     the caller does -- the Runner does, which yields exactly what the device world returns.  ``events`` counts what
     happened (with frame skip or sticky actions also ``cut``: episode ends that dropped game frames of their agent step, and
     ``sticky``: game frames that kept an action other than the requested one) for tests that must see every rule at work.  ``step`` / ``advance`` are the AGENT
     step: ``frame_skip`` game frames (module docstring)."""
+    WHAT, N_ACTIONS = "Breakout", N_ACTIONS
     action_space = _ActionSpace()
 
     def __init__(self, seed=0, env_id=0, lives=5, max_episode_steps=10000, frame_skip=1, sticky_num=0, sticky_den=1):
         self.lives, self.max_episode_steps = check_world(lives, max_episode_steps)
-        self.frame_skip, self.sticky_num, self.sticky_den = check_repeat(frame_skip, sticky_num, sticky_den, "Breakout")
-        self.prev = 0
-        self.seed_, self.env_id = int(seed) & _M, int(env_id)
+        super().__init__(seed, env_id, frame_skip, sticky_num, sticky_den,
+                         ("side_wall", "ceiling", "brick", "speed_up", "paddle_hit", "life_lost", "cleared", "episode_end"))
         self.paddle_x = PADDLE_START_X
         self.ball_x, self.ball_y, self.vx, self.vy = SERVE_X0, SERVE_Y, 1, -1
         self.lives_left, self.bricks_left, self.rows = self.lives, N_BRICKS, [FULL_ROW] * BRICK_ROWS
-        self.draws = self.steps = self.ep_steps = self.ep_rew = 0
-        self.over = True
-        self.events = dict(side_wall=0, ceiling=0, brick=0, speed_up=0, paddle_hit=0, life_lost=0, cleared=0, episode_end=0)
-        if (self.frame_skip, self.sticky_num) != (1, 0):      # a plain world can neither cut nor keep an action
-            self.events.update(cut=0, sticky=0)
-
-    def seed(self, seed):
-        self.seed_ = int(seed) & _M
+        self.ep_rew = 0
 
     def _serve(self):
-        d = hash32(self.seed_, self.env_id, self.draws)
-        self.draws = (self.draws + 1) & _M
+        d = self._draw()
         self.ball_x, self.ball_y = SERVE_X0 + d % SERVE_SPAN, SERVE_Y
         self.vx, self.vy = (1 if (d >> 8) & 1 else -1), -1
-
-    # ---- gym surface
-    def reset(self):
-        self.new_episode()
-        return self.render_rgb()
 
     def new_episode(self):
         """the reset without its frame"""
@@ -155,34 +130,6 @@ class BreakoutEnv:
         self.paddle_x = PADDLE_START_X
         self._serve()
         self.over = False
-
-    def step(self, action):
-        rew, done = self.advance(action)
-        return self.render_rgb(), rew, done, {}
-
-    def advance(self, action):
-        """the agent step without its frame: ``frame_skip`` game frames -> (summed reward, done)"""
-        if self.over:
-            raise RuntimeError("BreakoutEnv.step() after done: call reset()")
-        a = int(action) % 4
-        total, done = 0.0, False
-        for s in range(self.frame_skip):
-            x = a
-            if self.sticky_num > 0:
-                d = hash32(self.seed_, self.env_id, self.draws)
-                self.draws = (self.draws + 1) & _M
-                if d % self.sticky_den < self.sticky_num:
-                    x = self.prev
-                    self.events["sticky"] += x != a
-                self.prev = x
-            rew, done = self._frame(x)
-            total += rew
-            if done:
-                self.prev = 0
-                if s < self.frame_skip - 1:
-                    self.events["cut"] += 1
-                break
-        return total, done
 
     def _frame(self, a):
         """one game frame with action ``a`` in 0..3 -> (reward, done)"""
@@ -242,9 +189,6 @@ class BreakoutEnv:
             self._serve()
         return float(rew), done
 
-    def render(self):
-        return self.render_rgb()
-
     # ---- frames
     def prepped(self):
         """the (1, 80, 72) uint8 frame breakout_prep makes of render_rgb(): the bricks' grey levels, 200 on the paddle and
@@ -291,114 +235,34 @@ class BreakoutEnv:
         self.over = False
 
 
-class BreakoutFactory:
-    """picklable ``env_fn`` for ``SequentialEnvironment`` / the env worker processes"""
-
-    def __init__(self, env_id=0, **world):
-        self.kw = dict(world, env_id=env_id)
-
-    def __call__(self, *a, **k):
-        return BreakoutEnv(**self.kw)
+# picklable ``env_fn``: ``BreakoutFactory(env_id=j, **world)()`` is a ``BreakoutEnv``
+BreakoutFactory = factory_of(BreakoutEnv)
 
 
-class DeviceBreakoutPool:
+class DeviceBreakoutPool(DeviceWorldPool):
     """``n_envs`` Breakout worlds in device memory (the Runner's device-pool protocol).  Env j is the world
     ``BreakoutEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames; with ``frame_skip`` / ``sticky_num`` /
-    ``sticky_den`` other than (1, 0, .) a step is an agent step of a2c_breakout_step_skip.  ``device_step`` returns ``done`` and ``reset`` as two
-    tensors holding the same values, the real done.  ``episode_stats`` counts the finished episodes and sums their rewards."""
-    needs_actions = True
+    ``sticky_den`` other than (1, 0, .) a step is an agent step of a2c_breakout_step_skip.
+    ``device_step`` returns ``done`` and ``reset`` as two tensors holding the same values, the real done.  ``episode_stats``
+    counts the finished episodes and sums their rewards."""
     frame_shape = (1, H, W)
 
     def __init__(self, n_envs, device="cuda", seed=0, lives=5, max_episode_steps=10000, env_id0=0, frame_skip=1, sticky_num=0,
                  sticky_den=1):
-        import torch
         from . import ops
         self.world = check_world(lives, max_episode_steps)
         self.repeat = check_repeat(frame_skip, sticky_num, sticky_den, "Breakout")
         self.plain = self.repeat[:2] == (1, 0)      # today's world: the entry points without frame skip
-        self.B, self.seed, self.device = int(n_envs), int(seed) & _M, torch.device(device)
-        if self.B < 1:
-            raise ValueError("DeviceBreakoutPool: n_envs >= 1")
-        self.env_id0 = _env_id0(env_id0, self.B)
-        self.HW = H * W
-        self.words = ops.breakout_state_bytes(self.world[0]) // 4
-        dev = self.device
-        self.state = torch.zeros((self.B, self.words), dtype=torch.int32, device=dev)
-        self.frames = torch.zeros((self.B, self.HW), dtype=torch.float32, device=dev)
-        self.rew, self.done, self.reset_mask = (torch.zeros(self.B, dtype=torch.float32, device=dev) for _ in range(3))
-        self.ep_stats = torch.zeros(2, dtype=torch.int32, device=dev)      # episodes finished, sum of their rewards
-        self.action_shift = 0
-        self.started = False
+        super().__init__(n_envs, device, seed, env_id0, ops.breakout_state_bytes(self.world[0]) // 4)
 
-    def __len__(self):
-        return self.B
-
-    def reset_all(self, env_id0=None):
-        """(re)starts every world: counters to 0, then the serve draw; state and frames of the reset positions.  ``env_id0``
-        re-bases the pool first: env j becomes world ``env_id0 + j``"""
+    def _reset(self):
         from . import ops
-        if env_id0 is not None:
-            self.env_id0 = _env_id0(env_id0, self.B)
         ops.breakout_reset(self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
-        self.started = True
 
-    def start(self, runner):
-        import torch
+    def _step(self, head, out, frames, post, sl):
         from . import ops
-        self.action_shift = int(runner.hyps["action_shift"])
-        self.reset_all()
-        ones = torch.ones(self.B, dtype=torch.float32, device=self.device)
-        ops.frame_stack_push(self.frames, ones, runner.bookmark.data_ptr(), runner.S, runner.bookmark.data_ptr(), runner.S,
-                             self.B, runner.C, runner.HW)
-
-    def step(self, actions_ptr, act_stride, env0=0, B=None):
-        """advance envs env0..env0+B by the int64 actions at ``actions_ptr`` (element stride ``act_stride``)"""
-        from . import ops
-        B = self.B - env0 if B is None else B
-        if not self.started:
-            raise RuntimeError("DeviceBreakoutPool: reset_all() / start(runner) first")
-        if env0 < 0 or B < 1 or env0 + B > self.B:
-            raise ValueError("DeviceBreakoutPool: env range outside the pool")
-        sl = slice(env0, env0 + B)
-        if self.plain:
-            ops.breakout_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
-                              self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl],
-                              self.reset_mask[sl], self.ep_stats[0:1], self.ep_stats[1:2])
+        if post is None:
+            fn, extra = (ops.breakout_step, ()) if self.plain else (ops.breakout_step_skip, self.repeat)
         else:
-            ops.breakout_step_skip(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
-                                   self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl],
-                                   self.reset_mask[sl], *self.repeat, self.ep_stats[0:1], self.ep_stats[1:2])
-        return self.frames[sl], self.rew[sl], self.done[sl], self.reset_mask[sl]
-
-    def device_step(self, t, env0, B, actions=None):
-        if actions is None:
-            raise ValueError("DeviceBreakoutPool.device_step needs actions=(address, stride)")
-        return self.step(actions[0], actions[1], env0, B)
-
-    def device_step_post(self, t, env0, B, actions, post, frames=False):
-        """``device_step`` + the bookkeeping of env step ``t`` + the frame stack in ONE launch (a2c_breakout_step_post): ``post`` is
-        an ``ops.world_post`` block.  The new frame goes into plane C - 1 of ``post.out``; ``self.frames`` is written as
-        well only with ``frames=True`` (the Runner does not read it).  -> (rew, done, reset)"""
-        from . import ops
-        if not self.started:
-            raise RuntimeError("DeviceBreakoutPool: reset_all() / start(runner) first")
-        if env0 < 0 or B < 1 or env0 + B > self.B:
-            raise ValueError("DeviceBreakoutPool: env range outside the pool")
-        sl = slice(env0, env0 + B)
-        if self.plain:
-            ops.breakout_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
-                                   self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl],
-                                   self.done[sl], self.reset_mask[sl], post, self.ep_stats[0:1], self.ep_stats[1:2])
-        else:
-            ops.breakout_step_post_skip(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
-                                        self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl],
-                                        self.done[sl], self.reset_mask[sl], *self.repeat, post, self.ep_stats[0:1],
-                                        self.ep_stats[1:2])
-        return self.rew[sl], self.done[sl], self.reset_mask[sl]
-
-    def episode_stats(self):
-        """(episodes finished, sum of their rewards) since the last call; one device read"""
-        n, s = (int(v) for v in self.ep_stats.tolist())
-        if n:
-            self.ep_stats.zero_()
-        return n, s
+            fn, extra = (ops.breakout_step_post, (post,)) if self.plain else (ops.breakout_step_post_skip, (*self.repeat, post))
+        fn(*head, *self.world, frames, self.HW, *out, *extra, self.ep_stats[0:1], self.ep_stats[1:2])

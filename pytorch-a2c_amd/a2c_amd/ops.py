@@ -1256,6 +1256,12 @@ def snake_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, G
 
 
 # ---------------------------------------------------------------- Pong worlds in device memory (csrc/pong.hip)
+def _chk_world(state, frames, rew=None, done=None, reset=None, ep_count=None, ep_rew_sum=None):
+    """the tensors of a Pong / Breakout entry point (None: absent)"""
+    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
+    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+
+
 def pong_state_bytes(points_to_win=21):
     """bytes of one env's state; raises for a world the kernels do not support"""
     n = int(lib().a2c_pong_state_bytes(points_to_win))
@@ -1266,7 +1272,7 @@ def pong_state_bytes(points_to_win=21):
 
 def pong_reset(state, B, env_id0, seed, points_to_win, max_episode_steps, opp_skill_num, opp_skill_den, frames, frame_ld,
                st=None):
-    _chk(state, "state", torch.int32); _chk(frames, "frames")
+    _chk_world(state, frames)
     check(lib().a2c_pong_reset(_p(state), B, env_id0, seed, points_to_win, max_episode_steps, opp_skill_num, opp_skill_den,
                                _p(frames), frame_ld, _st(st)), "a2c_pong_reset")
 
@@ -1274,8 +1280,7 @@ def pong_reset(state, B, env_id0, seed, points_to_win, max_episode_steps, opp_sk
 def pong_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win, max_episode_steps, opp_skill_num,
               opp_skill_den, frames, frame_ld, rew, done, reset, ep_count=None, ep_rew_sum=None, st=None):
     """actions_ptr: address of env 0's int64 action, ``act_stride`` elements between envs (a row of the rollout buffer)"""
-    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
-    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
     check(lib().a2c_pong_step(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
                               max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew), _p(done),
                               _p(reset), _p(ep_count), _p(ep_rew_sum), _st(st)), "a2c_pong_step")
@@ -1286,8 +1291,7 @@ def pong_step_skip(state, actions_ptr, act_stride, action_shift, B, env_id0, see
                    ep_count=None, ep_rew_sum=None, st=None):
     """pong_step over ``frame_skip`` game frames, each keeping the previous frame's action with probability ``sticky_num`` /
     ``sticky_den``; (1, 0, 1) is pong_step"""
-    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
-    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
     check(lib().a2c_pong_step_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
                                    max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew), _p(done),
                                    _p(reset), _p(ep_count), _p(ep_rew_sum), frame_skip, sticky_num, sticky_den, _st(st)),
@@ -1304,7 +1308,7 @@ def breakout_state_bytes(lives=5):
 
 
 def breakout_reset(state, B, env_id0, seed, lives, max_episode_steps, frames, frame_ld, st=None):
-    _chk(state, "state", torch.int32); _chk(frames, "frames")
+    _chk_world(state, frames)
     check(lib().a2c_breakout_reset(_p(state), B, env_id0, seed, lives, max_episode_steps, _p(frames), frame_ld, _st(st)),
           "a2c_breakout_reset")
 
@@ -1312,8 +1316,7 @@ def breakout_reset(state, B, env_id0, seed, lives, max_episode_steps, frames, fr
 def breakout_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames, frame_ld,
                   rew, done, reset, ep_count=None, ep_rew_sum=None, st=None):
     """actions_ptr: address of env 0's int64 action, ``act_stride`` elements between envs (a row of the rollout buffer)"""
-    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
-    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
     check(lib().a2c_breakout_step(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
                                   max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
                                   _p(ep_rew_sum), _st(st)), "a2c_breakout_step")
@@ -1323,8 +1326,7 @@ def breakout_step_skip(state, actions_ptr, act_stride, action_shift, B, env_id0,
                        frame_ld, rew, done, reset, frame_skip, sticky_num, sticky_den, ep_count=None, ep_rew_sum=None, st=None):
     """breakout_step over ``frame_skip`` game frames, each keeping the previous frame's action with probability
     ``sticky_num`` / ``sticky_den``; (1, 0, 1) is breakout_step"""
-    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
-    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
     check(lib().a2c_breakout_step_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
                                        max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
                                        _p(ep_rew_sum), frame_skip, sticky_num, sticky_den, _st(st)), "a2c_breakout_step_skip")
@@ -1362,8 +1364,7 @@ def pong_step_post(state, actions_ptr, act_stride, action_shift, B, env_id0, see
                    opp_skill_num, opp_skill_den, frames, frame_ld, rew, done, reset, post, ep_count=None, ep_rew_sum=None,
                    st=None):
     """pong_step + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
-    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
-    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
     check(lib().a2c_pong_step_post(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
                                          max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew),
                                          _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum), _post_ref(post), _st(st)),
@@ -1373,8 +1374,7 @@ def pong_step_post(state, actions_ptr, act_stride, action_shift, B, env_id0, see
 def breakout_step_post(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames,
                        frame_ld, rew, done, reset, post, ep_count=None, ep_rew_sum=None, st=None):
     """breakout_step + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
-    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
-    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
     check(lib().a2c_breakout_step_post(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
                                              max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset),
                                              _p(ep_count), _p(ep_rew_sum), _post_ref(post), _st(st)), "a2c_breakout_step_post")
@@ -1384,8 +1384,7 @@ def pong_step_post_skip(state, actions_ptr, act_stride, action_shift, B, env_id0
                         opp_skill_num, opp_skill_den, frames, frame_ld, rew, done, reset, frame_skip, sticky_num, sticky_den,
                         post, ep_count=None, ep_rew_sum=None, st=None):
     """pong_step_skip + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
-    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
-    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
     check(lib().a2c_pong_step_post_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
                                         max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew),
                                         _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum), frame_skip, sticky_num, sticky_den,
@@ -1396,8 +1395,7 @@ def breakout_step_post_skip(state, actions_ptr, act_stride, action_shift, B, env
                             frame_ld, rew, done, reset, frame_skip, sticky_num, sticky_den, post, ep_count=None,
                             ep_rew_sum=None, st=None):
     """breakout_step_skip + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
-    _chk(state, "state", torch.int32); _chk(frames, "frames"); _chk(rew, "rew"); _chk(done, "done"); _chk(reset, "reset")
-    _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
     check(lib().a2c_breakout_step_post_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
                                             max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset),
                                             _p(ep_count), _p(ep_rew_sum), frame_skip, sticky_num, sticky_den, _post_ref(post),

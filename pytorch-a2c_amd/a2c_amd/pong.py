@@ -40,7 +40,8 @@ agent step (after a serve the ball needs at least 33 frames to reach a goal line
 above word for word, k > 1 is that world stepped k times with one action and cut at the real done."""
 import numpy as np
 
-from .snake import _env_id0, hash32
+from .worlds import (MAX_FRAME_SKIP, MAX_STICKY_DEN, _M, DeviceWorldPool, HostWorld, _clamp, _env_id0, check_repeat,  # noqa: F401
+                     factory_of, hash32, repeat_from_hyps)
 
 N_ACTIONS = 3
 W = H = 80
@@ -53,29 +54,11 @@ HIT_VY = (-2, -2, -1, -1, 0, 1, 1, 2, 2)         # by off = ball y + 1 - paddle 
 HIT_SPEED = (2, 2, 1, 1, 1, 1, 1, 2, 2)          # |vx| after the hit
 MISS_RIGHT, MISS_LEFT = AGENT_X + PADDLE_W, OPP_X - BALL      # ball x >= 72: agent missed; ball x <= 6: opponent missed
 MAX_POINTS, MAX_EPISODE_STEPS, MAX_SKILL_DEN = 21, 1 << 24, 1 << 16
-MAX_FRAME_SKIP, MAX_STICKY_DEN = 8, 1 << 16
 # raw frames (ALE's layout): the playfield is rows 35..194 at 2 x scale; channel 0 of the two background colours is what
 # pong_prep removes
 RAW_H, RAW_W, RAW_TOP = 210, 160, 35
 FIELD_BG, BORDER_BG = (144, 72, 17), (109, 118, 43)
 OPP_RGB, AGENT_RGB, BALL_RGB = (213, 130, 74), (92, 186, 92), (236, 236, 236)
-_M = 0xFFFFFFFF
-
-
-def check_repeat(frame_skip=1, sticky_num=0, sticky_den=1, what="Pong"):
-    """the bounds a2c_<world>_step_skip enforces (A2C_ERR_ARG) on frame skip and sticky actions: same ones for the host
-    twins -> (frame_skip, sticky_num, sticky_den)"""
-    k, n, d = int(frame_skip), int(sticky_num), int(sticky_den)
-    if not (1 <= k <= MAX_FRAME_SKIP and 1 <= d <= MAX_STICKY_DEN and 0 <= n <= d):
-        raise ValueError(f"{what}: unsupported frame_skip={k} sticky={n}/{d} (1 <= frame_skip <= {MAX_FRAME_SKIP}, "
-                         f"1 <= sticky_den <= {MAX_STICKY_DEN}, 0 <= sticky_num <= sticky_den)")
-    return k, n, d
-
-
-def repeat_from_hyps(hyps, what="Pong"):
-    """(frame_skip, sticky_num, sticky_den) from the hyps (1, 0, 1 where absent); ValueError outside the bounds"""
-    get = lambda k, dflt: dflt if hyps.get(k) is None else hyps[k]
-    return check_repeat(get("frame_skip", 1), get("sticky_num", 0), get("sticky_den", 1), what)
 
 
 def check_world(points_to_win=21, max_episode_steps=10000, opp_skill_num=3, opp_skill_den=4, frame_skip=1, sticky_num=0,
@@ -97,55 +80,33 @@ def world_from_hyps(hyps):
                        get("opp_skill_den", 4))
 
 
-def _clamp(v, lo, hi):
-    return lo if v < lo else (hi if v > hi else v)
-
-
 class _ActionSpace:
     n = N_ACTIONS
 
 
-class PongEnv:
+class PongEnv(HostWorld):
     """One Pong world on the host.  ``reset()`` -> raw (210, 160, 3) uint8 frame; ``step(a)`` -> (frame, reward, done,
     info) with the REAL done (a score at ``points_to_win``, or the step limit).  Like a gym env it does not reset itself:
     the caller does -- the Runner does, which yields exactly what the device world returns.  ``events`` counts what
     happened (wall bounces, paddle hits, points, episode ends; with frame skip or sticky actions also ``cut``: episode ends
     that dropped game frames of their agent step, and ``sticky``: game frames that kept an action other than the requested one) for tests that must see every
     rule at work.  ``step`` / ``advance`` are the AGENT step: ``frame_skip`` game frames (module docstring)."""
+    WHAT, N_ACTIONS = "Pong", N_ACTIONS
     action_space = _ActionSpace()
 
     def __init__(self, seed=0, env_id=0, points_to_win=21, max_episode_steps=10000, opp_skill_num=3, opp_skill_den=4,
                  frame_skip=1, sticky_num=0, sticky_den=1):
         self.points_to_win, self.max_episode_steps, self.skill_num, self.skill_den = check_world(
             points_to_win, max_episode_steps, opp_skill_num, opp_skill_den)
-        self.frame_skip, self.sticky_num, self.sticky_den = check_repeat(frame_skip, sticky_num, sticky_den)
-        self.prev = 0
-        self.seed_, self.env_id = int(seed) & _M, int(env_id)
+        super().__init__(seed, env_id, frame_skip, sticky_num, sticky_den,
+                         ("wall", "hit_agent", "hit_opp", "agent_point", "opp_point", "episode_end"))
         self.agent_y = self.opp_y = PADDLE_START_Y
         self.ball_x, self.ball_y, self.vx, self.vy = SERVE_X, SERVE_Y, 1, 0
         self.score_agent = self.score_opp = 0
-        self.draws = self.steps = self.ep_steps = 0
-        self.over = True
-        self.events = dict(wall=0, hit_agent=0, hit_opp=0, agent_point=0, opp_point=0, episode_end=0)
-        if (self.frame_skip, self.sticky_num) != (1, 0):      # a plain world can neither cut nor keep an action
-            self.events.update(cut=0, sticky=0)
-
-    def seed(self, seed):
-        self.seed_ = int(seed) & _M
-
-    def _draw(self):
-        d = hash32(self.seed_, self.env_id, self.draws)
-        self.draws = (self.draws + 1) & _M
-        return d
 
     def _serve(self, d, towards_agent):
         self.ball_x, self.ball_y = SERVE_X, SERVE_Y
         self.vx, self.vy = (1 if towards_agent else -1), (d >> 1) % 5 - 2
-
-    # ---- gym surface
-    def reset(self):
-        self.new_episode()
-        return self.render_rgb()
 
     def new_episode(self):
         """the reset without its frame"""
@@ -155,32 +116,8 @@ class PongEnv:
         self._serve(d, bool(d & 1))
         self.over = False
 
-    def step(self, action):
-        rew, done = self.advance(action)
-        return self.render_rgb(), rew, done, {}
-
-    def advance(self, action):
-        """the agent step without its frame: ``frame_skip`` game frames -> (summed reward, done)"""
-        if self.over:
-            raise RuntimeError("PongEnv.step() after done: call reset()")
-        a = int(action) % 3
-        total, done = 0.0, False
-        for s in range(self.frame_skip):
-            x = a
-            if self.sticky_num > 0:
-                if self._draw() % self.sticky_den < self.sticky_num:
-                    x = self.prev
-                    self.events["sticky"] += x != a
-                self.prev = x
-            rew, done = self._frame(x)
-            total += rew
-            if done:
-                self.prev = 0
-                if s < self.frame_skip - 1:
-                    self.events["cut"] += 1
-                break
+    def _check_step(self, total):
         assert abs(total) <= 1, "more than one point in one agent step"
-        return total, done
 
     def _frame(self, a):
         """one game frame with action ``a`` in 0..2 -> (reward, done)"""
@@ -232,9 +169,6 @@ class PongEnv:
             self._serve(self._draw(), rew < 0)
         return float(rew), done
 
-    def render(self):
-        return self.render_rgb()
-
     # ---- frames
     def rectangles(self):
         """(x, y, w, h) of the opponent's paddle, the agent's paddle and the ball"""
@@ -257,115 +191,35 @@ class PongEnv:
         return pic
 
 
-class PongFactory:
-    """picklable ``env_fn`` for ``SequentialEnvironment`` / the env worker processes"""
-
-    def __init__(self, env_id=0, **world):
-        self.kw = dict(world, env_id=env_id)
-
-    def __call__(self, *a, **k):
-        return PongEnv(**self.kw)
+# picklable ``env_fn``: ``PongFactory(env_id=j, **world)()`` is a ``PongEnv``
+PongFactory = factory_of(PongEnv)
 
 
-class DevicePongPool:
+class DevicePongPool(DeviceWorldPool):
     """``n_envs`` Pong worlds in device memory (the Runner's device-pool protocol).  Env j is the world
     ``PongEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames; with ``frame_skip`` / ``sticky_num`` / ``sticky_den``
-    other than (1, 0, .) a step is an agent step of a2c_pong_step_skip.  ``device_step`` returns ``done = (rew != 0) or real
-    done`` (the Pong override of the reference's runner) and ``reset = real done`` as two tensors.  ``episode_stats``
-    counts what the Runner's ``rew_q`` counts for a "Pong" env type: every ``done``, with the reward since the last one."""
-    needs_actions = True
+    other than (1, 0, .) a step is an agent step of a2c_pong_step_skip.  ``device_step`` returns
+    ``done = (rew != 0) or real done`` (the Pong override of the reference's runner) and ``reset = real done`` as two tensors.
+    ``episode_stats`` counts what the Runner's ``rew_q`` counts for a "Pong" env type: every ``done``, with the reward since
+    the last one."""
     frame_shape = (1, H, W)
 
     def __init__(self, n_envs, device="cuda", seed=0, points_to_win=21, max_episode_steps=10000, opp_skill_num=3,
                  opp_skill_den=4, env_id0=0, frame_skip=1, sticky_num=0, sticky_den=1):
-        import torch
         from . import ops
         self.world = check_world(points_to_win, max_episode_steps, opp_skill_num, opp_skill_den)
         self.repeat = check_repeat(frame_skip, sticky_num, sticky_den)
         self.plain = self.repeat[:2] == (1, 0)      # today's world: the entry points without frame skip
-        self.B, self.seed, self.device = int(n_envs), int(seed) & _M, torch.device(device)
-        if self.B < 1:
-            raise ValueError("DevicePongPool: n_envs >= 1")
-        self.env_id0 = _env_id0(env_id0, self.B)
-        self.HW = H * W
-        self.words = ops.pong_state_bytes(self.world[0]) // 4
-        dev = self.device
-        self.state = torch.zeros((self.B, self.words), dtype=torch.int32, device=dev)
-        self.frames = torch.zeros((self.B, self.HW), dtype=torch.float32, device=dev)
-        self.rew, self.done, self.reset_mask = (torch.zeros(self.B, dtype=torch.float32, device=dev) for _ in range(3))
-        self.ep_stats = torch.zeros(2, dtype=torch.int32, device=dev)      # dones, sum of the rewards they closed
-        self.action_shift = 0
-        self.started = False
+        super().__init__(n_envs, device, seed, env_id0, ops.pong_state_bytes(self.world[0]) // 4)
 
-    def __len__(self):
-        return self.B
-
-    def reset_all(self, env_id0=None):
-        """(re)starts every world: counters to 0, then the reset draw; state and frames of the reset positions.  ``env_id0``
-        re-bases the pool first: env j becomes world ``env_id0 + j``"""
+    def _reset(self):
         from . import ops
-        if env_id0 is not None:
-            self.env_id0 = _env_id0(env_id0, self.B)
         ops.pong_reset(self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
-        self.started = True
 
-    def start(self, runner):
-        import torch
+    def _step(self, head, out, frames, post, sl):
         from . import ops
-        self.action_shift = int(runner.hyps["action_shift"])
-        self.reset_all()
-        ones = torch.ones(self.B, dtype=torch.float32, device=self.device)
-        ops.frame_stack_push(self.frames, ones, runner.bookmark.data_ptr(), runner.S, runner.bookmark.data_ptr(), runner.S,
-                             self.B, runner.C, runner.HW)
-
-    def step(self, actions_ptr, act_stride, env0=0, B=None):
-        """advance envs env0..env0+B by the int64 actions at ``actions_ptr`` (element stride ``act_stride``)"""
-        from . import ops
-        B = self.B - env0 if B is None else B
-        if not self.started:
-            raise RuntimeError("DevicePongPool: reset_all() / start(runner) first")
-        if env0 < 0 or B < 1 or env0 + B > self.B:
-            raise ValueError("DevicePongPool: env range outside the pool")
-        sl = slice(env0, env0 + B)
-        if self.plain:
-            ops.pong_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
-                          self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl], self.reset_mask[sl],
-                          self.ep_stats[0:1], self.ep_stats[1:2])
+        if post is None:
+            fn, extra = (ops.pong_step, ()) if self.plain else (ops.pong_step_skip, self.repeat)
         else:
-            ops.pong_step_skip(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
-                               self.seed, *self.world, self.frames[sl], self.HW, self.rew[sl], self.done[sl],
-                               self.reset_mask[sl], *self.repeat, self.ep_stats[0:1], self.ep_stats[1:2])
-        return self.frames[sl], self.rew[sl], self.done[sl], self.reset_mask[sl]
-
-    def device_step(self, t, env0, B, actions=None):
-        if actions is None:
-            raise ValueError("DevicePongPool.device_step needs actions=(address, stride)")
-        return self.step(actions[0], actions[1], env0, B)
-
-    def device_step_post(self, t, env0, B, actions, post, frames=False):
-        """``device_step`` + the bookkeeping of env step ``t`` + the frame stack in ONE launch (a2c_pong_step_post): ``post`` is
-        an ``ops.world_post`` block.  The new frame goes into plane C - 1 of ``post.out``; ``self.frames`` is written as
-        well only with ``frames=True`` (the Runner does not read it).  -> (rew, done, reset)"""
-        from . import ops
-        if not self.started:
-            raise RuntimeError("DevicePongPool: reset_all() / start(runner) first")
-        if env0 < 0 or B < 1 or env0 + B > self.B:
-            raise ValueError("DevicePongPool: env range outside the pool")
-        sl = slice(env0, env0 + B)
-        if self.plain:
-            ops.pong_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
-                               self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl],
-                               self.done[sl], self.reset_mask[sl], post, self.ep_stats[0:1], self.ep_stats[1:2])
-        else:
-            ops.pong_step_post_skip(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
-                                    self.seed, *self.world, self.frames[sl] if frames else None, self.HW, self.rew[sl],
-                                    self.done[sl], self.reset_mask[sl], *self.repeat, post, self.ep_stats[0:1],
-                                    self.ep_stats[1:2])
-        return self.rew[sl], self.done[sl], self.reset_mask[sl]
-
-    def episode_stats(self):
-        """(dones, sum of the rewards they closed) since the last call; one device read"""
-        n, s = (int(v) for v in self.ep_stats.tolist())
-        if n:
-            self.ep_stats.zero_()
-        return n, s
+            fn, extra = (ops.pong_step_post, (post,)) if self.plain else (ops.pong_step_post_skip, (*self.repeat, post))
+        fn(*head, *self.world, frames, self.HW, *out, *extra, self.ep_stats[0:1], self.ep_stats[1:2])

@@ -1477,7 +1477,7 @@ class DeviceStatsRunner:
         if not r._ready:
             r.start(net)
         r.__dict__.get("_dev_graphs", {}).clear()          # (graphs of the ids the pool leaves: never replayed again)
-        (pool.reset_all if hasattr(pool, "reset_all") else pool.reset)(env_id0=self.ENV_ID0 + self.calls * self.E)
+        pool.reset_all(env_id0=self.ENV_ID0 + self.calls * self.E)
         ops.frame_stack_push(pool.frames, self._ones, r.bookmark.data_ptr(), r.S, r.bookmark.data_ptr(), r.S, self.E, r.C, r.HW)
         r.val_prev.zero_()
         r.done_eff.zero_()

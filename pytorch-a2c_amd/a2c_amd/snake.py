@@ -23,28 +23,13 @@ in row-major order with ``k = draw mod n_free``.  The body is a time-to-live map
 number of steps it stays occupied (head = length)."""
 import numpy as np
 
+from .worlds import _M, DeviceWorldPool, _env_id0, _fin, hash32  # noqa: F401
+
 N_ACTIONS = 4
 DR = (-1, 0, 1, 0)
 DC = (0, 1, 0, -1)
 SPACE, BODY, HEAD, FOOD = (0, 255, 0), (1, 0, 0), (255, 0, 0), (0, 0, 255)
 PREP_SPACE, PREP_BODY, PREP_HEAD, PREP_FOOD = 0.0, 1.0, 1.5, .33          # what snake_prep makes of the four colours
-_M = 0xFFFFFFFF
-
-
-def _fin(x):
-    """the integer finaliser (lowbias32): x ^= x>>16; x *= 0x7FEB352D; x ^= x>>15; x *= 0x846CA68B; x ^= x>>16 (mod 2^32)"""
-    x &= _M
-    x ^= x >> 16
-    x = (x * 0x7FEB352D) & _M
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & _M
-    x ^= x >> 16
-    return x
-
-
-def hash32(seed, env_id, draw_index):
-    """fin(fin(fin(seed + 0x9E3779B9) ^ env_id) ^ draw_index), everything mod 2^32"""
-    return _fin(_fin(_fin((int(seed) + 0x9E3779B9) & _M) ^ (int(env_id) & _M)) ^ (int(draw_index) & _M))
 
 
 def check_world(grid_size, unit_size, n_foods):
@@ -170,98 +155,31 @@ class SnakeFactory:
         return SnakeEnv(**self.kw)
 
 
-def _env_id0(env_id0, B):
-    """first env id of a pool of B worlds: the kernels take ids as non-negative C ints"""
-    v = int(env_id0)
-    if v < 0 or v + int(B) > 0x7FFFFFFF:
-        raise ValueError(f"env_id0={env_id0}: env ids are 0 .. 2^31 - 1")
-    return v
-
-
-class DeviceSnakePool:
+class DeviceSnakePool(DeviceWorldPool):
     """``n_envs`` Snake worlds in device memory (the Runner's device-pool protocol).  Env j is the world
-    ``SnakeEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames.  ``needs_actions``: the Runner hands ``device_step`` the
-    address and stride of the int64 actions the sampler just wrote."""
-    needs_actions = True
+    ``SnakeEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames (with ``raw_frames`` also the raw RGB ones, ``rgb``)."""
+
+    MIN_ENVS = 0      # a pool of no worlds constructs and resets (a2c_snake_reset accepts B == 0), as it always did
 
     def __init__(self, n_envs, device="cuda", seed=0, grid_size=15, unit_size=4, n_foods=2, raw_frames=False, env_id0=0):
         import torch
         from . import ops
         self.G, self.u, self.n_foods = check_world(grid_size, unit_size, n_foods)
-        self.B, self.seed, self.device = int(n_envs), int(seed) & _M, torch.device(device)
-        self.env_id0 = _env_id0(env_id0, self.B)
         side = self.G * self.u
         self.frame_shape = (1, side, side)
-        self.HW = side * side
-        self.words = ops.snake_state_bytes(self.G, self.n_foods) // 4
-        dev = self.device
-        self.state = torch.zeros((self.B, self.words), dtype=torch.int32, device=dev)
-        self.frames = torch.zeros((self.B, self.HW), dtype=torch.float32, device=dev)
-        self.rgb = torch.zeros((self.B, side, side, 3), dtype=torch.uint8, device=dev) if raw_frames else None
-        self.rew, self.done, self.reset_mask = (torch.zeros(self.B, dtype=torch.float32, device=dev) for _ in range(3))
-        self.ep_stats = torch.zeros(2, dtype=torch.int32, device=dev)      # finished episodes, sum of their rewards
-        self.action_shift = 0
-        self.started = False
+        super().__init__(n_envs, device, seed, env_id0, ops.snake_state_bytes(self.G, self.n_foods) // 4)
+        self.rgb = torch.zeros((self.B, side, side, 3), dtype=torch.uint8, device=self.device) if raw_frames else None
 
-    def __len__(self):
-        return self.B
+    reset = DeviceWorldPool.reset_all
 
-    def reset(self, env_id0=None):
-        """(re)starts every world: state, frames (and raw frames) of the reset positions.  ``env_id0`` re-bases the pool
-        first: env j becomes world ``env_id0 + j``"""
+    def _reset(self):
         from . import ops
-        if env_id0 is not None:
-            self.env_id0 = _env_id0(env_id0, self.B)
         ops.snake_reset(self.state, self.B, self.env_id0, self.seed, self.G, self.u, self.n_foods, self.frames, self.rgb)
-        self.started = True
 
-    def start(self, runner):
-        import torch
+    def _step(self, head, out, frames, post, sl):
         from . import ops
-        self.action_shift = int(runner.hyps["action_shift"])
-        self.reset()
-        ones = torch.ones(self.B, dtype=torch.float32, device=self.device)
-        ops.frame_stack_push(self.frames, ones, runner.bookmark.data_ptr(), runner.S, runner.bookmark.data_ptr(), runner.S,
-                             self.B, runner.C, runner.HW)
-
-    def step(self, actions_ptr, act_stride, env0=0, B=None):
-        """advance envs env0..env0+B by the int64 actions at ``actions_ptr`` (element stride ``act_stride``)"""
-        from . import ops
-        B = self.B - env0 if B is None else B
-        if not self.started:
-            raise RuntimeError("DeviceSnakePool: reset() / start(runner) first")
-        if env0 < 0 or B < 1 or env0 + B > self.B:
-            raise ValueError("DeviceSnakePool: env range outside the pool")
-        sl = slice(env0, env0 + B)
-        ops.snake_step(self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0,
-                       self.seed, self.G, self.u, self.n_foods, self.rew[sl], self.done[sl], self.reset_mask[sl],
-                       self.frames[sl], None if self.rgb is None else self.rgb[sl], self.ep_stats)
-        return self.frames[sl], self.rew[sl], self.done[sl], self.reset_mask[sl]
-
-    def device_step(self, t, env0, B, actions=None):
-        if actions is None:
-            raise ValueError("DeviceSnakePool.device_step needs actions=(address, stride)")
-        return self.step(actions[0], actions[1], env0, B)
-
-    def device_step_post(self, t, env0, B, actions, post, frames=False):
-        """``device_step`` + the bookkeeping of env step ``t`` + the frame stack in ONE launch (a2c_snake_step_post): ``post`` is
-        an ``ops.world_post`` block.  The new frame goes into plane C - 1 of ``post.out``; ``self.frames`` is written as
-        well only with ``frames=True`` (the Runner does not read it).  -> (rew, done, reset)"""
-        from . import ops
-        if not self.started:
-            raise RuntimeError("DeviceSnakePool: reset() / start(runner) first")
-        if env0 < 0 or B < 1 or env0 + B > self.B:
-            raise ValueError("DeviceSnakePool: env range outside the pool")
-        sl = slice(env0, env0 + B)
-        ops.snake_step_post(self.state[sl], actions[0], actions[1], self.action_shift, B, self.env_id0 + env0,
-                            self.seed, self.G, self.u, self.n_foods, self.rew[sl], self.done[sl], self.reset_mask[sl],
-                            self.frames[sl] if frames else None, post, None if self.rgb is None else self.rgb[sl],
-                            self.ep_stats)
-        return self.rew[sl], self.done[sl], self.reset_mask[sl]
-
-    def episode_stats(self):
-        """(episodes finished, sum of their rewards) since the last call; one device read"""
-        n, s = (int(v) for v in self.ep_stats.tolist())
-        if n:
-            self.ep_stats.zero_()
-        return n, s
+        rgb = None if self.rgb is None else self.rgb[sl]
+        if post is None:
+            ops.snake_step(*head, self.G, self.u, self.n_foods, *out, frames, rgb, self.ep_stats)
+        else:
+            ops.snake_step_post(*head, self.G, self.u, self.n_foods, *out, frames, post, rgb, self.ep_stats)

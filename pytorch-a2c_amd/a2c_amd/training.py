@@ -21,7 +21,7 @@ from collections import deque
 import numpy as np
 import torch
 
-from . import models, preprocessing
+from . import breakout, models, pong, preprocessing, snake, worlds
 from .runner import DeviceStatsRunner, HostEnvPool, Runner, SequentialEnvironment, StatsRunner
 from .updater import Updater
 from .utils import cuda_if, deque_maxmin, try_key
@@ -44,6 +44,22 @@ def get_save_folder(hyps):
     folder = os.path.join(hyps["main_path"], hyps["exp_name"], f"{hyps['exp_name']}_{hyps['exp_num']}")
     os.makedirs(folder, exist_ok=True)
     return folder
+
+
+# The device-world families of train(), env_type "<family>-device" / "<family>-host": the module of a2c_amd, its preprocessor,
+# the "Pong" done override, the one-bit frame transport of the process pool ({0, 1} frames only), the names of what the
+# module's world_from_hyps returns (the world kwargs), and whether the family takes frame_skip / sticky_num / sticky_den.
+_WORLDS = {
+    "Snake": (snake, "snake_prep", False, False, ("grid_size", "unit_size", "n_foods"), False),
+    "Pong": (pong, "pong_prep", True, True, ("points_to_win", "max_episode_steps", "opp_skill_num", "opp_skill_den"), True),
+    "Breakout": (breakout, "breakout_prep", False, False, ("lives", "max_episode_steps"), True),
+}
+
+
+def _world_family(env_type):
+    """"Pong" of "Pong-device" / "Pong-host"; None for every other env_type"""
+    family, _, where = str(env_type).partition("-")
+    return family if family in _WORLDS and where in ("device", "host") else None
 
 
 class _PositionalFactory:
@@ -92,9 +108,8 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
             "Snake-device", "Pong-device", "Breakout-device")):
         raise ValueError("a2c_amd: hyps['eval_pool'] = 'device' evaluates the device worlds (env_type 'Snake-device', "
                          "'Pong-device' or 'Breakout-device') and takes no eval_env / env_fn")
-    if env_fn is None and hyps.get("env_type") in ("Snake-device", "Snake-host"):
-        from .pong import repeat_from_hyps
-        if repeat_from_hyps(hyps, "Snake")[:2] != (1, 0):
+    if env_fn is None and _world_family(hyps.get("env_type")) == "Snake":
+        if worlds.repeat_from_hyps(hyps, "Snake")[:2] != (1, 0):
             raise ValueError("a2c_amd: frame_skip / sticky_num are keys of the Pong and Breakout worlds: the Snake worlds "
                              "play one game frame per step")
     if hyps["n_rollouts"] is None:
@@ -114,79 +129,40 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     # environments
     serial = try_key(hyps, "env_pool", "process") == "serial"
     probe = None
-    snake_world = pong_world = breakout_world = None
-    if env_fn is None and hyps["env_type"] in ("Snake-device", "Snake-host"):
-        from . import snake
-        G, unit, n_foods = snake_world = snake.world_from_hyps(hyps)
-        hyps["prep_fxn"], hyps["preprocessor"] = "snake_prep", preprocessing.snake_prep
-        hyps["is_discrete"], n_act = True, snake.N_ACTIONS
+    family, raw = _world_family(hyps["env_type"]) if env_fn is None else None, False
+    if family is not None:
+        mod, prep_name, pong_done, bits, names, repeats = _WORLDS[family]
+        world = dict(zip(names, mod.world_from_hyps(hyps)), seed=hyps["seed"])
+        if family == "Breakout":
+            # device_prep: the workers hand on the RAW frames (null_prep) and a2c_frame_prep_u8 crops / strides them
+            raw = try_key(hyps, "device_prep", None) is not None
+            if raw and (hyps["device_prep"] != "breakout_prep" or hyps["env_type"] == "Breakout-device" or serial):
+                raise ValueError("a2c_amd: device_prep on Breakout worlds is 'breakout_prep', on env_type='Breakout-host' behind "
+                                 "the process env pool (the device worlds write prepped frames themselves)")
+        hyps["prep_fxn"] = "null_prep" if raw else prep_name
+        prep = hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
+        hyps["is_discrete"], n_act = True, mod.N_ACTIONS
         # a policy that circles never ends its evaluation episode: cap it (StatsRunner reads the key)
         hyps["max_eval_steps"] = try_key(hyps, "max_eval_steps", 2000)
-        world = dict(seed=hyps["seed"], grid_size=G, unit_size=unit, n_foods=n_foods)
-        mk_env = lambda j: SequentialEnvironment(hyps["env_type"], preprocessing.snake_prep, seed=hyps["seed"],
-                                                 env_fn=snake.SnakeFactory(env_id=j, **world))
-        if hyps["env_type"] == "Snake-device":
-            pool = snake.DeviceSnakePool(hyps["n_envs"], device=cuda_if(torch.zeros(1)).device, **world)
+        if repeats:
+            world.update(zip(("frame_skip", "sticky_num", "sticky_den"), worlds.repeat_from_hyps(hyps, family)))
+        factory, device_pool = getattr(mod, family + "Factory"), getattr(mod, "Device" + family + "Pool")
+        mk_env = lambda j: SequentialEnvironment(hyps["env_type"], getattr(preprocessing, prep_name), seed=hyps["seed"],
+                                                 env_fn=factory(env_id=j, **world))
+        side = world["grid_size"] * world["unit_size"] if family == "Snake" else None
+        world_shape = (1, side, side) if family == "Snake" else device_pool.frame_shape
+        if hyps["env_type"] == family + "-device":
+            pool = device_pool(hyps["n_envs"], device=cuda_if(torch.zeros(1)).device, **world)
         elif serial:
-            pool = HostEnvPool([mk_env(j) for j in range(hyps["n_envs"])], frame_shape=(1, G * unit, G * unit))
+            pool = HostEnvPool([mk_env(j) for j in range(hyps["n_envs"])], frame_shape=world_shape)
         else:
             from .hostpool import ProcessEnvPool
-            kws = [dict(env_type=hyps["env_type"], preprocessor=preprocessing.snake_prep, seed=hyps["seed"],
-                        env_fn=snake.SnakeFactory(env_id=j, **world)) for j in range(hyps["n_envs"])]
+            kws = [dict(env_type=hyps["env_type"], preprocessor=prep, seed=hyps["seed"], env_fn=factory(env_id=j, **world))
+                   for j in range(hyps["n_envs"])]
+            # frame_bits: {0, 1} uint8 planes cross the host link one bit per pixel; grey levels one byte per pixel
             pool = ProcessEnvPool(SequentialEnvironment, hyps["n_envs"], env_kwargs=kws,
-                                  n_workers=try_key(hyps, "n_env_workers", None), pong=False,
-                                  action_shift=try_key(hyps, "action_shift", 0), frame_bits=False)
-    elif env_fn is None and hyps["env_type"] in ("Pong-device", "Pong-host"):
-        from . import pong
-        pong_world = pong.world_from_hyps(hyps)
-        hyps["prep_fxn"], hyps["preprocessor"] = "pong_prep", preprocessing.pong_prep
-        hyps["is_discrete"], n_act = True, pong.N_ACTIONS
-        hyps["max_eval_steps"] = try_key(hyps, "max_eval_steps", 2000)
-        world = dict(zip(("points_to_win", "max_episode_steps", "opp_skill_num", "opp_skill_den"), pong_world),
-                     seed=hyps["seed"])
-        world.update(zip(("frame_skip", "sticky_num", "sticky_den"), pong.repeat_from_hyps(hyps)))
-        mk_env = lambda j: SequentialEnvironment(hyps["env_type"], preprocessing.pong_prep, seed=hyps["seed"],
-                                                 env_fn=pong.PongFactory(env_id=j, **world))
-        if hyps["env_type"] == "Pong-device":
-            pool = pong.DevicePongPool(hyps["n_envs"], device=cuda_if(torch.zeros(1)).device, **world)
-        elif serial:
-            pool = HostEnvPool([mk_env(j) for j in range(hyps["n_envs"])], frame_shape=pong.DevicePongPool.frame_shape)
-        else:
-            from .hostpool import ProcessEnvPool
-            kws = [dict(env_type=hyps["env_type"], preprocessor=preprocessing.pong_prep, seed=hyps["seed"],
-                        env_fn=pong.PongFactory(env_id=j, **world)) for j in range(hyps["n_envs"])]
-            # pong_prep yields {0,1} uint8 planes: one bit per pixel crosses the host link
-            pool = ProcessEnvPool(SequentialEnvironment, hyps["n_envs"], env_kwargs=kws,
-                                  n_workers=try_key(hyps, "n_env_workers", None), pong=True,
-                                  action_shift=try_key(hyps, "action_shift", 0), frame_bits=True)
-    elif env_fn is None and hyps["env_type"] in ("Breakout-device", "Breakout-host"):
-        from . import breakout
-        breakout_world = breakout.world_from_hyps(hyps)
-        # device_prep: the workers hand on the RAW frames (null_prep) and a2c_frame_prep_u8 crops / strides them
-        raw = try_key(hyps, "device_prep", None) is not None
-        if raw and (hyps["device_prep"] != "breakout_prep" or hyps["env_type"] == "Breakout-device" or serial):
-            raise ValueError("a2c_amd: device_prep on Breakout worlds is 'breakout_prep', on env_type='Breakout-host' behind "
-                             "the process env pool (the device worlds write prepped frames themselves)")
-        hyps["prep_fxn"] = "null_prep" if raw else "breakout_prep"
-        prep = hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
-        hyps["is_discrete"], n_act = True, breakout.N_ACTIONS
-        hyps["max_eval_steps"] = try_key(hyps, "max_eval_steps", 2000)
-        world = dict(zip(("lives", "max_episode_steps"), breakout_world), seed=hyps["seed"])
-        world.update(zip(("frame_skip", "sticky_num", "sticky_den"), breakout.repeat_from_hyps(hyps)))
-        mk_env = lambda j: SequentialEnvironment(hyps["env_type"], preprocessing.breakout_prep, seed=hyps["seed"],
-                                                 env_fn=breakout.BreakoutFactory(env_id=j, **world))
-        if hyps["env_type"] == "Breakout-device":
-            pool = breakout.DeviceBreakoutPool(hyps["n_envs"], device=cuda_if(torch.zeros(1)).device, **world)
-        elif serial:
-            pool = HostEnvPool([mk_env(j) for j in range(hyps["n_envs"])], frame_shape=breakout.DeviceBreakoutPool.frame_shape)
-        else:
-            from .hostpool import ProcessEnvPool
-            kws = [dict(env_type=hyps["env_type"], preprocessor=prep, seed=hyps["seed"],
-                        env_fn=breakout.BreakoutFactory(env_id=j, **world)) for j in range(hyps["n_envs"])]
-            # grey levels 0..255: one byte per pixel crosses the host link (the packed one-bit transport does not apply)
-            pool = ProcessEnvPool(SequentialEnvironment, hyps["n_envs"], env_kwargs=kws,
-                                  n_workers=try_key(hyps, "n_env_workers", None), pong=False,
-                                  action_shift=try_key(hyps, "action_shift", 0), frame_bits=False)
+                                  n_workers=try_key(hyps, "n_env_workers", None), pong=pong_done,
+                                  action_shift=try_key(hyps, "action_shift", 0), frame_bits=bits)
     elif env_fn is None:
         hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
         probe = eval_env or SequentialEnvironment(**hyps)             # the probe for shapes (training.py:60-65)
@@ -207,7 +183,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     f32_dim = None
     if not hyps["is_discrete"] and not serial:
         f32_dim = int(n_act if env_fn is None else hyps["action_size"])
-    if snake_world is not None or pong_world is not None or breakout_world is not None:
+    if family is not None:
         pass
     elif env_fn is None:
         kws = [dict({k: v for k, v in hyps.items() if k != "seed"}, seed=hyps["seed"] + j) for j in range(hyps["n_envs"])]
@@ -234,8 +210,8 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                                   probe_reset=True, frame_bits=bool(try_key(hyps, "frame_bits", False)), action_dim=f32_dim)
         n_act = hyps["action_size"]
     hyps["state_shape"] = [hyps["n_frame_stack"]] + list(pool.frame_shape[1:])
-    if breakout_world is not None and raw:      # the pool carries raw frames: the states are what the device makes of them
-        hyps["state_shape"] = [hyps["n_frame_stack"]] + list(breakout.DeviceBreakoutPool.frame_shape[1:])
+    if raw:      # the pool carries raw frames: the states are what the device makes of them
+        hyps["state_shape"] = [hyps["n_frame_stack"]] + list(world_shape[1:])
     if hyps["env_type"] == "Pong-v0":
         action_size, hyps["action_shift"] = 3, 1                      # training.py:67-69
     else:
@@ -293,7 +269,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                                          uniform_fn=uniform_fn)
     elif eval_env is not None:
         stats_runner = StatsRunner(hyps, env=eval_env)
-    elif snake_world is not None or pong_world is not None or breakout_world is not None:
+    elif family is not None:
         # host twins of worlds the training pool does not play (env ids from 10007 on)
         stats_runner = StatsRunner(hyps, envs=[mk_env(10007 + j) for j in range(try_key(hyps, "n_test_eps", 15))])
     else:

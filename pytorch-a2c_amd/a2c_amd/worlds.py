@@ -1,0 +1,217 @@
+"""What the worlds that can live in HBM (snake.py, pong.py, breakout.py) share on the Python side: the counter-based draws,
+the bounds of frame skip and sticky actions, ``HostWorld`` -- the agent step of the host twins ``PongEnv`` / ``BreakoutEnv`` --
+and ``DeviceWorldPool``, the Runner's device-pool protocol over ``n_envs`` worlds in device memory (the kernels' side:
+csrc/world.h)."""
+import functools
+
+_M = 0xFFFFFFFF
+MAX_FRAME_SKIP, MAX_STICKY_DEN = 8, 1 << 16
+
+
+def _fin(x):
+    """the integer finaliser (lowbias32): x ^= x>>16; x *= 0x7FEB352D; x ^= x>>15; x *= 0x846CA68B; x ^= x>>16 (mod 2^32)"""
+    x &= _M
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & _M
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & _M
+    x ^= x >> 16
+    return x
+
+
+def hash32(seed, env_id, draw_index):
+    """fin(fin(fin(seed + 0x9E3779B9) ^ env_id) ^ draw_index), everything mod 2^32"""
+    return _fin(_fin(_fin((int(seed) + 0x9E3779B9) & _M) ^ (int(env_id) & _M)) ^ (int(draw_index) & _M))
+
+
+def _env_id0(env_id0, B):
+    """first env id of a pool of B worlds: the kernels take ids as non-negative C ints"""
+    v = int(env_id0)
+    if v < 0 or v + int(B) > 0x7FFFFFFF:
+        raise ValueError(f"env_id0={env_id0}: env ids are 0 .. 2^31 - 1")
+    return v
+
+
+def _clamp(v, lo, hi):
+    return lo if v < lo else (hi if v > hi else v)
+
+
+def _i32(v):
+    """a 32-bit word as the signed int the device stores"""
+    v &= _M
+    return v - (1 << 32) if v >> 31 else v
+
+
+def check_repeat(frame_skip=1, sticky_num=0, sticky_den=1, what="Pong"):
+    """the bounds a2c_<world>_step_skip enforces (A2C_ERR_ARG) on frame skip and sticky actions: same ones for the host
+    twins -> (frame_skip, sticky_num, sticky_den)"""
+    k, n, d = int(frame_skip), int(sticky_num), int(sticky_den)
+    if not (1 <= k <= MAX_FRAME_SKIP and 1 <= d <= MAX_STICKY_DEN and 0 <= n <= d):
+        raise ValueError(f"{what}: unsupported frame_skip={k} sticky={n}/{d} (1 <= frame_skip <= {MAX_FRAME_SKIP}, "
+                         f"1 <= sticky_den <= {MAX_STICKY_DEN}, 0 <= sticky_num <= sticky_den)")
+    return k, n, d
+
+
+def repeat_from_hyps(hyps, what="Pong"):
+    """(frame_skip, sticky_num, sticky_den) from the hyps (1, 0, 1 where absent); ValueError outside the bounds"""
+    get = lambda k, dflt: dflt if hyps.get(k) is None else hyps[k]
+    return check_repeat(get("frame_skip", 1), get("sticky_num", 0), get("sticky_den", 1), what)
+
+
+class HostWorld:
+    """The gym-like surface and the AGENT step of the host twins of the register worlds (csrc/world.h):
+    ``frame_skip`` game frames with sticky actions (the module docstrings of pong.py / breakout.py state the rule).  A
+    subclass supplies ``WHAT`` (its name in messages), ``N_ACTIONS``, ``new_episode()``, ``_frame(a)`` -> (reward, done),
+    ``render_rgb()`` and, where an agent step has an invariant, ``_check_step(total)``."""
+    WHAT, N_ACTIONS = "World", 1
+
+    def __init__(self, seed, env_id, frame_skip, sticky_num, sticky_den, events):
+        self.frame_skip, self.sticky_num, self.sticky_den = check_repeat(frame_skip, sticky_num, sticky_den, self.WHAT)
+        self.prev = 0
+        self.seed_, self.env_id = int(seed) & _M, int(env_id)
+        self.draws = self.steps = self.ep_steps = 0
+        self.over = True
+        self.events = dict.fromkeys(events, 0)
+        if (self.frame_skip, self.sticky_num) != (1, 0):      # a plain world can neither cut nor keep an action
+            self.events.update(cut=0, sticky=0)
+
+    def seed(self, seed):
+        self.seed_ = int(seed) & _M
+
+    def _draw(self):
+        d = hash32(self.seed_, self.env_id, self.draws)
+        self.draws = (self.draws + 1) & _M
+        return d
+
+    # ---- gym surface
+    def reset(self):
+        self.new_episode()
+        return self.render_rgb()
+
+    def step(self, action):
+        rew, done = self.advance(action)
+        return self.render_rgb(), rew, done, {}
+
+    def render(self):
+        return self.render_rgb()
+
+    def advance(self, action):
+        """the agent step without its frame: ``frame_skip`` game frames -> (summed reward, done)"""
+        if self.over:
+            raise RuntimeError(f"{self.WHAT}Env.step() after done: call reset()")
+        a = int(action) % self.N_ACTIONS
+        total, done = 0.0, False
+        for s in range(self.frame_skip):
+            x = a
+            if self.sticky_num > 0:
+                if self._draw() % self.sticky_den < self.sticky_num:
+                    x = self.prev
+                    self.events["sticky"] += x != a
+                self.prev = x
+            rew, done = self._frame(x)
+            total += rew
+            if done:
+                self.prev = 0
+                if s < self.frame_skip - 1:
+                    self.events["cut"] += 1
+                break
+        self._check_step(total)
+        return total, done
+
+    def _check_step(self, total):
+        pass
+
+
+class WorldFactory:
+    """picklable ``env_fn`` for ``SequentialEnvironment`` / the env worker processes: ``env(env_id=..., **world)``"""
+
+    def __init__(self, env, env_id=0, **world):
+        self.env, self.kw = env, dict(world, env_id=env_id)
+
+    def __call__(self, *a, **k):
+        return self.env(**self.kw)
+
+
+def factory_of(env):
+    """``WorldFactory`` with its env class bound: ``factory_of(PongEnv)(env_id=3, seed=1)()`` is a ``PongEnv``"""
+    return functools.partial(WorldFactory, env)
+
+
+class DeviceWorldPool:
+    """``n_envs`` worlds in device memory (the Runner's device-pool protocol: ``start`` / ``device_step`` /
+    ``device_step_post``).  ``needs_actions``: the Runner hands ``device_step`` the address and stride of the int64 actions the
+    sampler just wrote.  A subclass checks its world in ``__init__``, sets ``frame_shape`` and makes the library calls in
+    ``_reset()`` and ``_step(head, out, frames, post, sl)``."""
+    needs_actions = True
+    MIN_ENVS = 1
+
+    def __init__(self, n_envs, device, seed, env_id0, words):
+        import torch
+        self.B, self.seed, self.device = int(n_envs), int(seed) & _M, torch.device(device)
+        if self.B < self.MIN_ENVS:
+            raise ValueError(f"{type(self).__name__}: n_envs >= {self.MIN_ENVS}")
+        self.env_id0 = _env_id0(env_id0, self.B)
+        self.HW = self.frame_shape[1] * self.frame_shape[2]
+        self.words = words
+        dev = self.device
+        self.state = torch.zeros((self.B, self.words), dtype=torch.int32, device=dev)
+        self.frames = torch.zeros((self.B, self.HW), dtype=torch.float32, device=dev)
+        self.rew, self.done, self.reset_mask = (torch.zeros(self.B, dtype=torch.float32, device=dev) for _ in range(3))
+        self.ep_stats = torch.zeros(2, dtype=torch.int32, device=dev)      # dones, sum of the rewards they closed
+        self.action_shift = 0
+        self.started = False
+
+    def __len__(self):
+        return self.B
+
+    def reset_all(self, env_id0=None):
+        """(re)starts every world: counters to 0, then the reset draws; state and frames of the reset positions.  ``env_id0``
+        re-bases the pool first: env j becomes world ``env_id0 + j``"""
+        if env_id0 is not None:
+            self.env_id0 = _env_id0(env_id0, self.B)
+        self._reset()
+        self.started = True
+
+    def start(self, runner):
+        import torch
+        from . import ops
+        self.action_shift = int(runner.hyps["action_shift"])
+        self.reset_all()
+        ones = torch.ones(self.B, dtype=torch.float32, device=self.device)
+        ops.frame_stack_push(self.frames, ones, runner.bookmark.data_ptr(), runner.S, runner.bookmark.data_ptr(), runner.S,
+                             self.B, runner.C, runner.HW)
+
+    def _launch(self, actions_ptr, act_stride, env0, B, frames, post):
+        """one launch over envs env0..env0+B: the arguments every world's step begins with, and its three outputs"""
+        if not self.started:
+            raise RuntimeError(f"{type(self).__name__}: reset_all() / start(runner) first")
+        if env0 < 0 or B < 1 or env0 + B > self.B:
+            raise ValueError(f"{type(self).__name__}: env range outside the pool")
+        sl = slice(env0, env0 + B)
+        head = (self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0, self.seed)
+        out = (self.rew[sl], self.done[sl], self.reset_mask[sl])
+        self._step(head, out, self.frames[sl] if frames else None, post, sl)
+        return out
+
+    def step(self, actions_ptr, act_stride, env0=0, B=None):
+        """advance envs env0..env0+B by the int64 actions at ``actions_ptr`` (element stride ``act_stride``)"""
+        B = self.B - env0 if B is None else B
+        return (self.frames[env0:env0 + B],) + self._launch(actions_ptr, act_stride, env0, B, True, None)
+
+    def device_step(self, t, env0, B, actions=None):
+        if actions is None:
+            raise ValueError(f"{type(self).__name__}.device_step needs actions=(address, stride)")
+        return self.step(actions[0], actions[1], env0, B)
+
+    def device_step_post(self, t, env0, B, actions, post, frames=False):
+        """``device_step`` + the bookkeeping of env step ``t`` + the frame stack in ONE launch (a2c_<world>_step_post): ``post``
+        is an ``ops.world_post`` block.  The new frame goes into plane C - 1 of ``post.out``; ``self.frames`` is written as
+        well only with ``frames=True`` (the Runner does not read it).  -> (rew, done, reset)"""
+        return self._launch(actions[0], actions[1], env0, B, frames, post)
+
+    def episode_stats(self):
+        """(dones, sum of the rewards they closed) since the last call; one device read"""
+        n, s = (int(v) for v in self.ep_stats.tolist())
+        if n:
+            self.ep_stats.zero_()
+        return n, s

@@ -101,54 +101,3 @@ __device__ __forceinline__ float a2c_td_delta(float prev_rew, float prev_done, f
   const float gv = __fmul_rn(gamma, val);
   return __fsub_rn(__fadd_rn(prev_rew, __fmul_rn(gv, __fsub_rn(1.f, prev_done))), prev_val);
 }
-
-// ---- a2c_<world>_step_post (snake.hip, pong.hip, breakout.hip): what the three fused world kernels share.
-// One workgroup of WORLD_POST_WAVES wavefronts per env (why 4: DESIGN.md section 6e).
-constexpr int WORLD_POST_WAVES = 4, WORLD_POST_THREADS = 64 * WORLD_POST_WAVES;
-
-// the launcher's checks of the argument block (HW: floats of one plane of this world)
-static inline bool a2c_world_post_ok(const a2c_world_post* p, int64_t HW) {
-  if (p == nullptr || p->val == nullptr || p->val_prev == nullptr || p->rewards == nullptr || p->dones == nullptr ||
-      p->deltas == nullptr || p->prev == nullptr || p->out == nullptr)
-    return false;
-  if (p->T < 1 || p->t < 0 || p->t >= p->T || p->C < 1) return false;
-  if (p->prev_stride % 4 != 0 || p->out_stride % 4 != 0 || p->prev_stride < p->C * HW || p->out_stride < p->C * HW) return false;
-  if ((((uintptr_t)p->out | (uintptr_t)p->prev) & 15u) != 0 || p->out == p->prev) return false;
-  return p->h == nullptr || p->hdim >= 1;
-}
-
-// the effective done of the step: the world's done, or any non-zero reward for a "Pong" env type
-__device__ __forceinline__ float world_post_done(const a2c_world_post& p, float r, float done) {
-  return (done != 0.f || (p.pong && r != 0.f)) ? 1.f : 0.f;
-}
-
-// One lane: rewards / dones / deltas / val_prev of env b, what record_kernel and post_kernel of rollout_ops.hip do (the
-// delta is a2c_td_delta, the body all of them share)
-__device__ __forceinline__ void world_post_book(const a2c_world_post& p, int b, float r, float d) {
-  const long e = (long)(p.slot0 + b) * p.T + p.t;
-  p.rewards[e] = r;
-  p.dones[e] = d;
-  if (p.done_eff_out != nullptr) p.done_eff_out[b] = d;
-  const float v = p.val[(long)b * p.val_stride];
-  if (p.t > 0) p.deltas[e - 1] = a2c_td_delta(p.rewards[e - 1], p.dones[e - 1], p.gamma, v, p.val_prev[b]);
-  p.val_prev[b] = v;
-}
-
-// All WORLD_POST_THREADS lanes: the hidden row of an env whose step closed is zeroed (zero_done_rows_kernel), and planes
-// 0 .. C-2 of out[b] = reset ? 0 : planes 1 .. C-1 of prev[b], one contiguous run of (C - 1) * HW floats as 16-byte accesses.
-// -> where the world renders plane C - 1
-__device__ __forceinline__ float* world_post_planes(const a2c_world_post& p, int b, float d, bool rst, int HW, int tid) {
-  if (p.h != nullptr && d != 0.f)
-    for (int i = tid; i < p.hdim; i += WORLD_POST_THREADS) p.h[(long)b * p.hdim + i] = 0.f;
-  float* __restrict__ o = p.out + (long)b * p.out_stride;
-  const int n4 = ((p.C - 1) * HW) >> 2;
-  float4* __restrict__ o4 = reinterpret_cast<float4*>(o);
-  if (rst) {
-    for (int i = tid; i < n4; i += WORLD_POST_THREADS) o4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  } else {
-    const float4* __restrict__ s4 = reinterpret_cast<const float4*>(p.prev + (long)b * p.prev_stride + HW);
-#pragma unroll 8
-    for (int i = tid; i < n4; i += WORLD_POST_THREADS) o4[i] = s4[i];
-  }
-  return o + (long)(p.C - 1) * HW;
-}

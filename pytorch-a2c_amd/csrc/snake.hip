@@ -4,22 +4,16 @@
 // head holds the length), kept in HBM between launches and worked on in LDS: a step is one pass over the cells, a food
 // placement one ballot/popcount pass that finds the k-th free cell in row-major order (no rejection loop).  The draw and
 // step counters are part of the state the kernel advances, so a captured launch plays NEW steps at every replay.  The
-// prepped frame row (snake_prep's values) is written as 16-byte stores where the frame-stack kernel reads it.
-#include "a2c_common.h"
+// prepped frame row (snake_prep's values) is written as 16-byte stores where the frame-stack kernel reads it.  The draws
+// (world_hash) and the a2c_snake_step_post helpers come from world.h; the kernels are this file's own, because the cells live
+// in LDS and the step is cooperative.
+#include "world.h"
 
 namespace {
 
 constexpr int SNAKE_HDR = 8;        // int32 words in front of the cells: head row, head col, length, draws, steps, episode reward
 constexpr int SNAKE_MAX_G = 32;
 constexpr int SNAKE_MAX_CELLS = SNAKE_MAX_G * SNAKE_MAX_G;
-
-__device__ __forceinline__ uint32_t snake_fin(uint32_t x) {       // lowbias32
-  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ uint32_t snake_hash(uint32_t seed, uint32_t env, uint32_t draw) {
-  return snake_fin(snake_fin(snake_fin(seed + 0x9E3779B9u) ^ env) ^ draw);
-}
 
 // food on the k-th free cell in row-major order (k < number of free cells); the whole wave calls it
 __device__ __forceinline__ void snake_place_food(int* s, int NC, uint32_t k, int lane) {
@@ -47,8 +41,8 @@ __device__ __forceinline__ void snake_place_food(int* s, int NC, uint32_t k, int
 __device__ __forceinline__ void snake_new_episode(int* s, int G, int NC, int n_foods, uint32_t seed, uint32_t env,
                                                   uint32_t& draws, int& hr, int& hc, int& len, int lane) {
   for (int i = lane; i < NC; i += 64) s[i] = 0;
-  const int h = (int)(snake_hash(seed, env, draws++) & 3u);
-  const int k = (int)(snake_hash(seed, env, draws++) % (uint32_t)((G - 2) * G));
+  const int h = (int)(world_hash(seed, env, draws++) & 3u);
+  const int k = (int)(world_hash(seed, env, draws++) % (uint32_t)((G - 2) * G));
   const int a = k / G, b = k % G;
   const int dr = h == 0 ? -1 : (h == 2 ? 1 : 0), dc = h == 1 ? 1 : (h == 3 ? -1 : 0);
   hr = h == 0 ? a : (h == 2 ? a + 2 : b);
@@ -58,7 +52,7 @@ __device__ __forceinline__ void snake_new_episode(int* s, int G, int NC, int n_f
   if (lane < 3) s[(hr - lane * dr) * G + (hc - lane * dc)] = 3 - lane;
   __syncthreads();
   for (int i = 0; i < n_foods; ++i)
-    snake_place_food(s, NC, snake_hash(seed, env, draws++) % (uint32_t)(NC - 3 - i), lane);
+    snake_place_food(s, NC, world_hash(seed, env, draws++) % (uint32_t)(NC - 3 - i), lane);
 }
 
 __device__ __forceinline__ float snake_prep_value(int v, int len) {
@@ -138,7 +132,7 @@ __device__ __forceinline__ float snake_advance(int* s, const int32_t* st, SnakeH
     __syncthreads();
     const int n_free = NC - h.len - (n_foods - 1);
     if (n_free == 0) over = true;    // the grid is full
-    else snake_place_food(s, NC, snake_hash(seed, env, h.draws++) % (uint32_t)n_free, lane);
+    else snake_place_food(s, NC, world_hash(seed, env, h.draws++) % (uint32_t)n_free, lane);
   } else {                           // plain move: every occupied cell ages, the tail cell is vacated
     for (int i = lane; i < NC; i += 64) {
       const int c = s[i];
