@@ -1038,6 +1038,38 @@ int a2c_breakout_step_post_skip(int32_t *state, const int64_t *actions, int64_t 
                                 float *rew, float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, int frame_skip,
                                 int sticky_num, int sticky_den, const a2c_world_post *post, a2c_stream_t stream);
 
+/* ------------------------------------------------------------------ random frame skip, episodic life, reward clipping
+ * The rest of what Pong-v0 and the usual wrappers do around ALE, as one block and one entry point
+ * per world: a2c_<world>_step_rules(<the arguments of a2c_<world>_step>, rules, post, stream).  post == NULL is the step
+ * of a2c_<world>_step_skip (frames must be given), else that of a2c_<world>_step_post_skip; with frame_skip_max ==
+ * frame_skip and both flags 0 the call IS that entry point: same checks, same kernel.  Otherwise
+ *   1. frame_skip_max > frame_skip: the agent step first takes ONE draw d (before its first sticky draw) and plays
+ *      k = frame_skip + d mod (frame_skip_max - frame_skip + 1) game frames.  k is not kept anywhere.
+ *   2. episodic_life (Breakout): a game frame that loses a life without ending the episode closes the agent step as an
+ *      episode end does -- word 17 = 0, the remaining frames dropped, done = reset = 1 (with post: the C - 1 older planes
+ *      and the hidden row are zeroed) -- but the world is NOT restarted: bricks, lives, the episode-step word and its
+ *      limit carry on, and `frames` shows the ball as just served.  ep_count / ep_rew_sum count these closes too, with the
+ *      reward since the previous close (word 10 is zeroed by every close).
+ *   3. clip_rewards (Breakout): rew (and, with post, rewards[]) is the sign of the agent step's summed reward; word 10
+ *      and ep_rew_sum keep booking the sum itself.
+ * A2C_ERR_ARG without a launch, besides what a2c_<world>_step_skip / _step_post_skip reject: a NULL rules,
+ * frame_skip_max outside frame_skip .. 8, a flag that is neither 0 nor 1, either flag set for Pong (a point closes every
+ * step there already, and |rew| <= 1).                                                                                   */
+typedef struct {
+  int32_t frame_skip, frame_skip_max;   /* game frames per agent step: frame_skip .. frame_skip_max, drawn per step    */
+  int32_t sticky_num, sticky_den;
+  int32_t episodic_life, clip_rewards;  /* 0 or 1; Breakout only                                                       */
+} a2c_world_rules;
+
+int a2c_pong_step_rules(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                        uint32_t seed, int points_to_win, int max_episode_steps, int opp_skill_num, int opp_skill_den,
+                        float *frames, int64_t frame_ld, float *rew, float *done, float *reset, int32_t *ep_count,
+                        int32_t *ep_rew_sum, const a2c_world_rules *rules, const a2c_world_post *post, a2c_stream_t stream);
+int a2c_breakout_step_rules(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                            uint32_t seed, int lives, int max_episode_steps, float *frames, int64_t frame_ld, float *rew,
+                            float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_rules *rules,
+                            const a2c_world_post *post, a2c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

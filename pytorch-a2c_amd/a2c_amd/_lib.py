@@ -6,7 +6,7 @@ non-CUDA tensor, this module raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liba2c_mi355x.so")
@@ -60,9 +60,16 @@ class WorldPost(Structure):
                 ("done_eff_out", P), ("h", P), ("hdim", c_int)]
 
 
+class WorldRules(Structure):
+    """a2c_world_rules"""
+    _fields_ = [("frame_skip", c_int32), ("frame_skip_max", c_int32), ("sticky_num", c_int32), ("sticky_den", c_int32),
+                ("episodic_life", c_int32), ("clip_rewards", c_int32)]
+
+
 PS = POINTER(A3CStepArgs)
 PR = POINTER(A3CRolloutArgs)
 PW = POINTER(WorldPost)
+PU = POINTER(WorldRules)
 
 # name -> (restype, argtypes); one entry per prototype in include/a2c_mi355x.h
 SIGNATURES = {
@@ -223,6 +230,10 @@ SIGNATURES = {
                                        c_int, c_int, c_int, P]),
     "a2c_breakout_step_post_skip": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P,
                                             P, c_int, c_int, c_int, PW, P]),
+    "a2c_pong_step_rules": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, c_int, c_int, P, c_int64, P, P, P,
+                                    P, P, PU, PW, P]),
+    "a2c_breakout_step_rules": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P, P,
+                                        PU, PW, P]),
 }
 
 _lib = None

@@ -42,11 +42,22 @@ frame executed, state word 17) if ``d mod sticky_den < sticky_num``; prev = x; t
 added to the agent step's (several bricks may fall in one agent step).  A frame that ends the episode zeroes ``prev``
 and the remaining frames are DROPPED (``events["cut"]``).  ``steps``, ``ep_steps`` and ``max_episode_steps`` count game
 frames.  With ``sticky_num == 0`` no draw is taken and ``prev`` stays 0: k = 1 is the world above word for word, k > 1 is
-that world stepped k times with one action and cut at the done."""
+that world stepped k times with one action and cut at the done.
+
+Random frame skip, episodic life, reward clipping (a2c_breakout_step_rules):
+  * ``frame_skip_max`` (``frame_skip`` .. 8; None = ``frame_skip``): above ``frame_skip`` the agent step first takes ONE draw
+    ``d``, before its first sticky draw, and plays k = frame_skip + d mod (frame_skip_max - frame_skip + 1) game frames;
+  * ``episodic_life``: a game frame that loses a life WITHOUT ending the episode (rule 5; rule 6 has already served the
+    ball) closes the agent step as an episode end does: prev = 0, the remaining frames dropped (``events["cut"]``;
+    ``events["life_close"]`` counts the closes), done = 1, ``ep_rew`` zeroed.  The world is not restarted: bricks, lives,
+    ``ep_steps`` and its limit carry on, and the ``reset()`` that follows such a done continues the game -- no draw, no
+    word changed, the current frame (``continue_episode()`` is its frameless form; ``new_episode()`` stays the full restart);
+  * ``clip_rewards``: the agent step's reward is the sign of its sum; ``ep_rew`` keeps the sum itself."""
 import numpy as np
 
 from . import worlds
-from .worlds import _M, DeviceWorldPool, HostWorld, _clamp, _env_id0, _i32, check_repeat, factory_of, hash32  # noqa: F401
+from .worlds import (_M, DeviceWorldPool, HostWorld, _clamp, _env_id0, _i32, check_repeat, check_rules, factory_of,  # noqa: F401
+                     hash32)
 
 N_ACTIONS = 4
 W, H = 72, 80
@@ -79,14 +90,25 @@ def repeat_from_hyps(hyps):
     return worlds.repeat_from_hyps(hyps, "Breakout")
 
 
-def check_world(lives=5, max_episode_steps=10000, frame_skip=1, sticky_num=0, sticky_den=1):
-    """the bounds a2c_breakout_step / a2c_breakout_step_skip enforce (A2C_ERR_ARG): same ones for the host twin"""
+def check_world(lives=5, max_episode_steps=10000, frame_skip=1, sticky_num=0, sticky_den=1, frame_skip_max=None,
+                episodic_life=False, clip_rewards=False):
+    """the bounds a2c_breakout_step / a2c_breakout_step_skip / a2c_breakout_step_rules enforce (A2C_ERR_ARG): same ones for the
+    host twin"""
     n, m = int(lives), int(max_episode_steps)
     check_repeat(frame_skip, sticky_num, sticky_den, "Breakout")
+    check_rules(frame_skip, frame_skip_max, episodic_life, clip_rewards, "Breakout", flags=True)
     if not (1 <= n <= MAX_LIVES and 1 <= m <= MAX_EPISODE_STEPS):
         raise ValueError(f"Breakout: unsupported world lives={n} max_episode_steps={m} (1 <= lives <= {MAX_LIVES}, "
                          f"1 <= max_episode_steps <= {MAX_EPISODE_STEPS})")
     return n, m
+
+
+RULE_KEYS = worlds.RULE_KEYS
+
+
+def rules_from_hyps(hyps):
+    """{frame_skip_max, episodic_life, clip_rewards} from the hyps (frame_skip, False, False where absent)"""
+    return worlds.rules_from_hyps(hyps, "Breakout", RULE_KEYS)
 
 
 def world_from_hyps(hyps):
@@ -105,14 +127,22 @@ class BreakoutEnv(HostWorld):
     the caller does -- the Runner does, which yields exactly what the device world returns.  ``events`` counts what
     happened (with frame skip or sticky actions also ``cut``: episode ends that dropped game frames of their agent step, and
     ``sticky``: game frames that kept an action other than the requested one) for tests that must see every rule at work.  ``step`` / ``advance`` are the AGENT
-    step: ``frame_skip`` game frames (module docstring)."""
+    step: ``frame_skip`` .. ``frame_skip_max`` game frames; with ``episodic_life`` its done is also a lost life, which
+    ``reset()`` answers by continuing the game, and with ``clip_rewards`` its reward is a sign (module docstring)."""
     WHAT, N_ACTIONS = "Breakout", N_ACTIONS
     action_space = _ActionSpace()
 
-    def __init__(self, seed=0, env_id=0, lives=5, max_episode_steps=10000, frame_skip=1, sticky_num=0, sticky_den=1):
+    def __init__(self, seed=0, env_id=0, lives=5, max_episode_steps=10000, frame_skip=1, sticky_num=0, sticky_den=1,
+                 frame_skip_max=None, episodic_life=False, clip_rewards=False):
         self.lives, self.max_episode_steps = check_world(lives, max_episode_steps)
+        _, self.episodic_life, self.clip_rewards = check_rules(frame_skip, frame_skip_max, episodic_life, clip_rewards,
+                                                               "Breakout", flags=True)
         super().__init__(seed, env_id, frame_skip, sticky_num, sticky_den,
-                         ("side_wall", "ceiling", "brick", "speed_up", "paddle_hit", "life_lost", "cleared", "episode_end"))
+                         ("side_wall", "ceiling", "brick", "speed_up", "paddle_hit", "life_lost", "cleared", "episode_end"),
+                         frame_skip_max)
+        if self.episodic_life:
+            self.events.update(cut=0, sticky=0, life_close=0)
+        self._lost = False              # the last game frame lost a life
         self.paddle_x = PADDLE_START_X
         self.ball_x, self.ball_y, self.vx, self.vy = SERVE_X0, SERVE_Y, 1, -1
         self.lives_left, self.bricks_left, self.rows = self.lives, N_BRICKS, [FULL_ROW] * BRICK_ROWS
@@ -129,7 +159,19 @@ class BreakoutEnv(HostWorld):
         self.ep_steps = self.ep_rew = self.prev = 0
         self.paddle_x = PADDLE_START_X
         self._serve()
-        self.over = False
+        self.over = self.closed = False
+
+    def _closes(self):
+        """episodic life: the game frame lost a life and the episode goes on"""
+        if not (self.episodic_life and self._lost):
+            return False
+        self.ep_rew = 0
+        self.events["life_close"] += 1
+        return True
+
+    def advance(self, action):
+        total, done = super().advance(action)
+        return (float((total > 0) - (total < 0)) if self.clip_rewards else total), done
 
     def _frame(self, a):
         """one game frame with action ``a`` in 0..3 -> (reward, done)"""
@@ -172,7 +214,7 @@ class BreakoutEnv(HostWorld):
             self.events["paddle_hit"] += 1
         self.ball_x, self.ball_y = x, y
         # 5. a life
-        lost = y > LOST_Y
+        lost = self._lost = y > LOST_Y
         if lost:
             self.lives_left -= 1
             self.events["life_lost"] += 1
@@ -232,7 +274,7 @@ class BreakoutEnv(HostWorld):
             setattr(self, k, v & _M if k == "draws" else v)
         self.rows = [v & FULL_ROW for v in w[len(WORD_NAMES):len(WORD_NAMES) + BRICK_ROWS]]
         self.prev = w[PREV_WORD]
-        self.over = False
+        self.over = self.closed = False
 
 
 # picklable ``env_fn``: ``BreakoutFactory(env_id=j, **world)()`` is a ``BreakoutEnv``
@@ -242,17 +284,22 @@ BreakoutFactory = factory_of(BreakoutEnv)
 class DeviceBreakoutPool(DeviceWorldPool):
     """``n_envs`` Breakout worlds in device memory (the Runner's device-pool protocol).  Env j is the world
     ``BreakoutEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames; with ``frame_skip`` / ``sticky_num`` /
-    ``sticky_den`` other than (1, 0, .) a step is an agent step of a2c_breakout_step_skip.
-    ``device_step`` returns ``done`` and ``reset`` as two tensors holding the same values, the real done.  ``episode_stats``
-    counts the finished episodes and sums their rewards."""
+    ``sticky_den`` other than (1, 0, .) a step is an agent step of a2c_breakout_step_skip, with
+    ``frame_skip_max`` / ``episodic_life`` / ``clip_rewards`` other than (frame_skip, False, False) one of
+    a2c_breakout_step_rules (section 6i).  ``device_step`` returns ``done`` and ``reset`` as two tensors holding the same
+    values, the real done (with ``episodic_life`` also a lost life).  ``episode_stats`` counts those dones and sums the
+    (unclipped) rewards they closed."""
     frame_shape = (1, H, W)
 
     def __init__(self, n_envs, device="cuda", seed=0, lives=5, max_episode_steps=10000, env_id0=0, frame_skip=1, sticky_num=0,
-                 sticky_den=1):
+                 sticky_den=1, frame_skip_max=None, episodic_life=False, clip_rewards=False):
         from . import ops
         self.world = check_world(lives, max_episode_steps)
         self.repeat = check_repeat(frame_skip, sticky_num, sticky_den, "Breakout")
-        self.plain = self.repeat[:2] == (1, 0)      # today's world: the entry points without frame skip
+        # None: every key of section 6i at its default -- the entry points above; else the block of a2c_breakout_step_rules
+        self.rules = ops.world_rules(*self.repeat, *check_rules(frame_skip, frame_skip_max, episodic_life, clip_rewards,
+                                                                "Breakout", flags=True))
+        self.plain = self.repeat[:2] == (1, 0) and self.rules is None      # today's world: the entry points without frame skip
         super().__init__(n_envs, device, seed, env_id0, ops.breakout_state_bytes(self.world[0]) // 4)
 
     def _reset(self):
@@ -261,7 +308,9 @@ class DeviceBreakoutPool(DeviceWorldPool):
 
     def _step(self, head, out, frames, post, sl):
         from . import ops
-        if post is None:
+        if self.rules is not None:
+            fn, extra = ops.breakout_step_rules, (self.rules, post)
+        elif post is None:
             fn, extra = (ops.breakout_step, ()) if self.plain else (ops.breakout_step_skip, self.repeat)
         else:
             fn, extra = (ops.breakout_step_post, (post,)) if self.plain else (ops.breakout_step_post_skip, (*self.repeat, post))

@@ -1400,3 +1400,37 @@ def breakout_step_post_skip(state, actions_ptr, act_stride, action_shift, B, env
                                             max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset),
                                             _p(ep_count), _p(ep_rew_sum), frame_skip, sticky_num, sticky_den, _post_ref(post),
                                             _st(st)), "a2c_breakout_step_post_skip")
+
+
+# ---------------------------------------------------------------- random frame skip, episodic life, reward clipping
+def world_rules(frame_skip=1, sticky_num=0, sticky_den=1, frame_skip_max=None, episodic_life=False, clip_rewards=False,
+                always=False):
+    """the a2c_world_rules block of a2c_<world>_step_rules; None when it asks for nothing the _skip
+    entry points do not do (``frame_skip_max`` None or ``frame_skip``, both flags off), unless ``always``"""
+    kmax = frame_skip if frame_skip_max is None else frame_skip_max
+    if not always and kmax == frame_skip and not episodic_life and not clip_rewards:
+        return None
+    return _lib.WorldRules(frame_skip=frame_skip, frame_skip_max=kmax, sticky_num=sticky_num, sticky_den=sticky_den,
+                           episodic_life=int(episodic_life), clip_rewards=int(clip_rewards))
+
+
+def pong_step_rules(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win, max_episode_steps,
+                    opp_skill_num, opp_skill_den, frames, frame_ld, rew, done, reset, rules, post=None, ep_count=None,
+                    ep_rew_sum=None, st=None):
+    """pong_step_skip (``post`` None) / pong_step_post_skip by a ``world_rules`` block: the game frames of an agent step drawn
+    from frame_skip .. frame_skip_max"""
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
+    check(lib().a2c_pong_step_rules(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
+                                    max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew), _p(done),
+                                    _p(reset), _p(ep_count), _p(ep_rew_sum), _post_ref(rules), _post_ref(post), _st(st)),
+          "a2c_pong_step_rules")
+
+
+def breakout_step_rules(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames,
+                        frame_ld, rew, done, reset, rules, post=None, ep_count=None, ep_rew_sum=None, st=None):
+    """breakout_step_skip (``post`` None) / breakout_step_post_skip by a ``world_rules`` block: the game frames of an agent
+    step drawn, a lost life closing the step (episodic_life), the reward as a sign (clip_rewards)"""
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
+    check(lib().a2c_breakout_step_rules(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
+                                        max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
+                                        _p(ep_rew_sum), _post_ref(rules), _post_ref(post), _st(st)), "a2c_breakout_step_rules")

@@ -37,11 +37,18 @@ step's.  A frame that ends the episode zeroes ``prev`` and the remaining frames 
 agent step's done is the real done; the "Pong" done is that or a non-zero summed reward.  At most one point falls in an
 agent step (after a serve the ball needs at least 33 frames to reach a goal line, and k <= 8).  ``steps``, ``ep_steps`` and
 ``max_episode_steps`` count game frames.  With ``sticky_num == 0`` no draw is taken and ``prev`` stays 0: k = 1 is the world
-above word for word, k > 1 is that world stepped k times with one action and cut at the real done."""
+above word for word, k > 1 is that world stepped k times with one action and cut at the real done.
+
+Random frame skip (a2c_pong_step_rules): with ``frame_skip_max`` (``frame_skip`` .. 8; None =
+``frame_skip``) above ``frame_skip`` the agent step first takes ONE draw ``d``, before its first sticky draw, and plays
+k = frame_skip + d mod (frame_skip_max - frame_skip + 1) game frames: ``frame_skip=2, frame_skip_max=4, sticky_num=1,
+sticky_den=4`` is the stepping rule of ``Pong-v0``.  Episodic life and reward clipping are keys of the Breakout worlds: here
+a point closes every step already and |reward| <= 1."""
 import numpy as np
 
+from . import worlds
 from .worlds import (MAX_FRAME_SKIP, MAX_STICKY_DEN, _M, DeviceWorldPool, HostWorld, _clamp, _env_id0, check_repeat,  # noqa: F401
-                     factory_of, hash32, repeat_from_hyps)
+                     check_rules, factory_of, hash32, repeat_from_hyps)
 
 N_ACTIONS = 3
 W = H = 80
@@ -62,15 +69,23 @@ OPP_RGB, AGENT_RGB, BALL_RGB = (213, 130, 74), (92, 186, 92), (236, 236, 236)
 
 
 def check_world(points_to_win=21, max_episode_steps=10000, opp_skill_num=3, opp_skill_den=4, frame_skip=1, sticky_num=0,
-                sticky_den=1):
-    """the bounds a2c_pong_step / a2c_pong_step_skip enforce (A2C_ERR_ARG): same ones for the host twin"""
+                sticky_den=1, frame_skip_max=None):
+    """the bounds a2c_pong_step / a2c_pong_step_skip / a2c_pong_step_rules enforce (A2C_ERR_ARG): same ones for the host twin"""
     p, m, n, d = int(points_to_win), int(max_episode_steps), int(opp_skill_num), int(opp_skill_den)
-    check_repeat(frame_skip, sticky_num, sticky_den)
+    check_repeat(frame_skip, sticky_num, sticky_den, frame_skip_max=frame_skip_max)
     if not (1 <= p <= MAX_POINTS and 1 <= m <= MAX_EPISODE_STEPS and 1 <= d <= MAX_SKILL_DEN and 0 <= n <= d):
         raise ValueError(f"Pong: unsupported world points_to_win={p} max_episode_steps={m} opp_skill={n}/{d} (1 <= "
                          f"points_to_win <= {MAX_POINTS}, 1 <= max_episode_steps <= {MAX_EPISODE_STEPS}, 1 <= opp_skill_den "
                          f"<= {MAX_SKILL_DEN}, 0 <= opp_skill_num <= opp_skill_den)")
     return p, m, n, d
+
+
+RULE_KEYS = ("frame_skip_max",)
+
+
+def rules_from_hyps(hyps):
+    """{frame_skip_max} from the hyps (frame_skip where absent); ValueError for episodic_life / clip_rewards"""
+    return worlds.rules_from_hyps(hyps, "Pong", RULE_KEYS)
 
 
 def world_from_hyps(hyps):
@@ -95,11 +110,11 @@ class PongEnv(HostWorld):
     action_space = _ActionSpace()
 
     def __init__(self, seed=0, env_id=0, points_to_win=21, max_episode_steps=10000, opp_skill_num=3, opp_skill_den=4,
-                 frame_skip=1, sticky_num=0, sticky_den=1):
+                 frame_skip=1, sticky_num=0, sticky_den=1, frame_skip_max=None):
         self.points_to_win, self.max_episode_steps, self.skill_num, self.skill_den = check_world(
             points_to_win, max_episode_steps, opp_skill_num, opp_skill_den)
         super().__init__(seed, env_id, frame_skip, sticky_num, sticky_den,
-                         ("wall", "hit_agent", "hit_opp", "agent_point", "opp_point", "episode_end"))
+                         ("wall", "hit_agent", "hit_opp", "agent_point", "opp_point", "episode_end"), frame_skip_max)
         self.agent_y = self.opp_y = PADDLE_START_Y
         self.ball_x, self.ball_y, self.vx, self.vy = SERVE_X, SERVE_Y, 1, 0
         self.score_agent = self.score_opp = 0
@@ -198,18 +213,21 @@ PongFactory = factory_of(PongEnv)
 class DevicePongPool(DeviceWorldPool):
     """``n_envs`` Pong worlds in device memory (the Runner's device-pool protocol).  Env j is the world
     ``PongEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames; with ``frame_skip`` / ``sticky_num`` / ``sticky_den``
-    other than (1, 0, .) a step is an agent step of a2c_pong_step_skip.  ``device_step`` returns
+    other than (1, 0, .) a step is an agent step of a2c_pong_step_skip, with ``frame_skip_max`` above
+    ``frame_skip`` one of a2c_pong_step_rules (section 6i).  ``device_step`` returns
     ``done = (rew != 0) or real done`` (the Pong override of the reference's runner) and ``reset = real done`` as two tensors.
     ``episode_stats`` counts what the Runner's ``rew_q`` counts for a "Pong" env type: every ``done``, with the reward since
     the last one."""
     frame_shape = (1, H, W)
 
     def __init__(self, n_envs, device="cuda", seed=0, points_to_win=21, max_episode_steps=10000, opp_skill_num=3,
-                 opp_skill_den=4, env_id0=0, frame_skip=1, sticky_num=0, sticky_den=1):
+                 opp_skill_den=4, env_id0=0, frame_skip=1, sticky_num=0, sticky_den=1, frame_skip_max=None):
         from . import ops
         self.world = check_world(points_to_win, max_episode_steps, opp_skill_num, opp_skill_den)
         self.repeat = check_repeat(frame_skip, sticky_num, sticky_den)
-        self.plain = self.repeat[:2] == (1, 0)      # today's world: the entry points without frame skip
+        # None: frame_skip_max at its default -- the entry points above; else the block of a2c_pong_step_rules
+        self.rules = ops.world_rules(*self.repeat, *check_rules(frame_skip, frame_skip_max))
+        self.plain = self.repeat[:2] == (1, 0) and self.rules is None      # today's world: the entry points without frame skip
         super().__init__(n_envs, device, seed, env_id0, ops.pong_state_bytes(self.world[0]) // 4)
 
     def _reset(self):
@@ -218,7 +236,9 @@ class DevicePongPool(DeviceWorldPool):
 
     def _step(self, head, out, frames, post, sl):
         from . import ops
-        if post is None:
+        if self.rules is not None:
+            fn, extra = ops.pong_step_rules, (self.rules, post)
+        elif post is None:
             fn, extra = (ops.pong_step, ()) if self.plain else (ops.pong_step_skip, self.repeat)
         else:
             fn, extra = (ops.pong_step_post, (post,)) if self.plain else (ops.pong_step_post_skip, (*self.repeat, post))

@@ -48,12 +48,16 @@ def get_save_folder(hyps):
 
 # The device-world families of train(), env_type "<family>-device" / "<family>-host": the module of a2c_amd, its preprocessor,
 # the "Pong" done override, the one-bit frame transport of the process pool ({0, 1} frames only), the names of what the
-# module's world_from_hyps returns (the world kwargs), and whether the family takes frame_skip / sticky_num / sticky_den.
+# module's world_from_hyps returns (the world kwargs), whether the family takes frame_skip / sticky_num / sticky_den, and which
+# of frame_skip_max / episodic_life / clip_rewards it takes.
 _WORLDS = {
-    "Snake": (snake, "snake_prep", False, False, ("grid_size", "unit_size", "n_foods"), False),
-    "Pong": (pong, "pong_prep", True, True, ("points_to_win", "max_episode_steps", "opp_skill_num", "opp_skill_den"), True),
-    "Breakout": (breakout, "breakout_prep", False, False, ("lives", "max_episode_steps"), True),
+    "Snake": (snake, "snake_prep", False, False, ("grid_size", "unit_size", "n_foods"), False, ()),
+    "Pong": (pong, "pong_prep", True, True, ("points_to_win", "max_episode_steps", "opp_skill_num", "opp_skill_den"), True,
+             pong.RULE_KEYS),
+    "Breakout": (breakout, "breakout_prep", False, False, ("lives", "max_episode_steps"), True, breakout.RULE_KEYS),
 }
+# the keys of section 6i that shape what a policy is TRAINED on, not the game: evaluation worlds do not get them
+_TRAINING_ONLY = ("episodic_life", "clip_rewards")
 
 
 def _world_family(env_type):
@@ -87,11 +91,15 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     ``env_pool`` choices with ``prep_fxn="snake_prep"``; both are evaluated on host ``SnakeEnv``s.
     ``env_type`` "Pong-device" / "Pong-host" (a2c_amd/pong.py; keys ``points_to_win``, ``max_episode_steps``,
     ``opp_skill_num``, ``opp_skill_den``; ``frame_skip``, ``sticky_num``, ``sticky_den``: game frames per step and sticky
-    actions, DESIGN.md section 6g, for the Pong and Breakout worlds, training pools and evaluation worlds alike)
+    actions, DESIGN.md section 6g, for the Pong and Breakout worlds, training pools and evaluation worlds alike;
+    ``frame_skip_max``: the game frames of a step drawn from frame_skip .. frame_skip_max, section 6i, likewise -- with
+    ``frame_skip=2, frame_skip_max=4, sticky_num=1, sticky_den=4`` the stepping rule of ``Pong-v0``)
     likewise: ``DevicePongPool``, or ``PongEnv``s behind the usual pools with
     ``prep_fxn="pong_prep"`` (the process pool carries their {0, 1} frames packed, one bit per pixel); 3 actions,
     ``action_shift`` 0 unless given, the "Pong" done override applies, evaluation on host ``PongEnv``s.
-    ``env_type`` "Breakout-device" / "Breakout-host" (a2c_amd/breakout.py; keys ``lives``, ``max_episode_steps``) likewise:
+    ``env_type`` "Breakout-device" / "Breakout-host" (a2c_amd/breakout.py; keys ``lives``, ``max_episode_steps``, and for the
+    training worlds only ``episodic_life``: a lost life closes the step, and ``clip_rewards``: the step's reward is its sign,
+    section 6i -- a ValueError on the Pong worlds, as all three keys of that section are on the Snake worlds) likewise:
     ``DeviceBreakoutPool``, or ``BreakoutEnv``s behind the usual pools with ``prep_fxn="breakout_prep"`` (grey levels
     0..255 on the uint8 transport; with ``hyps["device_prep"] = "breakout_prep"`` the process pool carries the RAW frames
     and the device preps them); 4 actions, ``action_shift`` 0 unless given, real dones only, evaluation on host
@@ -112,6 +120,11 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
         if worlds.repeat_from_hyps(hyps, "Snake")[:2] != (1, 0):
             raise ValueError("a2c_amd: frame_skip / sticky_num are keys of the Pong and Breakout worlds: the Snake worlds "
                              "play one game frame per step")
+    if env_fn is None and _world_family(hyps.get("env_type")) is not None:
+        # frame_skip_max / episodic_life / clip_rewards: refused here, before anything is written or allocated, where the
+        # family does not take them or they are out of bounds
+        family = _world_family(hyps["env_type"])
+        rules = worlds.rules_from_hyps(hyps, family, _WORLDS[family][6])
     if hyps["n_rollouts"] is None:
         hyps["n_rollouts"] = hyps["n_envs"]
     hyps["main_path"] = try_key(hyps, "main_path", "./")
@@ -131,7 +144,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     probe = None
     family, raw = _world_family(hyps["env_type"]) if env_fn is None else None, False
     if family is not None:
-        mod, prep_name, pong_done, bits, names, repeats = _WORLDS[family]
+        mod, prep_name, pong_done, bits, names, repeats, _ = _WORLDS[family]
         world = dict(zip(names, mod.world_from_hyps(hyps)), seed=hyps["seed"])
         if family == "Breakout":
             # device_prep: the workers hand on the RAW frames (null_prep) and a2c_frame_prep_u8 crops / strides them
@@ -146,9 +159,12 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
         hyps["max_eval_steps"] = try_key(hyps, "max_eval_steps", 2000)
         if repeats:
             world.update(zip(("frame_skip", "sticky_num", "sticky_den"), worlds.repeat_from_hyps(hyps, family)))
+        # evaluation plays whole games for the game's score: the dynamics (frame_skip_max), not the training flags
+        eval_world = dict(world, **{k: v for k, v in rules.items() if k not in _TRAINING_ONLY})
+        world.update(rules)
         factory, device_pool = getattr(mod, family + "Factory"), getattr(mod, "Device" + family + "Pool")
-        mk_env = lambda j: SequentialEnvironment(hyps["env_type"], getattr(preprocessing, prep_name), seed=hyps["seed"],
-                                                 env_fn=factory(env_id=j, **world))
+        mk_env = lambda j, kw=world: SequentialEnvironment(hyps["env_type"], getattr(preprocessing, prep_name),
+                                                           seed=hyps["seed"], env_fn=factory(env_id=j, **kw))
         side = world["grid_size"] * world["unit_size"] if family == "Snake" else None
         world_shape = (1, side, side) if family == "Snake" else device_pool.frame_shape
         if hyps["env_type"] == family + "-device":
@@ -265,13 +281,13 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     if eval_pool == "device":
         # a second pool of the training pool's kind: same world and seed, n_test_eps worlds (DeviceStatsRunner gives them the
         # env ids of the host twins below, and fresh ones on every later call)
-        stats_runner = DeviceStatsRunner(hyps, type(pool)(try_key(hyps, "n_test_eps", 15), device=pool.device, **world),
+        stats_runner = DeviceStatsRunner(hyps, type(pool)(try_key(hyps, "n_test_eps", 15), device=pool.device, **eval_world),
                                          uniform_fn=uniform_fn)
     elif eval_env is not None:
         stats_runner = StatsRunner(hyps, env=eval_env)
     elif family is not None:
         # host twins of worlds the training pool does not play (env ids from 10007 on)
-        stats_runner = StatsRunner(hyps, envs=[mk_env(10007 + j) for j in range(try_key(hyps, "n_test_eps", 15))])
+        stats_runner = StatsRunner(hyps, envs=[mk_env(10007 + j, eval_world) for j in range(try_key(hyps, "n_test_eps", 15))])
     else:
         stats_runner = StatsRunner(hyps) if env_fn is None else None
     entr_coef_diff, lr_diff = hyps["entr_coef"] - hyps["entr_coef_low"], hyps["lr"] - hyps["lr_low"]

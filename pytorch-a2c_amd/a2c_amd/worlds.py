@@ -42,37 +42,78 @@ def _i32(v):
     return v - (1 << 32) if v >> 31 else v
 
 
-def check_repeat(frame_skip=1, sticky_num=0, sticky_den=1, what="Pong"):
-    """the bounds a2c_<world>_step_skip enforces (A2C_ERR_ARG) on frame skip and sticky actions: same ones for the host
-    twins -> (frame_skip, sticky_num, sticky_den)"""
+def check_repeat(frame_skip=1, sticky_num=0, sticky_den=1, what="Pong", frame_skip_max=None):
+    """the bounds a2c_<world>_step_skip / _step_rules enforce (A2C_ERR_ARG) on frame skip (``frame_skip_max``: None, or
+    frame_skip .. 8) and sticky actions: same ones for the host twins -> (frame_skip, sticky_num, sticky_den)"""
     k, n, d = int(frame_skip), int(sticky_num), int(sticky_den)
     if not (1 <= k <= MAX_FRAME_SKIP and 1 <= d <= MAX_STICKY_DEN and 0 <= n <= d):
         raise ValueError(f"{what}: unsupported frame_skip={k} sticky={n}/{d} (1 <= frame_skip <= {MAX_FRAME_SKIP}, "
                          f"1 <= sticky_den <= {MAX_STICKY_DEN}, 0 <= sticky_num <= sticky_den)")
+    if frame_skip_max is not None and not k <= int(frame_skip_max) <= MAX_FRAME_SKIP:
+        raise ValueError(f"{what}: unsupported frame_skip_max={frame_skip_max} (frame_skip = {k} <= frame_skip_max <= "
+                         f"{MAX_FRAME_SKIP})")
     return k, n, d
 
 
+def check_rules(frame_skip=1, frame_skip_max=None, episodic_life=False, clip_rewards=False, what="Pong", flags=False):
+    """the bounds a2c_<world>_step_rules enforces on what DESIGN.md section 6i adds; ``flags``: the world has episodic_life /
+    clip_rewards (Breakout) -> (frame_skip_max, episodic_life, clip_rewards), ``frame_skip_max`` None becoming ``frame_skip``"""
+    k = check_repeat(frame_skip, what=what, frame_skip_max=frame_skip_max)[0]
+    out = []
+    for name, v in (("episodic_life", episodic_life), ("clip_rewards", clip_rewards)):
+        v = 0 if v is None else v
+        if isinstance(v, str) or v not in (0, 1):
+            raise ValueError(f"{what}: {name}={v!r} is neither 0 nor 1")
+        if v and not flags:
+            raise ValueError(f"{what}: {name} is a key of the Breakout worlds ({what} closes its steps and bounds its rewards "
+                             "by its own rules)")
+        out.append(bool(v))
+    return (k if frame_skip_max is None else int(frame_skip_max), *out)
+
+
+RULE_KEYS = ("frame_skip_max", "episodic_life", "clip_rewards")
+
+
 def repeat_from_hyps(hyps, what="Pong"):
-    """(frame_skip, sticky_num, sticky_den) from the hyps (1, 0, 1 where absent); ValueError outside the bounds"""
+    """(frame_skip, sticky_num, sticky_den) from the hyps (1, 0, 1 where absent); ValueError outside the bounds, those of a
+    ``frame_skip_max`` among the hyps included"""
     get = lambda k, dflt: dflt if hyps.get(k) is None else hyps[k]
-    return check_repeat(get("frame_skip", 1), get("sticky_num", 0), get("sticky_den", 1), what)
+    return check_repeat(get("frame_skip", 1), get("sticky_num", 0), get("sticky_den", 1), what, hyps.get("frame_skip_max"))
+
+
+def rules_from_hyps(hyps, what="Pong", keys=RULE_KEYS):
+    """{key: value} of the keys of RULE_KEYS this world family takes (``keys``), defaults where absent; ValueError outside the
+    bounds and for a key of RULE_KEYS the family does not take"""
+    get = lambda k, dflt: dflt if hyps.get(k) is None else hyps[k]
+    alien = [k for k in RULE_KEYS if k not in keys and hyps.get(k) is not None and (k == "frame_skip_max" or hyps[k] != 0)]
+    if alien:
+        raise ValueError(f"a2c_amd: {', '.join(alien)}: not a key of the {what} worlds (frame_skip_max: Pong and Breakout; "
+                         "episodic_life, clip_rewards: Breakout)")
+    vals = check_rules(get("frame_skip", 1), hyps.get("frame_skip_max"), get("episodic_life", False),
+                       get("clip_rewards", False), what, flags="episodic_life" in keys)
+    return {k: v for k, v in zip(RULE_KEYS, vals) if k in keys}
 
 
 class HostWorld:
     """The gym-like surface and the AGENT step of the host twins of the register worlds (csrc/world.h):
-    ``frame_skip`` game frames with sticky actions (the module docstrings of pong.py / breakout.py state the rule).  A
-    subclass supplies ``WHAT`` (its name in messages), ``N_ACTIONS``, ``new_episode()``, ``_frame(a)`` -> (reward, done),
-    ``render_rgb()`` and, where an agent step has an invariant, ``_check_step(total)``."""
+    ``frame_skip`` .. ``frame_skip_max`` game frames with sticky actions (the module docstrings of pong.py / breakout.py state
+    the rules).  A subclass supplies ``WHAT`` (its name in messages), ``N_ACTIONS``, ``new_episode()``, ``_frame(a)`` ->
+    (reward, done), ``render_rgb()`` and, where an agent step has an invariant, ``_check_step(total)``; where something other
+    than an episode end closes an agent step, ``_closes()``."""
     WHAT, N_ACTIONS = "World", 1
 
-    def __init__(self, seed, env_id, frame_skip, sticky_num, sticky_den, events):
-        self.frame_skip, self.sticky_num, self.sticky_den = check_repeat(frame_skip, sticky_num, sticky_den, self.WHAT)
+    def __init__(self, seed, env_id, frame_skip, sticky_num, sticky_den, events, frame_skip_max=None):
+        self.frame_skip, self.sticky_num, self.sticky_den = check_repeat(frame_skip, sticky_num, sticky_den, self.WHAT,
+                                                                         frame_skip_max)
+        self.frame_skip_max = self.frame_skip if frame_skip_max is None else int(frame_skip_max)
         self.prev = 0
+        self.last_k = 0                 # game frames the last agent step was to play (DESIGN.md section 6i, rule 1)
         self.seed_, self.env_id = int(seed) & _M, int(env_id)
         self.draws = self.steps = self.ep_steps = 0
         self.over = True
+        self.closed = False             # the last agent step closed without ending the episode: reset() continues the game
         self.events = dict.fromkeys(events, 0)
-        if (self.frame_skip, self.sticky_num) != (1, 0):      # a plain world can neither cut nor keep an action
+        if (self.frame_skip_max, self.sticky_num) != (1, 0):      # a plain world can neither cut nor keep an action
             self.events.update(cut=0, sticky=0)
 
     def seed(self, seed):
@@ -85,8 +126,19 @@ class HostWorld:
 
     # ---- gym surface
     def reset(self):
-        self.new_episode()
+        """after a done that closed an agent step without ending the episode (``closed``): the game goes on -- no draw, no
+        state changed, the current frame (what baselines' EpisodicLifeEnv does); else the full restart"""
+        if self.closed:
+            self.continue_episode()
+        else:
+            self.new_episode()
         return self.render_rgb()
+
+    def continue_episode(self):
+        """the continuing reset without its frame: takes up the game where a close that was no episode end left it"""
+        if self.over or not self.closed:
+            raise RuntimeError(f"{self.WHAT}Env.continue_episode(): the last step did not close inside an episode")
+        self.closed = False
 
     def step(self, action):
         rew, done = self.advance(action)
@@ -96,12 +148,17 @@ class HostWorld:
         return self.render_rgb()
 
     def advance(self, action):
-        """the agent step without its frame: ``frame_skip`` game frames -> (summed reward, done)"""
-        if self.over:
+        """the agent step without its frame: k game frames -> (summed reward, done), k = ``frame_skip``, or with
+        ``frame_skip_max`` above it ONE draw d taken first: k = frame_skip + d mod (frame_skip_max - frame_skip + 1)"""
+        if self.over or self.closed:
             raise RuntimeError(f"{self.WHAT}Env.step() after done: call reset()")
         a = int(action) % self.N_ACTIONS
+        k = self.frame_skip
+        if self.frame_skip_max > k:
+            k += self._draw() % (self.frame_skip_max - k + 1)
+        self.last_k = k
         total, done = 0.0, False
-        for s in range(self.frame_skip):
+        for s in range(k):
             x = a
             if self.sticky_num > 0:
                 if self._draw() % self.sticky_den < self.sticky_num:
@@ -110,16 +167,21 @@ class HostWorld:
                 self.prev = x
             rew, done = self._frame(x)
             total += rew
-            if done:
+            self.closed = not done and self._closes()
+            if done or self.closed:
                 self.prev = 0
-                if s < self.frame_skip - 1:
+                if s < k - 1:
                     self.events["cut"] += 1
                 break
         self._check_step(total)
-        return total, done
+        return total, done or self.closed
 
     def _check_step(self, total):
         pass
+
+    def _closes(self):
+        """after a game frame that did not end the episode: does it close the agent step all the same?"""
+        return False
 
 
 class WorldFactory:

@@ -1,6 +1,6 @@
 // What the worlds in device memory share (snake.hip, pong.hip, breakout.hip; not part of the C ABI): the counter-based draws,
 // the a2c_<world>_step_post helpers, and the scaffold of the worlds whose state fits in registers: counters, the frame-skip /
-// sticky-action loop, the two kernels and their launchers, written once over a game type G (Pong runs
+// sticky-action loop, the kernels and their launchers, written once over a game type G (DESIGN.md sections 6h and 6i; Pong runs
 // on it, Breakout uses the counters and small helpers and keeps kernels of its own, breakout.hip says why).  A game G supplies
 //   WORDS, HW, N_ACTIONS                  int32 state words per env, floats of one frame, actions
 //   World, Params, params_ok(Params)      the world in registers; its parameters, plain data, ONE kernel argument
@@ -217,6 +217,60 @@ __global__ __launch_bounds__(WORLD_POST_THREADS) void world_post_kernel(
   G::write_frame(w, top, frames == nullptr ? nullptr : frames + (int64_t)e * frame_ld, tid, WORLD_POST_THREADS);
 }
 
+// ---- a2c_<world>_step_rules: the agent step whose number of game frames is drawn.
+// The checks of an a2c_world_rules block; flags: the world has episodic_life / clip_rewards (Breakout)
+static inline bool world_rules_ok(const a2c_world_rules* r, bool flags) {
+  if (r == nullptr || !world_repeat_ok(r->frame_skip, r->sticky_num, r->sticky_den)) return false;
+  if (r->frame_skip_max < r->frame_skip || r->frame_skip_max > WORLD_MAX_FRAME_SKIP) return false;
+  if ((r->episodic_life | r->clip_rewards) & ~1) return false;
+  return flags || (r->episodic_life | r->clip_rewards) == 0;
+}
+
+// a block that asks for nothing new: the step is a2c_<world>_step[_post]_skip
+static inline bool world_rules_plain(const a2c_world_rules& r) {
+  return r.frame_skip_max == r.frame_skip && r.episodic_life == 0 && r.clip_rewards == 0;
+}
+
+// the game frames of this agent step: with frame_skip_max > frame_skip ONE draw, taken before the step's first sticky draw
+__device__ __forceinline__ int world_draw_skip(WorldCount& c, uint32_t seed, uint32_t env, const a2c_world_rules& r) {
+  if (r.frame_skip_max <= r.frame_skip) return r.frame_skip;
+  return r.frame_skip + (int)(world_hash(seed, env, c.draws++) % (uint32_t)(r.frame_skip_max - r.frame_skip + 1));
+}
+
+// The third instantiation beside REPEAT == false / true, as a kernel of its own that a game instantiates in a file of its
+// own (pong_rules.hip), so that those two stay what and where they were in their code object, to the byte (DESIGN.md section
+// 6i): world_kernel<G, true, true> (POST == false; `post` is not read) and world_post_kernel<G, true> (POST == true) with the
+// k-draw in front of the agent step.  k lives in registers only; every wave of the POST form draws the same k.
+template <typename G, bool POST>
+__global__ __launch_bounds__(POST ? WORLD_POST_THREADS : 64) void world_rules_kernel(
+    int32_t* __restrict__ state, const int64_t* __restrict__ actions, int64_t act_stride, int action_shift, int env_id0,
+    uint32_t seed, const typename G::Params gp, const a2c_world_rules rules, float* __restrict__ frames, int64_t frame_ld,
+    float* __restrict__ rew, float* __restrict__ done, float* __restrict__ reset, int32_t* __restrict__ ep_count,
+    int32_t* __restrict__ ep_rew_sum, const a2c_world_post post) {
+  const int e = blockIdx.x, tid = threadIdx.x;
+  const uint32_t env = (uint32_t)(env_id0 + e);
+  int32_t* st = state + (int64_t)e * G::WORDS;
+  typename G::World w;
+  WorldCount c;
+  G::load(st, w, c);
+  const int a = world_action<G::N_ACTIONS>(actions, act_stride, action_shift, e);
+  if (POST) __syncthreads();
+  bool over, closed;
+  int closed_rew;
+  const int k = world_draw_skip(c, seed, env, rules);
+  const int r = world_agent_step<G>(w, c, a, gp, seed, env, k, rules.sticky_num, rules.sticky_den, over, closed, closed_rew);
+  if (tid == 0) world_publish(e, r, over, closed, closed_rew, rew, done, reset, ep_count, ep_rew_sum);
+  if (tid < 64) G::store(st, w, c, tid);
+  if (POST) {
+    const float d = world_post_done(post, (float)r, closed ? 1.0f : 0.0f);
+    if (tid == 0) world_post_book(post, e, (float)r, d);
+    float* top = world_post_planes(post, e, d, over, G::HW, tid);
+    G::write_frame(w, top, frames == nullptr ? nullptr : frames + (int64_t)e * frame_ld, tid, WORLD_POST_THREADS);
+  } else {
+    G::write_frame(w, frames + (int64_t)e * frame_ld, nullptr, tid, 64);
+  }
+}
+
 // ---- the launchers: the argument checks of the extern "C" entry points and the launch
 template <typename G>
 int world_reset(int32_t* state, int B, int env_id0, uint32_t seed, const typename G::Params& gp, float* frames, int64_t frame_ld,
@@ -260,6 +314,38 @@ int world_step_post(int32_t* state, const int64_t* actions, int64_t act_stride, 
   hipLaunchKernelGGL(kernel, dim3(B), dim3(WORLD_POST_THREADS), 0, a2c_s(stream), state, actions, act_stride, action_shift,
                      env_id0, seed, gp, frame_skip, sticky_num, sticky_den, frames, frame_ld, rew, done, reset, ep_count,
                      ep_rew_sum, *post);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+// a2c_<world>_step_rules of a world on the scaffold (no episodic_life / clip_rewards: flags set are A2C_ERR_ARG): post == nullptr
+// is the plain step.  A block that asks for nothing new goes to the launchers above and the kernels they launch.
+template <typename G>
+int world_step_rules(int32_t* state, const int64_t* actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                     uint32_t seed, const typename G::Params& gp, float* frames, int64_t frame_ld, float* rew, float* done,
+                     float* reset, int32_t* ep_count, int32_t* ep_rew_sum, const a2c_world_rules* rules,
+                     const a2c_world_post* post, a2c_stream_t stream) {
+  if (!world_rules_ok(rules, false)) return A2C_ERR_ARG;
+  if (world_rules_plain(*rules))
+    return post == nullptr
+               ? world_step<G>(state, actions, act_stride, action_shift, B, env_id0, seed, gp, frames, frame_ld, rew, done, reset,
+                               ep_count, ep_rew_sum, rules->frame_skip, rules->sticky_num, rules->sticky_den, stream)
+               : world_step_post<G>(state, actions, act_stride, action_shift, B, env_id0, seed, gp, frames, frame_ld, rew, done,
+                                    reset, ep_count, ep_rew_sum, rules->frame_skip, rules->sticky_num, rules->sticky_den, post,
+                                    stream);
+  if (B <= 0 || env_id0 < 0 || act_stride < 0 || !G::params_ok(gp)) return A2C_ERR_ARG;
+  if (state == nullptr || actions == nullptr || rew == nullptr || done == nullptr || reset == nullptr) return A2C_ERR_ARG;
+  if (post == nullptr) {
+    if (!world_frames_ok(frames, frame_ld, G::HW)) return A2C_ERR_ARG;
+    hipLaunchKernelGGL((world_rules_kernel<G, false>), dim3(B), dim3(64), 0, a2c_s(stream), state, actions, act_stride,
+                       action_shift, env_id0, seed, gp, *rules, frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum,
+                       a2c_world_post{});
+  } else {
+    if ((frames != nullptr && !world_frames_ok(frames, frame_ld, G::HW)) || !a2c_world_post_ok(post, G::HW)) return A2C_ERR_ARG;
+    hipLaunchKernelGGL((world_rules_kernel<G, true>), dim3(B), dim3(WORLD_POST_THREADS), 0, a2c_s(stream), state, actions,
+                       act_stride, action_shift, env_id0, seed, gp, *rules, frames, frame_ld, rew, done, reset, ep_count,
+                       ep_rew_sum, *post);
+  }
   A2C_CHECK_LAUNCH();
   return A2C_OK;
 }

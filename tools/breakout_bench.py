@@ -19,10 +19,13 @@ sees them; `--repeats` samples, the median is reported with min and max beside i
 pre-drawn uniform ones.  One JSON line on stdout.
 
     python tools/breakout_bench.py [--iters 2000] [--epochs 30] [--repeats 5] [--n-envs 256] [--graphs on|off] [--learn 0]
-                               [--frame-skip 1] [--sticky 0/1]
+                               [--frame-skip 1] [--sticky 0/1] [--frame-skip-max K] [--episodic-life] [--clip-rewards]
 
 --frame-skip K / --sticky NUM/DEN measure worlds that play K game frames per env step with sticky actions (DESIGN.md section
 6g; the learning run keeps the plain world): the epochs then report game frames/s = K x env-steps/s beside env-steps/s.
+--frame-skip-max M draws the game frames of every env step from K .. M (section 6i; game frames/s then takes the mean
+(K + M) / 2, what the draw gives on average when no step is cut); --episodic-life / --clip-rewards are the Breakout worlds'
+training flags of that section.
 """
 import argparse
 import json
@@ -41,7 +44,7 @@ import torch  # noqa: E402
 N_ACT, FRAME = 4, (80, 72)
 
 
-REPEAT = {}      # --frame-skip / --sticky: the frame_skip, sticky_num and sticky_den of the measured pools
+REPEAT = {}      # --frame-skip / --sticky / --frame-skip-max / --episodic-life / --clip-rewards: the keywords of the measured pools
 
 
 def timed(fn, n, repeats):
@@ -178,8 +181,9 @@ def bench_epoch(model, n_envs, T, epochs, repeats, graphs=True):
         ops.lib = real
     f = lambda ms: round(N * epochs / (ms * 1e-3))
     k = REPEAT.get("frame_skip", 1)
+    k = (k + REPEAT.get("frame_skip_max", k)) / 2
     return dict(model=model, n_envs=n_envs, n_tsteps=T, rollout_graphs=graphs, ms_per_epoch=round(med / epochs, 3), env_steps_per_s=f(med),
-                game_frames_per_s=k * f(med), game_frames_per_s_min=k * f(hi), game_frames_per_s_max=k * f(lo),
+                game_frames_per_s=round(k * f(med)), game_frames_per_s_min=round(k * f(hi)), game_frames_per_s_max=round(k * f(lo)),
                 env_steps_per_s_min=f(hi), env_steps_per_s_max=f(lo), launches_issued_per_epoch=counted.n)
 
 
@@ -246,14 +250,23 @@ def main():
     ap.add_argument("--learn-model", default="FCModel")
     ap.add_argument("--frame-skip", type=int, default=1, help="game frames per env step (DESIGN.md section 6g)")
     ap.add_argument("--sticky", default="0/1", metavar="NUM/DEN", help="probability that a game frame keeps the previous action")
+    ap.add_argument("--frame-skip-max", type=int, default=None, help="draw the game frames per env step from frame-skip .. this "
+                    "(DESIGN.md section 6i)")
+    ap.add_argument("--episodic-life", action="store_true", help="a lost life closes the env step (Breakout worlds)")
+    ap.add_argument("--clip-rewards", action="store_true", help="the env step's reward is its sign (Breakout worlds)")
     args = ap.parse_args()
     num, den = (int(v) for v in args.sticky.split("/"))
     if (args.frame_skip, num) != (1, 0):
         REPEAT.update(frame_skip=args.frame_skip, sticky_num=num, sticky_den=den)
+    if args.frame_skip_max is not None:
+        REPEAT.update(frame_skip=args.frame_skip, frame_skip_max=args.frame_skip_max)
+    if args.episodic_life or args.clip_rewards:
+        REPEAT.update(episodic_life=args.episodic_life, clip_rewards=args.clip_rewards)
     assert torch.cuda.is_available(), "breakout_bench needs the MI355X"
     from a2c_amd.breakout import DeviceBreakoutPool as DevicePool
     res = dict(device=torch.cuda.get_device_name(0), iters=args.iters, repeats=args.repeats, graphs=args.graphs, frame_skip=args.frame_skip,
-               sticky=args.sticky, step={}, epoch={})
+               sticky=args.sticky, frame_skip_max=args.frame_skip_max, episodic_life=args.episodic_life, clip_rewards=args.clip_rewards,
+               step={}, epoch={})
     for B in (32, 256, 2048):
         res["step"][f"B{B}"] = bench_step(B, args.iters, args.repeats)
     if hasattr(DevicePool, "device_step_post"):
