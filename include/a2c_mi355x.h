@@ -1070,6 +1070,43 @@ int a2c_breakout_step_rules(int32_t *state, const int64_t *actions, int64_t act_
                             float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_rules *rules,
                             const a2c_world_post *post, a2c_stream_t stream);
 
+/* ------------------------------------------------------------------ Point worlds in device memory (csrc/point.hip)
+ * The continuous-control world of the Gaussian nets (FCModel / GRUFCModel with is_discrete = False): a point mass chasing
+ * targets on a 4096 x 4096 integer field, this project's own integer rules (the host twin
+ * a2c_amd/point.py produces the same integers).  The state of one env is 16 int32 words: px, py, vx, vy, tx, ty, targets
+ * reached, spare, then draw counter, game-frame counter, episode-frame counter, reward since the last done, the packed
+ * action of the previous game frame (sticky actions; 0 without them), 3 spare.  An action is TWO floats; each becomes
+ * q = 0 for a NaN x, else rint(clamp(x, -1, 1) * 64) (ties to even), x = fp32(a + action_shift): -64 .. 64.  One game frame:
+ * d0 = (|px - tx| + |py - ty|) / 64; per axis v = clamp(v + floor(q / 8), -64, 64), p += v, a wall (p < 0, p > 4095) stops
+ * the point there with v = 0; d1 likewise; rew = d0 - d1, + 10 and one more target reached when d1 == 0; the episode ends at
+ * targets_to_win targets or max_episode_steps frames (the world restarts: two draws place point and target), else a reached
+ * target is replaced with one draw.  place(d) = (512 + (d & 0xFFF) % 3072, 512 + ((d >> 12) & 0xFFF) % 3072); draw i of
+ * world env_id0 + e is hash32(seed, env_id, i).  done == reset: real dones only.  An observation is 8 floats, each an
+ * integer times a power of two: (2 px - 4095) / 4096, (2 py - 4095) / 4096, vx / 64, vy / 64, (tx - px) / 4096,
+ * (ty - py) / 4096, got / 8, 1.  World parameters: 1 <= targets_to_win <= 8, 1 <= max_episode_steps <= 2^24.
+ * One lane plays one env, 64 envs per wavefront.
+ * a2c_point_state_bytes: bytes of ONE env's state.                                                                       */
+size_t a2c_point_state_bytes(void);
+/* starts B worlds (counters to 0, then the two draws): state (B rows of 16 words) and obs (B rows of 8 floats, obs_ld
+ * floats apart).  A2C_ERR_ARG without a launch: B <= 0, env_id0 < 0, a world parameter out of bounds, a NULL state / obs,
+ * state or obs not 16-byte aligned, obs_ld < 8 or not a multiple of 4.                                                    */
+int a2c_point_reset(int32_t *state, int B, int env_id0, uint32_t seed, int targets_to_win, int max_episode_steps,
+                    float *obs, int64_t obs_ld, a2c_stream_t stream);
+/* one AGENT step of B worlds by the a2c_world_rules block (NULL: {1, 1, 0, 1, 0, 0}, one game frame): frame_skip ..
+ * frame_skip_max game frames with the action of env e, actions[e * act_ld + 0 .. 1], and sticky actions, draws in the order
+ * of a2c_<world>_step_rules (the k-draw first, then one sticky draw per frame before the frame's own); rew is the summed
+ * reward, an episode end drops the remaining frames.  ep_count / ep_rew_sum as in a2c_pong_step.
+ * post == NULL: the plain step; obs is required.  post != NULL: the step + the bookkeeping + the hidden-row reset + the
+ * frame stack of the a2c_world_post contract above (HW = 8) in one launch, bit-identical to the plain step followed by
+ * a2c_rollout_post (h == NULL) or by a2c_rollout_record + a2c_frame_stack_push (h != NULL); obs may be NULL then.
+ * A2C_ERR_ARG without a launch: what a2c_point_reset rejects (a NULL obs excepted with post), act_ld < 2, a NULL actions /
+ * rew / done / reset, actions not 4-byte aligned, a rules block a2c_pong_step_rules rejects (either flag set included), a
+ * post block a2c_<world>_step_post rejects.                                                                               */
+int a2c_point_step(int32_t *state, const float *actions, int64_t act_ld, float action_shift, int B, int env_id0,
+                   uint32_t seed, int targets_to_win, int max_episode_steps, float *obs, int64_t obs_ld, float *rew,
+                   float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_rules *rules,
+                   const a2c_world_post *post, a2c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,10 @@ SIGNATURES = {
                                     P, P, PU, PW, P]),
     "a2c_breakout_step_rules": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P, P,
                                         PU, PW, P]),
+    "a2c_point_state_bytes": (c_size_t, []),
+    "a2c_point_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P]),
+    "a2c_point_step": (c_int, [P, P, c_int64, c_float, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P, P, PU, PW,
+                               P]),
 }
 
 _lib = None

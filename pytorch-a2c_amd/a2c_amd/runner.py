@@ -25,7 +25,9 @@ Env pools (``env_pool=``):
     single host synchronisation and can be captured into one hipGraph.  ``device_step(t, env0, B)``
     returns (frames (B, HW) fp32, rew, done, reset) device tensors; a pool whose class sets
     ``needs_actions = True`` is called as ``device_step(t, env0, B, actions=(address, stride))`` with
-    the int64 actions the sampler just wrote, and one with ``episode_stats()`` feeds ``rew_q``.  A pool that also has
+    the int64 actions the sampler just wrote (a pool with ``float_actions``, ``point.DevicePointPool``: the float32 rows of
+    ``n_act`` actions a continuous net's a2c_gauss_head wrote, stride in floats), and one with ``episode_stats()`` feeds
+    ``rew_q``.  A pool that also has
     ``device_step_post(t, env0, B, actions, post)`` (the Snake / Pong / Breakout worlds: step, bookkeeping and next state
     in one launch) is played as ONE hipGraph per slot when ``hyps['rollout_graphs']`` (default true) and the ``actions``
     buffer is device resident: first rollout eager, second captured, then replayed (``_rollout_block_device``).
@@ -209,8 +211,16 @@ class Runner:
                              "thread env pool carry int32 actions")
         if not self.cont and int(getattr(pool, "act_dim", 0) or 0):
             raise ValueError("a2c_amd.Runner: a pool with float action granules (action_dim) needs a continuous-action net")
-        if self.cont and getattr(pool, "needs_actions", False):
+        # ... and a device pool with ``float_actions`` (point.DevicePointPool) reads the float rows where the sampler wrote them
+        self.float_pool = bool(getattr(pool, "float_actions", False))
+        if self.cont and getattr(pool, "needs_actions", False) and not self.float_pool:
             raise ValueError("a2c_amd.Runner: an action-driven device env pool reads int64 actions; the net is continuous")
+        if self.float_pool and not self.cont:
+            raise ValueError("a2c_amd.Runner: a device env pool with float actions needs a continuous-action net "
+                             "(is_discrete=False)")
+        if self.float_pool and int(pool.n_act) != self.n_act:
+            raise ValueError(f"a2c_amd.Runner: the device env pool takes {int(pool.n_act)} float actions, the net has "
+                             f"{self.n_act}")
         f32 = dict(dtype=torch.float32, device=dev)
         self.bookmark = torch.zeros((B, self.S), **f32)                  # state_bookmark of every env
         self.val_prev = torch.zeros(B, **f32)
@@ -510,7 +520,7 @@ class Runner:
         # opt-in (A2C_SIDE_STREAM=1).
         if not self.device_pool and os.environ.get("A2C_NO_STEP_GRAPHS") != "1":
             return self._rollout_block_segmented(net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h, acts_host_out)
-        if (self.device_pool and hasattr(pool, "device_step_post") and not self.cont and acts_host_out is None
+        if (self.device_pool and hasattr(pool, "device_step_post") and (not self.cont or self.float_pool) and acts_host_out is None
                 and try_key(hyps, "rollout_graphs", True) and os.environ.get("A2C_NO_SLOT_GRAPH") != "1"
                 and os.environ.get("A2C_SIDE_STREAM") != "1"):
             return self._rollout_block_device(net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h)
@@ -639,7 +649,13 @@ class Runner:
         if getattr(self, "_u_buf", None) is None or self._u_buf.shape != (T, self.B):
             self._u_buf = torch.zeros((T, self.B), dtype=torch.float32, device=dev)
         ub = self._u_buf
-        if self.uniform_fn is not None:
+        if self.cont:       # continuous nets: the slot's N(0,1) noise, one persistent (T, n_envs, n) buffer likewise
+            n = self.n_act
+            if getattr(self, "_e_buf", None) is None or self._e_buf.shape != (T, self.B, n):
+                self._e_buf = torch.zeros((T, self.B, n), dtype=torch.float32, device=dev)
+            for t in range(T):
+                self._e_buf[t, env0:env0 + B].copy_(self._normals(t, B, env0))
+        elif self.uniform_fn is not None:
             for t in range(T):
                 ub[t, env0:env0 + B].copy_(self.uniform_fn(t, B, env0).reshape(B))
         else:
@@ -692,12 +708,14 @@ class Runner:
             if h is not None:                                              # h_states[e] = h (runner.py:201)
                 hd = h.shape[1]
                 ops.copy_rows(h.data_ptr(), hd, D["h_states"].data_ptr() + 4 * (slot0 * T + t) * hd, T * hd, B, hd, st)
-            u = ub[t, env0:env0 + B]
+            # (continuous nets: a2c_gauss_head writes the float action rows in place, from the slot's persistent noise)
+            u = None if self.cont else ub[t, env0:env0 + B]
+            eps = self._e_buf[t, env0:env0 + B] if self.cont else None
             a_ptr, a_stride = self._act_row(slot0, T, t)
-            out = self._forward(net, sp(t), T * S, B, env0, st, sampler=(u, a_ptr, a_stride))
+            out = self._forward(net, sp(t), T * S, B, env0, st, sampler=None if self.cont else (u, a_ptr, a_stride))
             vals = out["vals"]
             if not out.get("sampled", False):
-                self._sample(net, out["logits"], u, None, a_ptr, a_stride, B, st)
+                self._sample(net, out["logits"], u, eps, a_ptr, a_stride, B, st)
             if h is not None and out["h"].data_ptr() != h.data_ptr():      # (the GRU models update h in place)
                 ops.copy_rows(out["h"].data_ptr(), h.shape[1], h.data_ptr(), h.shape[1], B, h.shape[1], st)
             nxt_ptr, nxt_stride = (sp(t + 1), T * S) if t + 1 < T else (bm.data_ptr(), S)
@@ -1431,14 +1449,19 @@ class DeviceStatsRunner:
 
     The private Runner neither stashes activations nor bootstraps (the scan reads the last step's rows as the env left
     them), and plays through a "roll" workspace of its own: what a training rollout left in the net for its update, and the
-    buffers its captured graphs point at, are as they were.  ``uniform_fn(t, E, 0)`` sees the GLOBAL step index t."""
+    buffers its captured graphs point at, are as they were.  ``uniform_fn(t, E, 0)`` sees the GLOBAL step index t, and so does
+    ``normal_fn(t, E, 0)``: the N(0,1) noise of a continuous net on a pool with ``float_actions`` (``point.DevicePointPool``),
+    whose actions are float rows of ``pool.n_act``."""
 
     ENV_ID0 = 10007
 
-    def __init__(self, hyps, pool, uniform_fn=None, keep_actions=False):
+    def __init__(self, hyps, pool, uniform_fn=None, keep_actions=False, normal_fn=None):
         if not hasattr(pool, "device_step_post"):
-            raise ValueError("DeviceStatsRunner: a device env pool with device_step_post (Snake / Pong / Breakout worlds)")
+            raise ValueError("DeviceStatsRunner: a device env pool with device_step_post (Snake / Pong / Breakout / Point "
+                             "worlds)")
         self.pool, self.uniform_fn, self.keep_actions = pool, uniform_fn, bool(keep_actions)
+        self.normal_fn = normal_fn                # continuous nets on a float-action pool: (t, E, 0) -> (E, n) device N(0,1)
+        self.float_pool = bool(getattr(pool, "float_actions", False))
         self.E = len(pool)
         self.K = int(try_key(hyps, "eval_chunk", None) or 32)
         self.max_steps = int(try_key(hyps, "max_eval_steps", None) or 10 ** 6)
@@ -1452,6 +1475,9 @@ class DeviceStatsRunner:
     def _uniforms(self, t, B, env0):
         return self.uniform_fn(self._chunk * self.K + t, B, env0)
 
+    def _normals(self, t, B, env0):
+        return self.normal_fn(self._chunk * self.K + t, B, env0)
+
     def _setup(self, net):
         E, K, dev = self.E, self.K, net._dev
         C = int(self.hyps["n_frame_stack"])
@@ -1459,12 +1485,14 @@ class DeviceStatsRunner:
         f32 = dict(dtype=torch.float32, device=dev)
         D = dict(states=torch.zeros((n, C) + tuple(self.pool.frame_shape[1:]), **f32), deltas=torch.zeros(n, **f32),
                  rewards=torch.zeros(n, **f32), dones=torch.zeros(n, **f32),
-                 actions=torch.zeros(n, dtype=torch.int64, device=dev))
+                 actions=torch.zeros((n, int(self.pool.n_act)), **f32) if self.float_pool else
+                 torch.zeros(n, dtype=torch.int64, device=dev))
         if net.is_recurrent:
             D["h_states"] = torch.zeros((n, net.h_size), **f32)
         self.datas = D
         self.runner = Runner(D, self.hyps, None, None, None, env_pool=self.pool,
-                             uniform_fn=None if self.uniform_fn is None else self._uniforms, stash=False, bootstrap=False)
+                             uniform_fn=None if self.uniform_fn is None else self._uniforms,
+                             normal_fn=None if self.normal_fn is None else self._normals, stash=False, bootstrap=False)
         self.ep_rew = torch.zeros(E, **f32)
         self.ep_len, self.active = (torch.zeros(E, dtype=torch.int32, device=dev) for _ in range(2))
         self.n_active = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1488,7 +1516,7 @@ class DeviceStatsRunner:
         self.active.fill_(1)
 
     def rollout(self, net):
-        if not getattr(net, "is_discrete", True):
+        if not getattr(net, "is_discrete", True) and not self.float_pool:
             raise ValueError("DeviceStatsRunner: the device worlds take discrete actions; the net is continuous")
         net._ensure_device()
         if self.runner is None:
@@ -1510,7 +1538,7 @@ class DeviceStatsRunner:
                               self.active, self.n_active)
                 if self.keep_actions:
                     for k in kept:
-                        kept[k].append(D[k].view(E, K).t().clone())
+                        kept[k].append(D[k].view(E, K, *D[k].shape[1:]).transpose(0, 1).clone())
                 left = int(self.n_active.item())               # the one host read of the chunk
                 chunk += 1
                 if left == 0 or chunk * K >= self.max_steps:

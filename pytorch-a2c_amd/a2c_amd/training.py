@@ -21,7 +21,7 @@ from collections import deque
 import numpy as np
 import torch
 
-from . import breakout, models, pong, preprocessing, snake, worlds
+from . import breakout, models, point, pong, preprocessing, snake, worlds
 from .runner import DeviceStatsRunner, HostEnvPool, Runner, SequentialEnvironment, StatsRunner
 from .updater import Updater
 from .utils import cuda_if, deque_maxmin, try_key
@@ -55,7 +55,11 @@ _WORLDS = {
     "Pong": (pong, "pong_prep", True, True, ("points_to_win", "max_episode_steps", "opp_skill_num", "opp_skill_den"), True,
              pong.RULE_KEYS),
     "Breakout": (breakout, "breakout_prep", False, False, ("lives", "max_episode_steps"), True, breakout.RULE_KEYS),
+    # the continuous-control world: vector observations, two float actions, Gaussian nets only
+    "Point": (point, "null_prep", False, False, ("targets_to_win", "max_episode_steps"), True, point.RULE_KEYS),
 }
+# the nets with a Gaussian head (models.py): what a family whose device pool has ``float_actions`` can be trained with
+_GAUSS_MODELS = ("FCModel", "GRUFCModel")
 # the keys of section 6i that shape what a policy is TRAINED on, not the game: evaluation worlds do not get them
 _TRAINING_ONLY = ("episodic_life", "clip_rewards")
 
@@ -104,7 +108,13 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     0..255 on the uint8 transport; with ``hyps["device_prep"] = "breakout_prep"`` the process pool carries the RAW frames
     and the device preps them); 4 actions, ``action_shift`` 0 unless given, real dones only, evaluation on host
     ``BreakoutEnv``s.
-    ``hyps["eval_pool"] = "device"`` (the three ``*-device`` env types, no ``eval_env``) evaluates on the device instead: a
+    ``env_type`` "Point-device" / "Point-host" (a2c_amd/point.py; keys ``targets_to_win``,
+    ``max_episode_steps``, ``frame_skip`` / ``frame_skip_max`` / ``sticky_num`` / ``sticky_den`` as on the Pong worlds) are the
+    continuous-control world: (1, 8) observations with ``prep_fxn="null_prep"``, ``is_discrete=False``, 2 float actions, for
+    ``model`` FCModel / GRUFCModel only (anything else is a ValueError before anything is allocated).  ``DevicePointPool``
+    reads the float action rows on the device; "Point-host" steps ``PointEnv``s behind ``env_pool`` "serial" (the default)
+    or "process_f32"; evaluation on host ``PointEnv``s.
+    ``hyps["eval_pool"] = "device"`` (the four ``*-device`` env types, no ``eval_env``) evaluates on the device instead: a
     second pool of ``n_test_eps`` worlds behind a ``DeviceStatsRunner`` (keys ``eval_chunk``, ``max_eval_steps``); the default
     ``"host"`` is the host twins.
     Returns the best evaluation reward."""
@@ -113,9 +123,9 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     if eval_pool not in ("host", "device"):
         raise ValueError(f"a2c_amd: hyps['eval_pool'] is 'host' or 'device', not {eval_pool!r}")
     if eval_pool == "device" and (eval_env is not None or env_fn is not None or hyps.get("env_type") not in (
-            "Snake-device", "Pong-device", "Breakout-device")):
+            "Snake-device", "Pong-device", "Breakout-device", "Point-device")):
         raise ValueError("a2c_amd: hyps['eval_pool'] = 'device' evaluates the device worlds (env_type 'Snake-device', "
-                         "'Pong-device' or 'Breakout-device') and takes no eval_env / env_fn")
+                         "'Pong-device', 'Breakout-device' or 'Point-device') and takes no eval_env / env_fn")
     if env_fn is None and _world_family(hyps.get("env_type")) == "Snake":
         if worlds.repeat_from_hyps(hyps, "Snake")[:2] != (1, 0):
             raise ValueError("a2c_amd: frame_skip / sticky_num are keys of the Pong and Breakout worlds: the Snake worlds "
@@ -125,6 +135,15 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
         # family does not take them or they are out of bounds
         family = _world_family(hyps["env_type"])
         rules = worlds.rules_from_hyps(hyps, family, _WORLDS[family][6])
+        if family == "Point":
+            # float actions: the nets with a Gaussian head, never as discrete ones; and no int32 process pool
+            if hyps.get("model") not in _GAUSS_MODELS or try_key(hyps, "is_discrete", False):
+                raise ValueError(f"a2c_amd: the Point worlds take two float actions: model {' / '.join(_GAUSS_MODELS)} with "
+                                 f"is_discrete=False, not {hyps.get('model')!r}"
+                                 + (" with is_discrete=True" if try_key(hyps, "is_discrete", False) else ""))
+            if hyps["env_type"] == "Point-host" and try_key(hyps, "env_pool", None) not in (None, "serial", "process_f32"):
+                raise ValueError("a2c_amd: env_type='Point-host' steps behind env_pool='serial' (the default) or 'process_f32' "
+                                 "(the int process pool and the thread pool carry int32 actions)")
     if hyps["n_rollouts"] is None:
         hyps["n_rollouts"] = hyps["n_envs"]
     hyps["main_path"] = try_key(hyps, "main_path", "./")
@@ -154,7 +173,10 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                                  "the process env pool (the device worlds write prepped frames themselves)")
         hyps["prep_fxn"] = "null_prep" if raw else prep_name
         prep = hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
-        hyps["is_discrete"], n_act = True, mod.N_ACTIONS
+        cont_world = bool(getattr(getattr(mod, "Device" + family + "Pool"), "float_actions", False))
+        hyps["is_discrete"], n_act = not cont_world, (mod.ACTION_SIZE if cont_world else mod.N_ACTIONS)
+        if cont_world:      # a Box: in this process unless env_pool='process_f32' (as below for every continuous env)
+            serial = try_key(hyps, "env_pool", None) != "process_f32"
         # a policy that circles never ends its evaluation episode: cap it (StatsRunner reads the key)
         hyps["max_eval_steps"] = try_key(hyps, "max_eval_steps", 2000)
         if repeats:
@@ -178,7 +200,10 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
             # frame_bits: {0, 1} uint8 planes cross the host link one bit per pixel; grey levels one byte per pixel
             pool = ProcessEnvPool(SequentialEnvironment, hyps["n_envs"], env_kwargs=kws,
                                   n_workers=try_key(hyps, "n_env_workers", None), pong=pong_done,
-                                  action_shift=try_key(hyps, "action_shift", 0), frame_bits=bits)
+                                  action_shift=try_key(hyps, "action_shift", 0), frame_bits=bits,
+                                  action_dim=n_act if cont_world else None,
+                                  # (null_prep puts an axis in front of the twin's (1, 8) row: the states are the device pool's)
+                                  frame_shape=world_shape if cont_world else None)
     elif env_fn is None:
         hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
         probe = eval_env or SequentialEnvironment(**hyps)             # the probe for shapes (training.py:60-65)

@@ -3,6 +3,7 @@ the bounds of frame skip and sticky actions, ``HostWorld`` -- the agent step of 
 and ``DeviceWorldPool``, the Runner's device-pool protocol over ``n_envs`` worlds in device memory (the kernels' side:
 csrc/world.h)."""
 import functools
+import math
 
 _M = 0xFFFFFFFF
 MAX_FRAME_SKIP, MAX_STICKY_DEN = 8, 1 << 16
@@ -152,7 +153,7 @@ class HostWorld:
         ``frame_skip_max`` above it ONE draw d taken first: k = frame_skip + d mod (frame_skip_max - frame_skip + 1)"""
         if self.over or self.closed:
             raise RuntimeError(f"{self.WHAT}Env.step() after done: call reset()")
-        a = int(action) % self.N_ACTIONS
+        a = self._action(action)
         k = self.frame_skip
         if self.frame_skip_max > k:
             k += self._draw() % (self.frame_skip_max - k + 1)
@@ -175,6 +176,11 @@ class HostWorld:
                 break
         self._check_step(total)
         return total, done or self.closed
+
+    def _action(self, action):
+        """what ``step`` was handed as the int the game frames take: ``action mod N_ACTIONS``; a world with float actions
+        (point.py) packs its quantised components instead.  0 must be the action ``prev`` holds after an episode end"""
+        return int(action) % self.N_ACTIONS
 
     def _check_step(self, total):
         pass
@@ -213,7 +219,7 @@ class DeviceWorldPool:
         if self.B < self.MIN_ENVS:
             raise ValueError(f"{type(self).__name__}: n_envs >= {self.MIN_ENVS}")
         self.env_id0 = _env_id0(env_id0, self.B)
-        self.HW = self.frame_shape[1] * self.frame_shape[2]
+        self.HW = math.prod(self.frame_shape[1:])          # (1, H, W) pictures, or a (1, L) vector
         self.words = words
         dev = self.device
         self.state = torch.zeros((self.B, self.words), dtype=torch.int32, device=dev)
