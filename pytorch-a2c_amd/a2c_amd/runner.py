@@ -132,6 +132,111 @@ class _Frames:
         self.ptr32, self.ptr8, self.stride = ptr32, ptr8, stride
 
 
+def env_action(na_j, shift, cont):
+    """what env.step receives: int(action) + shift, or the float32 (n,) vector + shift"""
+    if cont:
+        return na_j + np.float32(shift)
+    return int(na_j) + shift
+
+
+def host_env_step(pool, env0, B, np_act, np_frames, np_rew, np_done, ep_rew, rew_q, shift, pong, cont):
+    """Envs env0..env0+B of an in-process pool take one step (runner.py:208-232): actions from rows env0.. of the numpy view
+    ``np_act`` (``env_action``: int, or with ``cont`` float rows), frames / rewards / dones into the same rows of the other
+    views.  ``ep_rew`` sums each env's rewards; an episode's end folds the sum into the EMA that ``rew_q`` holds.  With
+    ``pong`` a non-zero reward ends the agent's episode, not the env's: no reset, done row 0."""
+    for j in range(env0, env0 + B):
+        obs, rew, done = pool.step(j, env_action(np_act[j], shift, cont))
+        ep_rew[j] += rew
+        reset = done
+        if pong and rew != 0:
+            done = True
+        if done and rew_q is not None:                                 # runner.py:216-217
+            rew_q.put(.99 * rew_q.get() + .01 * ep_rew[j])
+        if done:
+            ep_rew[j] = 0
+        if reset:
+            obs = pool.reset(j)
+        np_frames[j] = np.asarray(obs, dtype=np.float32).reshape(-1)
+        np_rew[j], np_done[j] = rew, float(reset)
+
+
+def play_graph(cache, key, body):
+    """The one graph state machine of the rollout paths.  ``body()`` only enqueues.  First call of ``key``: ``body()`` runs
+    eagerly (the conv tile tuners measure on eager calls) and the key is "warm"; second call: captured into a
+    torch.cuda.CUDAGraph, stored and replayed; later calls: replayed.  A capture that raises stores False, for good.
+    -> what ``cache[key]`` now holds; on False nothing was played and the caller decides what is."""
+    g = cache.get(key)
+    if g is None:
+        cache[key] = "warm"
+        body()
+        return "warm"
+    if g == "warm":
+        try:
+            g = torch.cuda.CUDAGraph()
+            with ops.graph_capture(g):
+                body()
+            cache[key] = g
+        except Exception:      # noqa: BLE001 -- capture not possible here
+            torch.cuda.synchronize()
+            g = cache[key] = False
+    if g:
+        g.replay()
+    return g
+
+
+class _Slot:
+    """One block of a rollout: slots slot0..slot0+B played by envs env0..env0+B for T steps -- what every rollout path
+    reads, built once in ``Runner._rollout_block``.  The segmented path adds its own fields (``_rollout_block_segmented``)."""
+
+    def __init__(self, r, net, slot0, env0, B, hyps):
+        D = r.datas
+        self.r, self.net, self.slot0, self.env0, self.B, self.hyps = r, net, slot0, env0, B, hyps
+        self.T, self.S = int(hyps["n_tsteps"]), r.S
+        self.gamma, self.pong, self.shift = hyps["gamma"], "Pong" in hyps["env_type"], hyps["action_shift"]
+        self.bm = r.bookmark[env0:env0 + B]
+        self.val_prev, self.done_eff = r.val_prev[env0:env0 + B], r.done_eff[env0:env0 + B]
+        self.h = None if r.h is None else r.h[env0:env0 + B]
+        self.act = r.act_dev[env0:env0 + B]
+        self.acts_host_out = D["actions"] if not D["actions"].is_cuda else None
+        # recurrent nets: bookkeeping + frame stack + hidden-state reset + the h_states row in ONE launch (a2c_rollout_post_rec,
+        # .._post_frames); GRUModel's cell stash needs it
+        self.fused_post = (self.h is not None and r.HW % 4 == 0 and r.S % 4 == 0
+                           and os.environ.get("A2C_NO_FUSED_POST") != "1")
+        self.fused = self.relay = self.lazy = False
+        self.stash = self.ub = self.fs = self.post_done = None
+
+    def sp(self, t):
+        """address of states[slot0*T + t]; the B slots' rows are T*S floats apart"""
+        return self.r.datas["states"].data_ptr() + 4 * (self.slot0 * self.T + t) * self.S
+
+    def nxt(self, t):
+        """(address, row stride) of the state after env step t: states[slot0*T + t + 1], or the bookmark after the last"""
+        return (self.sp(t + 1), self.T * self.S) if t + 1 < self.T else (self.bm.data_ptr(), self.S)
+
+    def act_row(self, t):
+        """(address, element stride) of datas['actions'][slot0*T + t] for B slots T rows apart (int64 or float rows of n)"""
+        a, n = self.r.datas["actions"], self.r.n_act
+        if self.r.cont:
+            return a.data_ptr() + 4 * n * (self.slot0 * self.T + t), self.T * n
+        return a.data_ptr() + 8 * (self.slot0 * self.T + t), self.T
+
+    def act_dst(self, t):
+        """where the sampler writes the actions of step t: in place into a device-resident actions buffer, else staging"""
+        if self.acts_host_out is None:
+            return self.act_row(t)
+        return self.act.data_ptr(), (self.r.n_act if self.r.cont else 1)
+
+    def h_row(self, t):
+        """(address, row stride) of datas['h_states'][slot0*T + t] (recurrent nets)"""
+        hd = self.h.shape[1]
+        return self.r.datas["h_states"].data_ptr() + 4 * (self.slot0 * self.T + t) * hd, self.T * hd
+
+    def acts_to_host_out(self, t, src):
+        """a host `actions` tensor like the reference's: step t's rows of the B slots"""
+        if self.acts_host_out is not None:
+            self.acts_host_out[self.slot0 * self.T + t:(self.slot0 + self.B) * self.T:self.T] = src
+
+
 class Runner:
     """Collects rollouts for ALL envs of this process into ``datas`` (reference signature:
     runner.py:110).  ``datas`` tensors should live on the device (``cuda_if`` them like
@@ -152,6 +257,17 @@ class Runner:
         self.ingest = ingest or try_key(hyps, "ingest", None)     # None: zero-copy when it applies, else memcpy
         self._ready = False
         self.error = None                     # exception that ended run() (training.train re-raises it)
+        self.proc_pool = self.device_pool = False     # (what the env pool is: start())
+        self.dev_prep = None
+        self._warned_partial = False
+        # what the rollout paths keep between calls: the slot's persistent noise (T, n_envs) / (T, n_envs, n), the relay's
+        # step counter, action staging, the frame store, and the graphs of the device (whole slot) and host (segment) paths:
+        # key -> "warm" (played eagerly once), a torch.cuda.CUDAGraph, or False (capture failed: eager for good)
+        self._u_buf = self._e_buf = self._seq_dev = self._act_gather = self._acts_dev = self._fstore = None
+        self._fstore_ok = True
+        self._states_stale = self._lm_written = False
+        self._frames_written = None
+        self._dev_graphs, self._seg_graphs = {}, {}
 
     # ------------------------------------------------------------------ set-up (body of run())
     def _make_pool(self):
@@ -315,7 +431,7 @@ class Runner:
                         # ONE Runner per gate_q is what performs: Runners sharing a gate_q (the reference's topology) each
                         # take part of the epoch's tokens, stall here once per epoch and play partial batches (which also
                         # re-capture slot graphs and defeat the activation stash).  Say so instead of stalling silently.
-                        if not getattr(self, "_warned_partial", False):
+                        if not self._warned_partial:
                             self._warned_partial = True
                             warnings.warn("a2c_amd.Runner: %d of %d gate tokens after %.2f s -- playing a partial batch; use ONE "
                                           "Runner per gate_q (or set hyps['gate_timeout_s'])" % (len(idxs), n_tok, gate_to),
@@ -344,14 +460,14 @@ class Runner:
         """Wait for the enqueued rollout work, surface a host-handshake timeout of the persistent kernel,
         publish the episode-reward EMA the env workers kept (runner.py:216) and let the workers idle."""
         torch.cuda.current_stream().synchronize()
-        if getattr(self, "proc_pool", False):
+        if self.proc_pool:
             if not (self.env_pool.dev_phase and self.datas["actions"].is_cuda):
                 self.env_pool.set_phase(0)
             self.check()
             if self.rew_q is not None:
                 self.rew_q.get()
                 self.rew_q.put(self.env_pool.rew_ema())
-        elif getattr(self, "device_pool", False) and self.rew_q is not None and hasattr(self.env_pool, "episode_stats"):
+        elif self.device_pool and self.rew_q is not None and hasattr(self.env_pool, "episode_stats"):
             # the pool counted finished episodes and summed their rewards on the device: ONE read per rollout.  The k
             # episodes enter the EMA of runner.py:216 together, as k updates with their mean
             k, total = self.env_pool.episode_stats()
@@ -359,12 +475,12 @@ class Runner:
                 self.rew_q.put(.99 ** k * self.rew_q.get() + (1 - .99 ** k) * total / k)
 
     def check(self):
-        if getattr(self, "proc_pool", False) and int(self.rollout_err.item()):
+        if self.proc_pool and int(self.rollout_err.item()):
             self.env_pool._check_workers()
             raise TimeoutError("a2c_a3c_rollout: an env worker did not answer within the time-out")
 
     def close(self):
-        if getattr(self, "proc_pool", False):
+        if self.proc_pool:
             self.env_pool.close()
 
     # ------------------------------------------------------------------ the rollout
@@ -380,7 +496,7 @@ class Runner:
         N = self.datas["states"].shape[0]
         T_ = int(hyps["n_tsteps"])
         # rows a lazy rollout (hyps['lazy_states']) left in the single-frame store only: a partial refill keeps the others
-        if getattr(self, "_states_stale", False):
+        if self._states_stale:
             if idxs == list(range(N // T_)):
                 self._states_stale = False
             else:
@@ -434,10 +550,10 @@ class Runner:
         if dev_phase:       # ... the last env step has been played: the workers sleep-poll through the update
             ops.store_u32_system(dev_phase, 0)
         if stash_all:
-            if getattr(self, "_lm_written", False):      # (A3CModel, ring kernel: lane masks of a1 beside the stash)
-                net.stash_commit(self.datas["states"], N, frames=getattr(self, "_frames_written", None), lanemask=True)
+            if self._lm_written:      # (A3CModel, ring kernel: lane masks of a1 beside the stash)
+                net.stash_commit(self.datas["states"], N, frames=self._frames_written, lanemask=True)
             else:
-                net.stash_commit(self.datas["states"], N, frames=getattr(self, "_frames_written", None))
+                net.stash_commit(self.datas["states"], N, frames=self._frames_written)
 
     def _uniforms(self, t, B, env0):
         if self.uniform_fn is not None:
@@ -449,12 +565,25 @@ class Runner:
             return self.normal_fn(t, B, env0).reshape(B, self.n_act)
         return torch.randn((B, self.n_act), device=self.net._dev, dtype=torch.float32)
 
-    def _act_row(self, slot0, T, t):
-        """(address, element stride) of datas['actions'][slot0*T + t] for B slots T rows apart (int64 or float rows of n)"""
+    def _slot_noise(self, T, env0, B):
+        """the slot's noise in ONE persistent buffer each (rows are what graph nodes read), filled before the slot and outside
+        any graph: uniforms ``_u_buf`` (T, n_envs); continuous nets: N(0,1) ``_e_buf`` (T, n_envs, n) instead"""
+        dev = self.net._dev
+        if self._u_buf is None or self._u_buf.shape != (T, self.B):
+            self._u_buf = torch.zeros((T, self.B), dtype=torch.float32, device=dev)
+        ub = self._u_buf
         if self.cont:
             n = self.n_act
-            return self.datas["actions"].data_ptr() + 4 * n * (slot0 * T + t), T * n
-        return self.datas["actions"].data_ptr() + 8 * (slot0 * T + t), T
+            if self._e_buf is None or self._e_buf.shape != (T, self.B, n):
+                self._e_buf = torch.zeros((T, self.B, n), dtype=torch.float32, device=dev)
+            for t in range(T):
+                self._e_buf[t, env0:env0 + B].copy_(self._normals(t, B, env0))
+        elif self.uniform_fn is not None:
+            for t in range(T):
+                ub[t, env0:env0 + B].copy_(self.uniform_fn(t, B, env0).reshape(B))
+        else:
+            ub[:, env0:env0 + B] = torch.rand((T, B), device=dev, dtype=torch.float32)
+        return ub
 
     def _sample(self, net, logits, u, eps, a_ptr, a_stride, B, st, pub=None):
         """actions of the step from the policy heads: softmax sampling, or mu + sigma*eps (a2c_gauss_head).  pub = (act, act_stride,
@@ -467,12 +596,6 @@ class Runner:
         else:
             ops.softmax_sample(logits, u, a_ptr, a_stride, B, net.output_space, st=st)
 
-    def _env_action(self, na_j, shift):
-        """what env.step receives: int(action) + shift, or the float32 (n,) vector + shift"""
-        if self.cont:
-            return na_j + np.float32(shift)
-        return int(na_j) + shift
-
     def _forward(self, net, x_ptr, bstride, B, env0, st, sampler=None, stash=None):
         """stash = (bufs, row0, row_stride): conv-stack nets write this step's activations into the update's buffers"""
         kw = dict(stash=stash) if (stash is not None and isinstance(stash[0], list)) else {}
@@ -484,7 +607,7 @@ class Runner:
 
     def _zero_copy_ok(self, net):
         """the persistent one-launch rollout applies: A3CModel-shaped net, process pool with uint8 frames"""
-        if not self.proc_pool or self.h is not None or self.ingest in ("memcpy", "relay") or getattr(self, "dev_prep", None):
+        if not self.proc_pool or self.h is not None or self.ingest in ("memcpy", "relay") or self.dev_prep:
             return False
         ok = (getattr(net, "_step_supported", lambda: False)() and self.u8 and self.HW % 16 == 0 and self.HW <= 8192
               and self.env_pool.dev_ptr != 0)
@@ -493,269 +616,196 @@ class Runner:
                              "process env pool with uint8 frames")
         return ok
 
+    def _policy_step(self, c, t, a_ptr, a_stride, st, noise=None):
+        """one env step of the policy on state t of the slot: the h_states row (recurrent nets, runner.py:201), the forward
+        with its sampler, the sampling launch unless the forward sampled, the new hidden rows back into ``h`` unless the net
+        updated them in place.  noise = (u, eps) rows of the slot's persistent buffers; None: drawn here, per step.
+        -> the forward's outputs"""
+        net, h, B, env0 = c.net, c.h, c.B, c.env0
+        if h is not None:
+            hd = h.shape[1]
+            ops.copy_rows(h.data_ptr(), hd, *c.h_row(t), B, hd, st)
+        if noise is None:
+            noise = (None, self._normals(t, B, env0)) if self.cont else (self._uniforms(t, B, env0), None)
+        u, eps = noise
+        out = self._forward(net, c.sp(t), c.T * c.S, B, env0, st, sampler=None if self.cont else (u, a_ptr, a_stride))
+        if not out.get("sampled", False):
+            self._sample(net, out["logits"], u, eps, a_ptr, a_stride, B, st)
+        if h is not None and out["h"].data_ptr() != h.data_ptr():      # (the GRU models update h in place)
+            ops.copy_rows(out["h"].data_ptr(), h.shape[1], h.data_ptr(), h.shape[1], B, h.shape[1], st)
+        return out
+
+    def _step_args(self, c, k, fr, rew, done, reset, stash):
+        """keyword block of ``net._step`` (a2c_a3c_step) for launch k of the slot, less the sampling / bootstrap arguments:
+        launch k writes state k -- the frame stack of state k-1 and the frame ``fr`` env step k-1 returned, restarted where
+        ``reset`` says; the bookmark for k == T -- and records env step k-1 (``rew``, ``done``); launch 0 copies the
+        bookmark.  stash = (a1, a2, heads) rows of the update's buffers: the activations of state (slot, k) go there too."""
+        D, T, S, slot0 = self.datas, c.T, c.S, c.slot0
+        kw = dict(val_prev=c.val_prev.data_ptr(), rewards=D["rewards"].data_ptr(), dones=D["dones"].data_ptr(),
+                  deltas=D["deltas"].data_ptr(), T=T, slot0=slot0, gamma=float(c.gamma), pong=int(c.pong))
+        if stash is not None and k < T:      # conv activations of state (slot, k) -> row slot*T + k of the update's buffers
+            n1, n2, hs = stash[0][0].numel(), stash[1][0].numel(), stash[2]
+            kw.update(a1_out=stash[0].data_ptr() + 4 * (slot0 * T + k) * n1, a1_stride=T * n1,
+                      a2_out=stash[1].data_ptr() + 4 * (slot0 * T + k) * n2, a2_stride=T * n2,
+                      heads_out=hs.data_ptr() + 4 * (slot0 * T + k) * hs.stride(0), heads_out_stride=T * hs.stride(0))
+        if k == 0:        # state of step 0 = the bookmark left by the previous slot (runner.py:190)
+            kw.update(prev=c.bm.data_ptr(), prev_stride=S, out=c.sp(0), out_stride=T * S)
+        else:
+            out_ptr, out_stride = c.nxt(k - 1)
+            kw.update(prev=c.sp(k - 1), prev_stride=T * S, reset_mask=reset.data_ptr(), out=out_ptr, out_stride=out_stride,
+                      rew=rew.data_ptr(), done=done.data_ptr(), t_rec=k - 1)
+            kw.update(dict(frame_u8=fr.ptr8, frame_stride=fr.stride) if fr.ptr8 else dict(frame_new=fr.ptr32))
+        return kw
+
     def _rollout_block(self, net, slot0, env0, B, hyps):
         D, pool = self.datas, self.env_pool
-        T, S, C, HW = int(hyps["n_tsteps"]), self.S, self.C, self.HW
-        gamma = hyps["gamma"]
-        pong = "Pong" in hyps["env_type"]
-        shift = hyps["action_shift"]
         st = ops.stream()
         if hasattr(net, "_set_rollout_batch"):
             net._set_rollout_batch(B)
         net._refresh(st)
-        states, rewards, dones, deltas = D["states"], D["rewards"], D["dones"], D["deltas"]
         for name in ("states", "rewards", "dones", "deltas"):
             ops._chk(D[name], name)
-        sp = lambda t: states.data_ptr() + 4 * (slot0 * T + t) * S        # states[slot0*T + t]
-        bm = self.bookmark[env0:env0 + B]
-        val_prev, done_eff = self.val_prev[env0:env0 + B], self.done_eff[env0:env0 + B]
-        h = None if self.h is None else self.h[env0:env0 + B]
-        acts_host_out = D["actions"] if not D["actions"].is_cuda else None
+        c = _Slot(self, net, slot0, env0, B, hyps)
         self._stash_used = False
         if self._zero_copy_ok(net):
-            return self._rollout_block_persistent(net, slot0, env0, B, hyps, bm, val_prev, acts_host_out, st)
-        # The per-step bookkeeping kernel only feeds later bookkeeping, so it CAN run on a side stream
-        # next to the frame-stack kernel (two branches in the hipGraph).  Measured on MI355X the
-        # fork/join costs more than the 4.8 us it hides (16.0 -> 17.8 ms per 256x128 epoch), so it is
-        # opt-in (A2C_SIDE_STREAM=1).
+            return self._rollout_block_persistent(net, slot0, env0, B, hyps, c.bm, c.val_prev, c.acts_host_out, st)
         if not self.device_pool and os.environ.get("A2C_NO_STEP_GRAPHS") != "1":
-            return self._rollout_block_segmented(net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h, acts_host_out)
-        if (self.device_pool and hasattr(pool, "device_step_post") and (not self.cont or self.float_pool) and acts_host_out is None
-                and try_key(hyps, "rollout_graphs", True) and os.environ.get("A2C_NO_SLOT_GRAPH") != "1"
-                and os.environ.get("A2C_SIDE_STREAM") != "1"):
-            return self._rollout_block_device(net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h)
+            return self._rollout_block_segmented(c)
+        if (self.device_pool and hasattr(pool, "device_step_post") and (not self.cont or self.float_pool)
+                and c.acts_host_out is None and try_key(hyps, "rollout_graphs", True)
+                and os.environ.get("A2C_NO_SLOT_GRAPH") != "1"):
+            return self._rollout_block_device(c)
         self._fstore_ok = False          # this slot is played by a path that does not keep the frame store: it goes stale
-        main = torch.cuda.current_stream()
-        side = None
-        if h is None and os.environ.get("A2C_SIDE_STREAM") == "1":
-            if getattr(self, "_side", None) is None:
-                self._side = torch.cuda.Stream(device=net._dev)
-            side = self._side
-        if h is None and side is None and getattr(net, "_step_supported", lambda: False)():
-            return self._rollout_block_fused(net, slot0, env0, B, hyps, sp, bm, val_prev, acts_host_out, st)
+        if c.h is None and getattr(net, "_step_supported", lambda: False)():
+            return self._rollout_block_fused(c, st)
+        # (The per-step bookkeeping launch only feeds later bookkeeping; running it on a second stream beside the frame-stack
+        # launch was tried, and the fork and join cost more than they hid.)
         # state of step 0 = the bookmark left by the previous slot (runner.py:190)
-        ops.copy_rows(bm.data_ptr(), S, sp(0), T * S, B, S, st)
-        for t in range(T):
-            if h is not None:                                              # h_states[e] = h (runner.py:201)
-                hs = D["h_states"]
-                ops.copy_rows(h.data_ptr(), h.shape[1], hs.data_ptr() + 4 * (slot0 * T + t) * h.shape[1],
-                              T * h.shape[1], B, h.shape[1], st)
-            u = self._uniforms(t, B, env0) if not self.cont else None
-            eps = self._normals(t, B, env0) if self.cont else None
-            act = self.act_dev[env0:env0 + B]
-            if acts_host_out is None:      # device-resident actions buffer: write it in place
-                a_ptr, a_stride = self._act_row(slot0, T, t)
-            else:
-                a_ptr, a_stride = act.data_ptr(), (self.n_act if self.cont else 1)
-            out = self._forward(net, sp(t), T * S, B, env0, st, sampler=None if self.cont else (u, a_ptr, a_stride))
-            logits, vals = out["logits"], out["vals"]
-            if not out.get("sampled", False):
-                self._sample(net, logits, u, eps, a_ptr, a_stride, B, st)
-            if h is not None and out["h"].data_ptr() != h.data_ptr():      # (the GRU models update h in place)
-                ops.copy_rows(out["h"].data_ptr(), h.shape[1], h.data_ptr(), h.shape[1], B, h.shape[1], st)
-            fr, rew, done, reset = self._env_step(pool, act, a_ptr, a_stride, env0, B, t, slot0, T, shift, acts_host_out, pong)
-            nxt_ptr, nxt_stride = (sp(t + 1), T * S) if t + 1 < T else (bm.data_ptr(), S)
-            if h is None and side is None and HW % 4 == 0 and S % 4 == 0 and os.environ.get("A2C_NO_POST_FUSE") != "1":
-                # feed-forward net: bookkeeping + next frame stack in ONE launch
-                if fr.ptr8:
-                    ops.rollout_post_u8(rew, done, vals.data_ptr(), vals.stride(0), val_prev, rewards, dones, deltas, T, t,
-                                        slot0, gamma, pong, fr.ptr8, fr.stride, reset, sp(t), T * S, nxt_ptr, nxt_stride, B,
-                                        C, HW, st)
-                else:
-                    ops.rollout_post(rew, done, vals.data_ptr(), vals.stride(0), val_prev, rewards, dones, deltas, T, t,
-                                     slot0, gamma, pong, _Ptr(fr.ptr32), reset, sp(t), T * S, nxt_ptr, nxt_stride, B, C,
-                                     HW, st)
-                continue
-            if side is not None:
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    ops.rollout_record(rew, done, vals.data_ptr(), vals.stride(0), val_prev, rewards, dones, deltas,
-                                       done_eff, None, B, T, t, slot0, gamma, pong, side.cuda_stream)
-            else:
-                ops.rollout_record(rew, done, vals.data_ptr(), vals.stride(0), val_prev, rewards, dones, deltas, done_eff,
-                                   h, B, T, t, slot0, gamma, pong, st)
-            # next state (utils.next_state): into states[t+1], or the bookmark after the last step
-            if fr.ptr8:
-                ops.frame_stack_push_u8(fr.ptr8, fr.stride, reset, sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
-            else:
-                ops.frame_stack_push(_Ptr(fr.ptr32), reset, sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
-            if side is not None:
-                main.wait_stream(side)     # join before the next forward overwrites the heads buffer
-        if not self.bootstrap:
-            return
-        # bootstrap (runner.py:236-245): value of the state after the last step
-        out = self._forward(net, bm.data_ptr(), S, B, env0, st)
-        ops.rollout_bootstrap(out["vals"].data_ptr(), out["vals"].stride(0), val_prev, rewards, dones, deltas, B, T,
-                              slot0, gamma, st)
+        ops.copy_rows(c.bm.data_ptr(), c.S, c.sp(0), c.T * c.S, B, c.S, st)
+        for t in range(c.T):
+            a_ptr, a_stride = c.act_dst(t)
+            vals = self._policy_step(c, t, a_ptr, a_stride, st)["vals"]
+            fr, rew, done, reset = self._env_step(c, a_ptr, a_stride, t)
+            self._post_step(c, t, fr, rew, done, reset, vals.data_ptr(), vals.stride(0),
+                            os.environ.get("A2C_NO_POST_FUSE") != "1", st)
+        if self.bootstrap:
+            self._bootstrap(c, st)
 
-    def _rollout_block_fused(self, net, slot0, env0, B, hyps, sp, bm, val_prev, acts_host_out, st, ub=None):
+    def _post_step(self, c, t, fr, rew, done, reset, v_ptr, v_ld, fuse, st):
+        """bookkeeping of env step t (runner.py:212-232; the values of state t are at v_ptr) and the next state
+        (utils.next_state) into states[t+1], or into the bookmark after the last step.  fuse: feed-forward nets do both in
+        ONE launch"""
+        D, slot0, B, T, S, C, HW = self.datas, c.slot0, c.B, c.T, c.S, self.C, self.HW
+        rewards, dones, deltas = D["rewards"], D["dones"], D["deltas"]
+        nxt_ptr, nxt_stride = c.nxt(t)
+        if fuse and c.h is None and HW % 4 == 0 and S % 4 == 0:
+            if fr.ptr8:
+                ops.rollout_post_u8(rew, done, v_ptr, v_ld, c.val_prev, rewards, dones, deltas, T, t, slot0, c.gamma, c.pong,
+                                    fr.ptr8, fr.stride, reset, c.sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
+            else:
+                ops.rollout_post(rew, done, v_ptr, v_ld, c.val_prev, rewards, dones, deltas, T, t, slot0, c.gamma, c.pong,
+                                 _Ptr(fr.ptr32), reset, c.sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
+            return
+        ops.rollout_record(rew, done, v_ptr, v_ld, c.val_prev, rewards, dones, deltas, c.done_eff, c.h, B, T, t, slot0,
+                           c.gamma, c.pong, st)
+        if fr.ptr8:
+            ops.frame_stack_push_u8(fr.ptr8, fr.stride, reset, c.sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
+        else:
+            ops.frame_stack_push(_Ptr(fr.ptr32), reset, c.sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
+
+    def _bootstrap(self, c, st):
+        """bootstrap (runner.py:236-245): the value of the state after the last step closes the slot's deltas"""
+        D = self.datas
+        out = self._forward(c.net, c.bm.data_ptr(), c.S, c.B, c.env0, st)
+        ops.rollout_bootstrap(out["vals"].data_ptr(), out["vals"].stride(0), c.val_prev, D["rewards"], D["dones"], D["deltas"],
+                              c.B, c.T, c.slot0, c.gamma, st)
+
+    def _rollout_block_fused(self, c, st, ub=None):
         """The same slot with ONE launch per step (a2c_a3c_step): launch t writes state t (frame
         stack of the frame env step t-1 returned), records env step t-1, runs the policy and samples
         action t; launch T records step T-1, leaves the bookmark and bootstraps (runner.py:174-248)."""
-        D, pool = self.datas, self.env_pool
-        T, S = int(hyps["n_tsteps"]), self.S
-        gamma, pong, shift = hyps["gamma"], "Pong" in hyps["env_type"], hyps["action_shift"]
-        rec = dict(val_prev=val_prev.data_ptr(), rewards=D["rewards"].data_ptr(), dones=D["dones"].data_ptr(),
-                   deltas=D["deltas"].data_ptr(), T=T, slot0=slot0, gamma=float(gamma), pong=int(pong))
+        net, env0, B, T = c.net, c.env0, c.B, c.T
         fr = rew = done = reset = None
         stash = self._stash_bufs
         self._stash_used = stash is not None
         for t in range(T + 1):
-            kw = dict(rec)
-            if stash is not None and t < T:      # conv activations of state (slot, t) -> row slot*T + t of the update's buffers
-                n1, n2 = stash[0][0].numel(), stash[1][0].numel()
-                kw.update(a1_out=stash[0].data_ptr() + 4 * (slot0 * T + t) * n1, a1_stride=T * n1,
-                          a2_out=stash[1].data_ptr() + 4 * (slot0 * T + t) * n2, a2_stride=T * n2,
-                          heads_out=stash[2].data_ptr() + 4 * (slot0 * T + t) * stash[2].stride(0),
-                          heads_out_stride=T * stash[2].stride(0))
-            if t == 0:        # state of step 0 = the bookmark left by the previous slot (runner.py:190)
-                kw.update(prev=bm.data_ptr(), prev_stride=S, out=sp(0), out_stride=T * S)
-            else:
-                out_ptr, out_stride = (sp(t), T * S) if t < T else (bm.data_ptr(), S)
-                kw.update(prev=sp(t - 1), prev_stride=T * S, reset_mask=reset.data_ptr(),
-                          out=out_ptr, out_stride=out_stride, rew=rew.data_ptr(), done=done.data_ptr(), t_rec=t - 1)
-                if fr.ptr8:
-                    kw.update(frame_u8=fr.ptr8, frame_stride=fr.stride)
-                else:
-                    kw.update(frame_new=fr.ptr32)
+            kw = self._step_args(c, t, fr, rew, done, reset, stash)
             if t == T:
                 net._step(B, st, bootstrap=int(self.bootstrap), **kw)
                 break
             u = self._uniforms(t, B, env0) if ub is None else ub[t, env0:env0 + B]      # ub: the slot's persistent uniforms
-            act = self.act_dev[env0:env0 + B]
-            if acts_host_out is None:
-                a_ptr, a_stride = D["actions"].data_ptr() + 8 * (slot0 * T + t), T
-            else:
-                a_ptr, a_stride = act.data_ptr(), 1
+            a_ptr, a_stride = c.act_dst(t)
             net._step(B, st, u=u.data_ptr(), actions=a_ptr, act_stride=a_stride, **kw)
-            fr, rew, done, reset = self._env_step(pool, act, a_ptr, a_stride, env0, B, t, slot0, T, shift, acts_host_out, pong)
+            fr, rew, done, reset = self._env_step(c, a_ptr, a_stride, t)
             for name, x in (("rew", rew), ("done", done), ("reset", reset)):
                 ops._chk(x, name)
 
     # ------------------------------------------------------------------ device pools: the slot as one hipGraph
-    def _rollout_block_device(self, net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h):
+    def _rollout_block_device(self, c):
         """Device env pools with ``device_step_post`` (the Snake / Pong / Breakout worlds): nothing happens on the host between
         the env steps, so the WHOLE slot -- T steps and the bootstrap -- is ONE hipGraph, like the relay branch of
-        _rollout_block_segmented: the slot's uniforms live in the persistent (T, n_envs) buffer and are filled before the
-        slot, outside the graph; the first rollout of a key runs eagerly (the conv tile tuners measure on eager calls), the
-        second is captured, later ones replay it; a failed capture issues the same launches eagerly, for good.  Called with
-        the stream already capturing (a caller's own graph), the block issues the same launches into that capture and
-        leaves its warm / graph state alone.  ``rollout_graphs=False`` (or A2C_NO_SLOT_GRAPH=1) is _rollout_block's eager
-        loop, which plays the same steps bit for bit."""
-        D, pool = self.datas, self.env_pool
-        T = int(hyps["n_tsteps"])
-        dev = net._dev
+        _rollout_block_segmented: the slot's noise lives in persistent buffers filled before the slot, outside the graph
+        (``_slot_noise``); the first rollout of a key runs eagerly, the second is captured, later ones replay it; a failed
+        capture issues the same launches eagerly, for good (``play_graph``).  Called with the stream already capturing (a
+        caller's own graph), the block issues the same launches into that capture and leaves its warm / graph state alone.
+        ``rollout_graphs=False`` (or A2C_NO_SLOT_GRAPH=1) is _rollout_block's eager loop, which plays the same steps bit
+        for bit."""
+        D, pool, net = self.datas, self.env_pool, c.net
         self._fstore_ok = False          # this slot does not keep the frame store: it goes stale
-        if getattr(self, "_u_buf", None) is None or self._u_buf.shape != (T, self.B):
-            self._u_buf = torch.zeros((T, self.B), dtype=torch.float32, device=dev)
-        ub = self._u_buf
-        if self.cont:       # continuous nets: the slot's N(0,1) noise, one persistent (T, n_envs, n) buffer likewise
-            n = self.n_act
-            if getattr(self, "_e_buf", None) is None or self._e_buf.shape != (T, self.B, n):
-                self._e_buf = torch.zeros((T, self.B, n), dtype=torch.float32, device=dev)
-            for t in range(T):
-                self._e_buf[t, env0:env0 + B].copy_(self._normals(t, B, env0))
-        elif self.uniform_fn is not None:
-            for t in range(T):
-                ub[t, env0:env0 + B].copy_(self.uniform_fn(t, B, env0).reshape(B))
-        else:
-            ub[:, env0:env0 + B] = torch.rand((T, B), device=dev, dtype=torch.float32)
-        fused = h is None and getattr(net, "_step_supported", lambda: False)()
+        ub = self._slot_noise(c.T, c.env0, c.B)
+        fused = c.h is None and getattr(net, "_step_supported", lambda: False)()
         stash = self._stash_bufs if fused else None
         self._stash_used = stash is not None
 
         def body():
             st = ops.stream()      # (a capture runs on a stream of its own: not the one the caller was on)
             if fused:       # a2c_a3c_step records, stacks, runs the policy and samples; the world's plain step feeds it
-                self._rollout_block_fused(net, slot0, env0, B, hyps, sp, bm, val_prev, None, st, ub=ub)
+                self._rollout_block_fused(c, st, ub=ub)
             else:
-                self._device_slot(net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h, st, ub)
+                self._device_slot(c, st, ub)
         if torch.cuda.is_current_stream_capturing():
             return body()
         stash_ptrs = None if stash is None else tuple(x.data_ptr() for x in stash if hasattr(x, "data_ptr"))
         # (the worlds' launches carry their env ids: a re-based pool is another key)
-        key = (id(net), id(pool), int(getattr(pool, "env_id0", 0)), slot0, env0, B, T, float(hyps["gamma"]),
-               "Pong" in hyps["env_type"], fused, stash_ptrs, tuple(D[k].data_ptr() for k in sorted(D) if D[k].is_cuda))
-        cache = self.__dict__.setdefault("_dev_graphs", {})
-        g = cache.get(key)
-        if g is None:
-            cache[key] = "warm"
-            return body()
-        if g == "warm":
-            try:
-                g = torch.cuda.CUDAGraph()
-                with ops.graph_capture(g):
-                    body()
-                cache[key] = g
-            except Exception:      # noqa: BLE001 -- capture not possible here: this key is played eagerly from now on
-                torch.cuda.synchronize()
-                g = cache[key] = False
-        if g:
-            g.replay()
-        else:
+        key = (id(net), id(pool), int(getattr(pool, "env_id0", 0)), c.slot0, c.env0, c.B, c.T, float(c.gamma), c.pong, fused,
+               stash_ptrs, tuple(D[k].data_ptr() for k in sorted(D) if D[k].is_cuda))
+        if play_graph(self._dev_graphs, key, body) is False:      # capture not possible here: played eagerly from now on
             body()
 
-    def _device_slot(self, net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h, st, ub):
-        """the launches of one slot on a device pool, nets without the one-launch step kernel: per env step the h_states row
-        (recurrent nets), the forward with its sampler, and ONE launch for the world's step, the bookkeeping and the next
-        state (a2c_<world>_step_post); then the bootstrap.  Only enqueues, reads its uniforms from ``ub``: safe to capture."""
-        D, pool = self.datas, self.env_pool
-        T, S, C = int(hyps["n_tsteps"]), self.S, self.C
-        gamma, pong = hyps["gamma"], "Pong" in hyps["env_type"]
+    def _device_slot(self, c, st, ub):
+        """the launches of one slot on a device pool, nets without the one-launch step kernel: per env step the policy step
+        (``_policy_step``) and ONE launch for the world's step, the bookkeeping and the next state (a2c_<world>_step_post);
+        then the bootstrap.  Only enqueues, reads its noise from the slot's persistent buffers: safe to capture."""
+        D, pool, h = self.datas, self.env_pool, c.h
+        slot0, env0, B, T, S = c.slot0, c.env0, c.B, c.T, c.S
         rewards, dones, deltas = D["rewards"], D["dones"], D["deltas"]
-        ops.copy_rows(bm.data_ptr(), S, sp(0), T * S, B, S, st)          # state 0 = the bookmark (runner.py:190)
+        ops.copy_rows(c.bm.data_ptr(), S, c.sp(0), T * S, B, S, st)      # state 0 = the bookmark (runner.py:190)
         for t in range(T):
-            if h is not None:                                              # h_states[e] = h (runner.py:201)
-                hd = h.shape[1]
-                ops.copy_rows(h.data_ptr(), hd, D["h_states"].data_ptr() + 4 * (slot0 * T + t) * hd, T * hd, B, hd, st)
             # (continuous nets: a2c_gauss_head writes the float action rows in place, from the slot's persistent noise)
-            u = None if self.cont else ub[t, env0:env0 + B]
-            eps = self._e_buf[t, env0:env0 + B] if self.cont else None
-            a_ptr, a_stride = self._act_row(slot0, T, t)
-            out = self._forward(net, sp(t), T * S, B, env0, st, sampler=None if self.cont else (u, a_ptr, a_stride))
-            vals = out["vals"]
-            if not out.get("sampled", False):
-                self._sample(net, out["logits"], u, eps, a_ptr, a_stride, B, st)
-            if h is not None and out["h"].data_ptr() != h.data_ptr():      # (the GRU models update h in place)
-                ops.copy_rows(out["h"].data_ptr(), h.shape[1], h.data_ptr(), h.shape[1], B, h.shape[1], st)
-            nxt_ptr, nxt_stride = (sp(t + 1), T * S) if t + 1 < T else (bm.data_ptr(), S)
+            noise = (None, self._e_buf[t, env0:env0 + B]) if self.cont else (ub[t, env0:env0 + B], None)
+            a_ptr, a_stride = c.act_row(t)
+            vals = self._policy_step(c, t, a_ptr, a_stride, st, noise)["vals"]
+            nxt_ptr, nxt_stride = c.nxt(t)
             # (done_eff is written for recurrent nets only, as the eager loop's a2c_rollout_record does)
-            post = ops.world_post(vals.data_ptr(), vals.stride(0), val_prev, rewards, dones, deltas, T, t, slot0, gamma, pong,
-                                  sp(t), T * S, nxt_ptr, nxt_stride, C, done_eff=None if h is None else done_eff, h=h)
+            post = ops.world_post(vals.data_ptr(), vals.stride(0), c.val_prev, rewards, dones, deltas, T, t, slot0, c.gamma,
+                                  c.pong, c.sp(t), T * S, nxt_ptr, nxt_stride, self.C,
+                                  done_eff=None if h is None else c.done_eff, h=h)
             pool.device_step_post(t, env0, B, (a_ptr, a_stride), post)
-        if not self.bootstrap:
-            return
-        out = self._forward(net, bm.data_ptr(), S, B, env0, st)            # bootstrap (runner.py:236-245)
-        ops.rollout_bootstrap(out["vals"].data_ptr(), out["vals"].stride(0), val_prev, rewards, dones, deltas, B, T, slot0,
-                              gamma, st)
+        if self.bootstrap:
+            self._bootstrap(c, st)
 
     # ------------------------------------------------------------------ host pools: one hipGraph per time step
-    def _rollout_block_segmented(self, net, slot0, env0, B, hyps, sp, bm, val_prev, done_eff, h, acts_host_out):
+    def _rollout_block_segmented(self, c):
         """Host env pools (memcpy ingest): the slot is T+1 device SEGMENTS separated by the one host hand-off of
         each env step.  Segment k = [H2D of what env step k-1 returned + its bookkeeping + frame stack] followed by
         [forward + sampling of state k + D2H of the actions] (k < T) or by the bootstrap (k == T).  A segment has
-        no host dependency inside, so each one is captured into a hipGraph the first time it runs (all pointers --
-        rollout buffer rows, workspaces, the pinned pool region, the slot's uniforms buffer -- are stable across
+        no host dependency inside, so each one is captured into a hipGraph the second time it runs (all pointers --
+        rollout buffer rows, workspaces, the pinned pool region, the slot's noise buffers -- are stable across
         epochs) and replayed afterwards: ONE launch per env step instead of 5-30 (runner.py:198-232 per step)."""
         D, pool = self.datas, self.env_pool
-        T, S = int(hyps["n_tsteps"]), self.S
-        shift, pong = hyps["action_shift"], "Pong" in hyps["env_type"]
+        net, slot0, env0, B, T, hyps, h, acts_host_out = c.net, c.slot0, c.env0, c.B, c.T, c.hyps, c.h, c.acts_host_out
         dev = net._dev
-        # the slot's uniforms in ONE persistent buffer (rows are what the graph nodes read)
-        if getattr(self, "_u_buf", None) is None or self._u_buf.shape != (T, self.B):
-            self._u_buf = torch.zeros((T, self.B), dtype=torch.float32, device=dev)
-        ub = self._u_buf
-        if self.cont:       # continuous nets: the slot's N(0,1) noise, one persistent (T, B, n) buffer likewise
-            n = self.n_act
-            if getattr(self, "_e_buf", None) is None or self._e_buf.shape != (T, self.B, n):
-                self._e_buf = torch.zeros((T, self.B, n), dtype=torch.float32, device=dev)
-            for t in range(T):
-                self._e_buf[t, env0:env0 + B].copy_(self._normals(t, B, env0))
-        elif self.uniform_fn is not None:
-            for t in range(T):
-                ub[t, env0:env0 + B].copy_(self.uniform_fn(t, B, env0).reshape(B))
-        else:
-            ub[:, env0:env0 + B] = torch.rand((T, B), device=dev, dtype=torch.float32)
+        c.ub = self._slot_noise(T, env0, B)
         # device relay (a2c_pool_publish_actions / a2c_pool_ingest): the segments hand actions and frames to the env
         # workers through the pinned region themselves, so the T+1 launches queue back to back with no host in between
         relay = (self.proc_pool and pool.dev_ptr != 0 and acts_host_out is None and self.ingest != "memcpy"
@@ -764,7 +814,7 @@ class Runner:
             raise ValueError("ingest='relay' needs a registered process/thread env pool and a device-resident "
                              "datas['actions'] tensor")
         if relay:
-            if getattr(self, "_seq_dev", None) is None:
+            if self._seq_dev is None:
                 self._seq_dev = torch.zeros(1, dtype=torch.int32, device=dev)
                 self._seq_pin = torch.zeros(64, dtype=torch.int32).pin_memory()      # ring: one entry per block in flight
                 self._seq_i = 0
@@ -789,122 +839,89 @@ class Runner:
         if fs is None:
             self._fstore_ok = False      # this slot does not keep the store: it goes stale
         lazy = fs is not None and bool(try_key(hyps, "lazy_states", False))
-        ctx = dict(net=net, slot0=slot0, env0=env0, B=B, T=T, hyps=hyps, sp=sp, bm=bm, val_prev=val_prev, done_eff=done_eff,
-                   h=h, acts_host_out=acts_host_out, fused=fused, stash=stash, ub=ub, relay=relay, fs=fs, lazy=lazy)
+        c.fused, c.stash, c.relay, c.fs, c.lazy = fused, stash, relay, fs, lazy
         if fs is not None:
             if self._stash_used:
                 self._frames_written = (fs[0], fs[1], T)
             if lazy:
                 self._states_stale = True
                 net._materialize_states = self.materialize_states
-        graphs = None
+
+        def whole():
+            for k in range(T + 1):
+                self._segment(k, c)
+        cache = key = None
         if try_key(hyps, "rollout_graphs", True) and torch.cuda.is_available():
-            key = (id(net), slot0, env0, B, T, fused, stash is not None, acts_host_out is None, pong, relay, float(hyps["gamma"]),
+            cache = self._seg_graphs
+            key = (id(net), slot0, env0, B, T, fused, stash is not None, acts_host_out is None, c.pong, relay, float(c.gamma),
                    fs is not None, lazy, tuple(D[k].data_ptr() for k in sorted(D) if D[k].is_cuda))
-            cache = self.__dict__.setdefault("_seg_graphs", {})
-            graphs = cache.setdefault(key, [None] * (T + 1))
-        if graphs is not None and relay and os.environ.get("A2C_NO_SLOT_GRAPH") != "1":
+        if cache is not None and relay and os.environ.get("A2C_NO_SLOT_GRAPH") != "1":
             # device relay: nothing happens on the host between the segments, so the WHOLE slot (T+1 segments, a few
-            # thousand kernel nodes) is ONE hipGraph -- first rollout eager (tuners), second captured, then replayed
-            whole = cache.setdefault(key + ("slot",), [None])
-            if whole[0] is None:
-                whole[0] = "warm"
-                for k in range(T + 1):
-                    self._segment(k, ctx)
-            else:
-                if whole[0] == "warm":
-                    try:
-                        g = torch.cuda.CUDAGraph()
-                        with ops.graph_capture(g):
-                            for k in range(T + 1):
-                                self._segment(k, ctx)
-                        whole[0] = g
-                    except Exception:      # noqa: BLE001 -- fall back to one graph per segment
-                        torch.cuda.synchronize()
-                        whole[0] = False
-                if whole[0]:
-                    whole[0].replay()
-            if whole[0] is not False:
-                self._mark_cells_done(net, stash, h, slot0, T, S, B)
+            # thousand kernel nodes) is ONE hipGraph; a failed capture falls back to one graph per segment
+            if play_graph(cache, key + ("slot",), whole) is not False:
+                self._mark_cells_done(c)
                 return
         for k in range(T + 1):
-            if graphs is None:
-                self._segment(k, ctx)
-            else:
-                if graphs[k] is None:          # first visit: eager (the conv tile tuners measure on eager calls only)
-                    graphs[k] = "warm"
-                    self._segment(k, ctx)
-                    if k < T and not relay:
-                        torch.cuda.current_stream().synchronize()
-                        self._host_env_step(pool, env0, B, k, slot0, T, shift, acts_host_out, pong)
-                    continue
-                if graphs[k] == "warm":
-                    try:
-                        g = torch.cuda.CUDAGraph()
-                        with ops.graph_capture(g):
-                            self._segment(k, ctx)
-                        graphs[k] = g
-                    except Exception:      # noqa: BLE001 -- capture not possible here: run this slot eagerly
-                        torch.cuda.synchronize()
-                        graphs[k] = False
-                if graphs[k]:
-                    graphs[k].replay()
-                else:
-                    self._segment(k, ctx)
-            if k < T and not relay:
+            # (a segment whose capture failed is played eagerly)
+            if cache is None or play_graph(cache, key + (k,), lambda: self._segment(k, c)) is False:
+                self._segment(k, c)
+            if k < T and not relay:     # the host hand-off of env step k
                 torch.cuda.current_stream().synchronize()
-                self._host_env_step(pool, env0, B, k, slot0, T, shift, acts_host_out, pong)
-        self._mark_cells_done(net, stash, h, slot0, T, S, B)
+                self._host_env_step(c, k)
+        self._mark_cells_done(c)
 
-    def _mark_cells_done(self, net, stash, h, slot0, T, S, B):
-        ro = getattr(net, "_roll_outputs", None)
-        if ro and stash is not None and h is not None and self.HW % 4 == 0 and S % 4 == 0 and \
-                os.environ.get("A2C_NO_FUSED_POST") != "1" and ro((stash, slot0 * T, T), B) is not None:
-            net._cells_done = T - 1          # every step of every slot went through the cell stash (eagerly or replayed)
+    def _mark_cells_done(self, c):
+        ro = getattr(c.net, "_roll_outputs", None)
+        if ro and c.stash is not None and c.fused_post and ro((c.stash, c.slot0 * c.T, c.T), c.B) is not None:
+            c.net._cells_done = c.T - 1      # every step of every slot went through the cell stash (eagerly or replayed)
 
-    def _post_frames_args(self, k, c, rew, done):
-        """arguments of a2c_rollout_post_frames for env step k - 1 of this segment context (after rew, done; before the stream):
-        where segment k - 1's forward left the values of its states and its new hidden rows -- the roll buffers, or rows of the
-        update's buffers (GRUModel's cell stash) -- a pure function of (net, k), safe under graph replay"""
-        net, slot0, env0, B, T, hyps = c["net"], c["slot0"], c["env0"], c["B"], c["T"], c["hyps"]
-        D, h = self.datas, c["h"]
-        hb, logits, vals = net._heads("roll", B)
-        ro = getattr(net, "_roll_outputs", None)
-        fused_post = h is not None and self.HW % 4 == 0 and self.S % 4 == 0 and os.environ.get("A2C_NO_FUSED_POST") != "1"
-        prev = ro((c["stash"], slot0 * T + k - 1, T), B) if (ro and c["stash"] is not None and k > 0 and fused_post) else None
-        v_ptr, v_ld, h_src = prev if prev else (vals.data_ptr(), vals.stride(0), 0)
-        F_, nv_rows, nv_carry = c["fs"]
-        hrow = 0
+    def _values_src(self, c, k):
+        """-> (v_ptr, v_ld, h_src): where segment k - 1's forward left the values of its states and its new hidden rows -- the
+        roll buffers (h_src 0: ``h`` itself), or rows of the update's buffers (GRUModel's cell stash, which needs the fused post
+        kernels) -- a pure function of (net, k), safe under graph replay"""
+        hb, logits, vals = c.net._heads("roll", c.B)
+        ro = getattr(c.net, "_roll_outputs", None)
+        prev = None
+        if ro and c.stash is not None and k > 0 and c.fused_post:
+            prev = ro((c.stash, c.slot0 * c.T + k - 1, c.T), c.B)
+        return prev if prev else (vals.data_ptr(), vals.stride(0), 0)
+
+    def _post_frames_args(self, k, c):
+        """arguments of a2c_rollout_post_frames for env step k - 1 of this slot (after rew, done; before the stream)"""
+        D, h = self.datas, c.h
+        v_ptr, v_ld, h_src = self._values_src(c, k)
+        F_, nv_rows, nv_carry = c.fs
+        hrow = hstride = 0
         if h is not None:
-            hrow = D["h_states"].data_ptr() + 4 * (slot0 * T + k) * h.shape[1] if k < T else 0
-        return (v_ptr, v_ld, c["val_prev"], D["rewards"], D["dones"], D["deltas"], T, k - 1, slot0, hyps["gamma"],
-                "Pong" in hyps["env_type"], c["done_eff"], h, hrow, 0 if h is None else T * h.shape[1], h_src, nv_rows,
-                nv_carry.data_ptr() + 4 * env0)
+            hrow, hstride = c.h_row(k) if k < c.T else (0, c.T * h.shape[1])
+        return (v_ptr, v_ld, c.val_prev, D["rewards"], D["dones"], D["deltas"], c.T, k - 1, c.slot0, c.gamma, c.pong,
+                c.done_eff, h, hrow, hstride, h_src, nv_rows, nv_carry.data_ptr() + 4 * c.env0)
 
     def _segment(self, k, c):
         """device work of segment k (see _rollout_block_segmented); only enqueues, never waits on the host"""
-        net, slot0, env0, B, T, hyps = c["net"], c["slot0"], c["env0"], c["B"], c["T"], c["hyps"]
+        net, slot0, env0, B, T, hyps = c.net, c.slot0, c.env0, c.B, c.T, c.hyps
         D, pool, S, C, HW = self.datas, self.env_pool, self.S, self.C, self.HW
-        sp, bm, val_prev, done_eff, h = c["sp"], c["bm"], c["val_prev"], c["done_eff"], c["h"]
-        gamma, pong = hyps["gamma"], "Pong" in hyps["env_type"]
+        sp, bm, val_prev, done_eff, h = c.sp, c.bm, c.val_prev, c.done_eff, c.h
+        gamma, pong = c.gamma, c.pong
         rewards, dones, deltas = D["rewards"], D["dones"], D["deltas"]
         st = ops.stream()
         fr = rew = done = None
-        if k > 0 and c.get("relay"):       # what env step k-1 returned: waited for and fetched by the device itself
+        if k > 0 and c.relay:       # what env step k-1 returned: waited for and fetched by the device itself
             rew, done = self.d_rew[env0:env0 + B], self.d_done[env0:env0 + B]
             fs, ds = self.fstride, self.dstride
             dst = self.d_frames.data_ptr() + env0 * ds
-            if c.get("fs") is not None:      # single-frame store: the new frame lands in frames[slot][k+3], nowhere else
-                F_ = c["fs"][0]
+            if c.fs is not None:      # single-frame store: the new frame lands in frames[slot][k+3], nowhere else
+                F_ = c.fs[0]
                 ds = F_.stride(0)
                 dst = F_.data_ptr() + slot0 * ds + (k + 3) * HW
             ticks = int(float(try_key(hyps, "env_timeout_s", 20.0)) * 1e8)
-            post = self._post_frames_args(k, c, rew, done) if (c.get("fs") is not None and not self.dev_prep
-                                                               and os.environ.get("A2C_NO_FUSED_POST_INGEST") != "1") else None
+            post = None
+            if c.fs is not None and not self.dev_prep and os.environ.get("A2C_NO_FUSED_POST_INGEST") != "1":
+                post = self._post_frames_args(k, c)
             if post is not None:     # the ingest workgroup of an env also does its bookkeeping (rollout_post_frames) of step k - 1
                 ops.pool_ingest_post(self.bits, pool.dev_rec + 8 * env0, pool.dev_frames + env0 * fs, fs, HW if self.bits else fs, B,
                                      self._seq_dev, k, ticks, self.rollout_err, rew, done, dst, ds, *post, st)
-                c["_post_done"] = k
+                c.post_done = k
             elif self.dev_prep:      # raw frames cross the link; crop / stride / binarise on the device into dst
                 raw = self.d_raw.data_ptr() + env0 * fs
                 ops.pool_ingest(pool.dev_rec + 8 * env0, pool.dev_frames + env0 * fs, fs, fs, B, self._seq_dev, k,
@@ -916,7 +933,7 @@ class Runner:
             else:
                 ops.pool_ingest(pool.dev_rec + 8 * env0, pool.dev_frames + env0 * fs, fs, fs, B, self._seq_dev, k,
                                 ticks, self.rollout_err, rew, done, dst, ds, st)
-            fr = self._staged_frames(dst, env0, B, st) if c.get("fs") is None else None
+            fr = self._staged_frames(dst, env0, B, st) if c.fs is None else None
         elif k > 0:     # what env step k-1 returned: pinned staging -> HBM
             rew, done = self.d_rew[env0:env0 + B], self.d_done[env0:env0 + B]
             rew.copy_(self.h_rew[env0:env0 + B], non_blocking=True)
@@ -927,114 +944,74 @@ class Runner:
                 df = self.d_frames[env0:env0 + B]
                 df.copy_(self.h_frames[env0:env0 + B], non_blocking=True)
                 fr = _Frames(ptr32=df.data_ptr())
-        act = self.act_dev[env0:env0 + B]
-        if c["acts_host_out"] is None:
-            a_ptr, a_stride = self._act_row(slot0, T, min(k, T - 1))
-        else:
-            a_ptr, a_stride = act.data_ptr(), (self.n_act if self.cont else 1)
-        if c["fused"]:      # a2c_a3c_step: record(k-1) + frame stack + forward + sample (+ bootstrap) in ONE launch
-            kw = dict(val_prev=val_prev.data_ptr(), rewards=rewards.data_ptr(), dones=dones.data_ptr(), deltas=deltas.data_ptr(),
-                      T=T, slot0=slot0, gamma=float(gamma), pong=int(pong))
-            if k == 0:
-                kw.update(prev=bm.data_ptr(), prev_stride=S, out=sp(0), out_stride=T * S)
-            else:
-                out_ptr, out_stride = (sp(k), T * S) if k < T else (bm.data_ptr(), S)
-                kw.update(prev=sp(k - 1), prev_stride=T * S, reset_mask=done.data_ptr(), out=out_ptr, out_stride=out_stride,
-                          rew=rew.data_ptr(), done=done.data_ptr(), t_rec=k - 1)
-                kw.update(dict(frame_u8=fr.ptr8, frame_stride=fr.stride) if fr.ptr8 else dict(frame_new=fr.ptr32))
-            if c["stash"] is not None and k < T:
-                n1, n2 = c["stash"][0][0].numel(), c["stash"][1][0].numel()
-                kw.update(a1_out=c["stash"][0].data_ptr() + 4 * (slot0 * T + k) * n1, a1_stride=T * n1,
-                          a2_out=c["stash"][1].data_ptr() + 4 * (slot0 * T + k) * n2, a2_stride=T * n2)
-                hs = c["stash"][2]
-                kw.update(heads_out=hs.data_ptr() + 4 * (slot0 * T + k) * hs.stride(0), heads_out_stride=T * hs.stride(0))
+        act = c.act
+        a_ptr, a_stride = c.act_dst(min(k, T - 1))
+        if c.fused:      # a2c_a3c_step: record(k-1) + frame stack + forward + sample (+ bootstrap) in ONE launch
+            kw = self._step_args(c, k, fr, rew, done, done, c.stash)      # (a host pool's envs reset where they are done)
             if k == T:
                 net._step(B, st, bootstrap=1, **kw)
                 return
-            net._step(B, st, u=c["ub"][k, env0:env0 + B].data_ptr(), actions=a_ptr, act_stride=a_stride, **kw)
+            net._step(B, st, u=c.ub[k, env0:env0 + B].data_ptr(), actions=a_ptr, act_stride=a_stride, **kw)
         else:
-            hb, logits, vals = net._heads("roll", B)
-            # where segment k-1's forward left the values of its states and its new hidden rows: the roll buffers, or
-            # rows of the update's buffers (GRUModel's cell stash) -- a pure function of (net, k), safe under graph replay
-            ro = getattr(net, "_roll_outputs", None)
-            fused_post = h is not None and HW % 4 == 0 and S % 4 == 0 and os.environ.get("A2C_NO_FUSED_POST") != "1"
-            prev = ro((c["stash"], slot0 * T + k - 1, T), B) if (ro and c["stash"] is not None and k > 0 and fused_post) else None
-            v_ptr, v_ld, h_src = prev if prev else (vals.data_ptr(), vals.stride(0), 0)
+            fused_post = c.fused_post
+            v_ptr, v_ld, h_src = self._values_src(c, k)
             h_row_done = False
-            if c.get("fs") is not None:
-                F_, nv_rows, nv_carry = c["fs"]
+            if c.fs is not None:
+                F_, nv_rows, nv_carry = c.fs
                 ss = F_.stride(0)
                 f0 = F_.data_ptr() + slot0 * ss
                 nvr, nvc = nv_rows.data_ptr() + 4 * slot0 * T, nv_carry.data_ptr() + 4 * env0
                 if k == 0:  # state 0 = the window the previous slot ended with (the bookmark, runner.py:190)
                     ops.frame_store_begin(f0, ss, T, C, HW, nvr, nvc, B, st)
-                elif c.get("_post_done") == k:      # ... done by the ingest launch of this segment (a2c_pool_ingest_post)
+                elif c.post_done == k:      # ... done by the ingest launch of this segment (a2c_pool_ingest_post)
                     h_row_done = h is not None
                 else:       # bookkeeping of env step k-1 (runner.py:212-232); the frame is already in the store
-                    pa = self._post_frames_args(k, c, rew, done)
+                    pa = self._post_frames_args(k, c)
                     ops.rollout_post_frames(rew, done, *pa[:11], B, *pa[11:], st)
                     h_row_done = h is not None
                 if k == T:  # the bookmark state stays materialised: any other rollout path can take over from here
                     ops.frames_to_states(f0 + T * HW, ss, nvc, 1, bm.data_ptr(), S, B, 1, C, HW, st)
                     net._frames_src = (f0 + T * HW, ss, 1, nvc, 1)
                 else:
-                    if not c["lazy"]:   # the reference's fp32 row of `states` (runner.py:199), expanded from the window
+                    if not c.lazy:   # the reference's fp32 row of `states` (runner.py:199), expanded from the window
                         ops.frames_to_states(f0 + k * HW, ss, nvr + 4 * k, T, sp(k), T * S, B, 1, C, HW, st)
                     net._frames_src = (f0 + k * HW, ss, 1, nvr + 4 * k, T)
             elif k == 0:    # state of step 0 = the bookmark left by the previous slot (runner.py:190)
                 ops.copy_rows(bm.data_ptr(), S, sp(0), T * S, B, S, st)
             else:           # bookkeeping of env step k-1 + the next state (utils.next_state)
                 t = k - 1
-                nxt_ptr, nxt_stride = (sp(k), T * S) if k < T else (bm.data_ptr(), S)
-                if h is None and HW % 4 == 0 and S % 4 == 0:
-                    if fr.ptr8:
-                        ops.rollout_post_u8(rew, done, v_ptr, v_ld, val_prev, rewards, dones, deltas, T, t,
-                                            slot0, gamma, pong, fr.ptr8, fr.stride, done, sp(t), T * S, nxt_ptr, nxt_stride, B,
-                                            C, HW, st)
-                    else:
-                        ops.rollout_post(rew, done, v_ptr, v_ld, val_prev, rewards, dones, deltas, T, t,
-                                         slot0, gamma, pong, _Ptr(fr.ptr32), done, sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
-                elif fused_post:
+                if fused_post:
                     # recurrent nets: bookkeeping + frame stack + hidden-state reset + the h_states row in ONE launch
-                    hs = D["h_states"]
-                    hrow = hs.data_ptr() + 4 * (slot0 * T + k) * h.shape[1] if k < T else 0
+                    nxt_ptr, nxt_stride = c.nxt(t)
+                    hrow = c.h_row(k)[0] if k < T else 0
                     ops.rollout_post_rec(rew, done, v_ptr, v_ld, val_prev, rewards, dones, deltas, T, t,
                                          slot0, gamma, pong, fr.ptr32 or 0, fr.ptr8 or 0, fr.stride if fr.ptr8 else 0, done,
                                          sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, done_eff, h, hrow, T * h.shape[1],
                                          h_src_ptr=h_src, st=st)
                     h_row_done = True
-                else:
-                    ops.rollout_record(rew, done, v_ptr, v_ld, val_prev, rewards, dones, deltas, done_eff,
-                                       h, B, T, t, slot0, gamma, pong, st)
-                    if fr.ptr8:
-                        ops.frame_stack_push_u8(fr.ptr8, fr.stride, done, sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
-                    else:
-                        ops.frame_stack_push(_Ptr(fr.ptr32), done, sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
-            if k == T:      # bootstrap (runner.py:236-245): value of the state after the last step
+                else:       # (a host pool's envs reset where they are done)
+                    self._post_step(c, t, fr, rew, done, done, v_ptr, v_ld, True, st)
+            if k == T:
                 try:
-                    out = self._forward(net, bm.data_ptr(), S, B, env0, st)
+                    self._bootstrap(c, st)
                 finally:
                     net._frames_src = None
-                ops.rollout_bootstrap(out["vals"].data_ptr(), out["vals"].stride(0), val_prev, rewards, dones, deltas, B, T,
-                                      slot0, gamma, st)
                 return
             if h is not None and not h_row_done:                            # h_states[e] = h (runner.py:201)
-                hs = D["h_states"]
-                ops.copy_rows(h.data_ptr(), h.shape[1], hs.data_ptr() + 4 * (slot0 * T + k) * h.shape[1], T * h.shape[1], B,
-                              h.shape[1], st)
-            u = c["ub"][k, env0:env0 + B]
+                ops.copy_rows(h.data_ptr(), h.shape[1], *c.h_row(k), B, h.shape[1], st)
+            u = c.ub[k, env0:env0 + B]
             net._cell_stash_ok = fused_post            # the cell stash needs the fused post kernel (h_src) of the next segment
             try:
                 pub = None      # device relay: the heads kernel's sampling thread hands the action to the env worker itself
-                if c.get("relay") and os.environ.get("A2C_NO_FUSED_PUBLISH") != "1":
+                if c.relay and os.environ.get("A2C_NO_FUSED_PUBLISH") != "1":
                     pub = (pool.dev_cmd + 8 * env0, self._seq_dev, k)
                 out = self._forward(net, sp(k), T * S, B, env0, st, sampler=(u, a_ptr, a_stride, pub),
-                                    stash=None if c["stash"] is None else (c["stash"], slot0 * T + k, T))
+                                    stash=None if c.stash is None else (c.stash, slot0 * T + k, T))
             finally:
                 net._frames_src = None
             if not out.get("sampled", False):
                 gpub = None
-                if c.get("relay") and self.cont:      # float action granules + doorbells of env step k, from the sampling threads
+                if c.relay and self.cont:      # float action granules + doorbells of env step k, from the sampling threads
                     ast = int(pool.header.act_stride)
                     gpub = (pool.dev_act + 8 * ast * env0, ast, pool.dev_cmd + 8 * env0, self._seq_dev, k)
                 self._sample(net, out["logits"], u, self._e_buf[k, env0:env0 + B] if self.cont else None, a_ptr, a_stride,
@@ -1045,8 +1022,8 @@ class Runner:
                 pass
             elif h is not None and out["h"].data_ptr() != h.data_ptr():    # (the GRU models update h in place)
                 ops.copy_rows(out["h"].data_ptr(), h.shape[1], h.data_ptr(), h.shape[1], B, h.shape[1], st)
-        if c.get("relay"):      # the sampled actions go to the env workers: cmd granules of env step k
-            if not c["fused"] and out.get("published", False):
+        if c.relay:      # the sampled actions go to the env workers: cmd granules of env step k
+            if not c.fused and out.get("published", False):
                 return
             ops.pool_publish_actions(pool.dev_cmd + 8 * env0, a_ptr, a_stride, B, self._seq_dev, k, st)
             return
@@ -1055,39 +1032,30 @@ class Runner:
         if (a_ptr == act.data_ptr()) if self.cont else a_stride == 1:
             ha.copy_(act, non_blocking=True)
         else:
-            if getattr(self, "_act_gather", None) is None:
+            if self._act_gather is None:
                 self._act_gather = torch.zeros_like(self.act_dev)
             ag = self._act_gather[env0:env0 + B]
             ag.copy_(D["actions"][slot0 * T + k::T][:B])
             ha.copy_(ag, non_blocking=True)
 
-    def _host_env_step(self, pool, env0, B, t, slot0, T, shift, acts_host_out, pong):
-        """host half of env step t (the segment's D2H of the actions has completed): hand the actions to the envs,
-        wait for them, leave rewards / dones (/ frames) in the pinned staging the next segment copies up"""
-        na = self.np_act[env0:env0 + B]
-        if acts_host_out is not None:
-            acts_host_out[slot0 * T + t:(slot0 + B) * T:T] = self.h_act[env0:env0 + B]
+    def _pool_exchange(self, c, t):
+        """process pool: the actions of env step t (pinned staging) go to the workers, which step their envs in parallel;
+        wait for them; their rewards / dones come into the pinned staging (the frames stay in the pool's region)"""
+        pool, env0, B = self.env_pool, c.env0, c.B
+        k = pool.seq_of(env0, B) + t
+        pool.post_actions(self.np_act[env0:env0 + B], env0=env0, seq=k)
+        c.acts_to_host_out(t, self.h_act[env0:env0 + B])
+        pool.wait_frames(k + 1, env0=env0, n=B, timeout=float(try_key(self.hyps, "env_timeout_s", 20.0)))
+        pool.unpack(self.np_rew[env0:env0 + B], self.np_done[env0:env0 + B], env0=env0)
+
+    def _host_env_step(self, c, t):
+        """host half of env step t (the D2H of the actions has completed): hand the actions to the envs, wait for them,
+        leave rewards / dones (/ frames) in the pinned staging that is copied up next"""
         if self.proc_pool:
-            k = pool.seq_of(env0, B) + t
-            pool.post_actions(na, env0=env0, seq=k)
-            pool.wait_frames(k + 1, env0=env0, n=B, timeout=float(try_key(self.hyps, "env_timeout_s", 20.0)))
-            pool.unpack(self.np_rew[env0:env0 + B], self.np_done[env0:env0 + B], env0=env0)
-            return
-        nf, nr, nd = (x[env0:env0 + B] for x in (self.np_frames, self.np_rew, self.np_done))
-        for j in range(B):
-            obs, rew, done = pool.step(env0 + j, self._env_action(na[j], shift))
-            self.ep_rew[env0 + j] += rew
-            reset = done
-            if pong and rew != 0:
-                done = True
-            if done and self.rew_q is not None:                            # runner.py:216-217
-                self.rew_q.put(.99 * self.rew_q.get() + .01 * self.ep_rew[env0 + j])
-            if done:
-                self.ep_rew[env0 + j] = 0
-            if reset:
-                obs = pool.reset(env0 + j)
-            nf[j] = np.asarray(obs, dtype=np.float32).reshape(-1)
-            nr[j], nd[j] = rew, float(reset)
+            return self._pool_exchange(c, t)
+        host_env_step(self.env_pool, c.env0, c.B, self.np_act, self.np_frames, self.np_rew, self.np_done, self.ep_rew,
+                      self.rew_q, c.shift, c.pong, self.cont)
+        c.acts_to_host_out(t, self.h_act[c.env0:c.env0 + c.B])
 
     def _rollout_block_persistent(self, net, slot0, env0, B, hyps, bm, val_prev, acts_host_out, st):
         """The whole slot as ONE persistent launch (a2c_a3c_rollout): the workgroups and the env worker
@@ -1104,7 +1072,7 @@ class Runner:
         if acts_host_out is None:
             acts = D["actions"]
         else:
-            if getattr(self, "_acts_dev", None) is None or self._acts_dev.numel() != D["actions"].numel():
+            if self._acts_dev is None or self._acts_dev.numel() != D["actions"].numel():
                 self._acts_dev = torch.zeros(D["actions"].numel(), dtype=torch.int64, device=dev)
             acts = self._acts_dev
         C, H, W = net.input_space[-3:]
@@ -1147,7 +1115,7 @@ class Runner:
                         tagged_chunks=int(pool.header.tagged_chunks), a1_lanemask_rows=0 if lm is None else lm.data_ptr(),
                         a2_maskbit_rows=0 if mb is None else mb.data_ptr())
         # every block of the call must have written them (a rollout of several blocks: all ring launches, or none counts)
-        self._lm_written = (lm is not None) and (getattr(self, "_lm_written", False) or slot0 == 0)
+        self._lm_written = (lm is not None) and (self._lm_written or slot0 == 0)
         if lazy:            # (only after the launch was accepted: a refused call must not leave rows marked stale)
             self._states_stale = True
             net._materialize_states = self.materialize_states
@@ -1161,7 +1129,7 @@ class Runner:
         """hyps['lazy_states']: the rollout kept one uint8 frame per env step (+ valid-plane counts) and did not write the
         fp32 ``states`` rows; this expands ALL of them (runner.py:199's layout and values, bit for bit) -- called by the
         net when an update needs the rows (no activation stash), by ``finish()`` unless hyps['lazy_states'], or by hand."""
-        if not getattr(self, "_states_stale", False):
+        if not self._states_stale:
             return
         F_, nv_rows, _ = self._fstore
         R, T = F_.shape[0], F_.shape[1] - 4
@@ -1178,9 +1146,9 @@ class Runner:
         frames[:, T+3] = the reset frame and one valid plane; any other rollout path switches the store off."""
         on = os.environ.get("A2C_FRAME_STORE") == "1" or bool(try_key(self.hyps, "frame_store", False))
         if not on or os.environ.get("A2C_NO_FRAME_STORE") == "1" or T < 4 or self.HW % 16 or \
-                not getattr(self, "_fstore_ok", True):
+                not self._fstore_ok:
             return None
-        fs = getattr(self, "_fstore", None)
+        fs = self._fstore
         if fs is None:
             if (self.env_pool.seq_env != self.env_pool.seq_start).any() or R != self.B:
                 self._fstore_ok = False
@@ -1192,29 +1160,29 @@ class Runner:
         return fs
 
     # ------------------------------------------------------------------ one env step of B envs
-    def _env_step(self, pool, act, a_ptr, a_stride, env0, B, t, slot0, T, shift, acts_host_out, pong):
+    def _env_step(self, c, a_ptr, a_stride, t):
         """-> (_Frames, rew, done, reset) device views of what the envs returned for the actions just sampled"""
+        pool, env0, B = self.env_pool, c.env0, c.B
         if self.device_pool:
             if getattr(pool, "needs_actions", False):      # an action-driven world: where the sampler wrote this step's actions
                 frames, rew, done, reset = pool.device_step(t, env0, B, actions=(a_ptr, a_stride))
-                if acts_host_out is not None:              # a host `actions` tensor like the reference's: one D2H per step
-                    acts_host_out[slot0 * T + t:(slot0 + B) * T:T] = act.cpu()
+                if c.acts_host_out is not None:            # a host `actions` tensor like the reference's: one D2H per step
+                    c.acts_to_host_out(t, c.act.cpu())
             else:
                 frames, rew, done, reset = pool.device_step(t, env0, B)
             ops._chk(frames, "frames")
             return _Frames(ptr32=frames.data_ptr()), rew, done, reset
         if self.proc_pool:
-            return self._pool_step(pool, act, a_stride, env0, B, t, slot0, T, acts_host_out)
-        return self._host_step(pool, act, a_ptr, a_stride, env0, B, t, slot0, T, shift, acts_host_out, pong)
+            return self._pool_step(c, a_stride, t)
+        return self._host_step(c, a_stride, t)
 
-    def _actions_to_host(self, act, a_stride, env0, B, t, slot0, T):
-        ha = self.h_act[env0:env0 + B]
+    def _actions_to_host(self, c, a_stride, t):
+        ha = self.h_act[c.env0:c.env0 + c.B]
         if (not self.datas["actions"].is_cuda) if self.cont else a_stride == 1:
-            ha.copy_(act, non_blocking=True)
+            ha.copy_(c.act, non_blocking=True)
         else:
-            ha.copy_(self.datas["actions"][slot0 * T + t::T][:B], non_blocking=True)
+            ha.copy_(self.datas["actions"][c.slot0 * c.T + t::c.T][:c.B], non_blocking=True)
         torch.cuda.current_stream().synchronize()
-        return ha
 
     def _staged_frames(self, dst, env0, B, st):
         """_Frames of the B frames staged at ``dst`` (stride self.dstride): uint8 pixels, or fp32 (compacted to dense
@@ -1232,7 +1200,7 @@ class Runner:
         fs, ds = self.fstride, self.dstride
         dst = self.d_frames.data_ptr() + env0 * ds
         src = pool.region.base + pool.header.off_frames + env0 * fs
-        if getattr(self, "dev_prep", None):
+        if self.dev_prep:
             raw = self.d_raw.data_ptr() + env0 * fs
             ops.memcpy_async(raw, src, B * fs, ops.H2D, st)
             ops.frame_prep_u8(self.dev_prep, raw, fs, *self.raw_dims, dst, ds, B, st)
@@ -1244,46 +1212,24 @@ class Runner:
             ops.memcpy_async(dst, src, B * fs, ops.H2D, st)
         return self._staged_frames(dst, env0, B, st)
 
-    def _pool_step(self, pool, act, a_stride, env0, B, t, slot0, T, acts_host_out):
+    def _pool_step(self, c, a_stride, t):
         """memcpy ingest with the process pool: actions D2H -> the workers step their envs in parallel ->
         frames H2D from the pinned region (uint8 when the pool carries uint8) + rewards / dones."""
-        ha = self._actions_to_host(act, a_stride, env0, B, t, slot0, T)
-        k = pool.seq_of(env0, B) + t
-        na = self.np_act[env0:env0 + B]
-        pool.post_actions(na, env0=env0, seq=k)
-        if acts_host_out is not None:
-            acts_host_out[slot0 * T + t:(slot0 + B) * T:T] = ha
-        pool.wait_frames(k + 1, env0=env0, n=B, timeout=float(try_key(self.hyps, "env_timeout_s", 20.0)))
-        pool.unpack(self.np_rew[env0:env0 + B], self.np_done[env0:env0 + B], env0=env0)
-        st = ops.stream()
-        fr = self._pool_frames_h2d(pool, env0, B, st)
+        env0, B = c.env0, c.B
+        self._actions_to_host(c, a_stride, t)
+        self._pool_exchange(c, t)
+        fr = self._pool_frames_h2d(self.env_pool, env0, B, ops.stream())
         dr, dd = self.d_rew[env0:env0 + B], self.d_done[env0:env0 + B]
         dr.copy_(self.h_rew[env0:env0 + B], non_blocking=True)
         dd.copy_(self.h_done[env0:env0 + B], non_blocking=True)
         return fr, dr, dd, dd
 
-    def _host_step(self, pool, act, a_ptr, a_stride, env0, B, t, slot0, T, shift, acts_host_out, pong):
+    def _host_step(self, c, a_stride, t):
         """serial in-process pool: actions D2H -> env.step one after the other -> frames/rewards/dones H2D
         through pinned buffers (numpy views of them: no per-element tensor writes)."""
-        self._actions_to_host(act, a_stride, env0, B, t, slot0, T)
-        na = self.np_act[env0:env0 + B]
-        nf, nr, nd = (x[env0:env0 + B] for x in (self.np_frames, self.np_rew, self.np_done))
-        for j in range(B):
-            obs, rew, done = pool.step(env0 + j, self._env_action(na[j], shift))
-            self.ep_rew[env0 + j] += rew
-            reset = done
-            if pong and rew != 0:
-                done = True
-            if done and self.rew_q is not None:                            # runner.py:216-217
-                self.rew_q.put(.99 * self.rew_q.get() + .01 * self.ep_rew[env0 + j])
-            if done:
-                self.ep_rew[env0 + j] = 0
-            if reset:
-                obs = pool.reset(env0 + j)
-            nf[j] = np.asarray(obs, dtype=np.float32).reshape(-1)
-            nr[j], nd[j] = rew, float(reset)
-        if acts_host_out is not None:
-            acts_host_out[slot0 * T + t:(slot0 + B) * T:T] = self.h_act[env0:env0 + B]
+        env0, B = c.env0, c.B
+        self._actions_to_host(c, a_stride, t)
+        self._host_env_step(c, t)
         df, dr, dd = (x[env0:env0 + B] for x in (self.d_frames, self.d_rew, self.d_done))
         df.copy_(self.h_frames[env0:env0 + B], non_blocking=True)
         dr.copy_(self.h_rew[env0:env0 + B], non_blocking=True)
@@ -1504,7 +1450,7 @@ class DeviceStatsRunner:
         pool, r = self.pool, self.runner
         if not r._ready:
             r.start(net)
-        r.__dict__.get("_dev_graphs", {}).clear()          # (graphs of the ids the pool leaves: never replayed again)
+        r._dev_graphs.clear()          # (graphs of the ids the pool leaves: never replayed again)
         pool.reset_all(env_id0=self.ENV_ID0 + self.calls * self.E)
         ops.frame_stack_push(pool.frames, self._ones, r.bookmark.data_ptr(), r.S, r.bookmark.data_ptr(), r.S, self.E, r.C, r.HW)
         r.val_prev.zero_()

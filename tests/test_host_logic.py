@@ -104,6 +104,111 @@ def test_gloo_world2_sharded_statistics_and_gradient_allreduce():
         assert g0 == 3.0 and gs == 3000.0                                       # sum over ranks: 1 + 2
 
 
+class _FakePool:
+    """3 in-process envs with scripted (reward, done) per step; frames say who produced them: step t of env j is the
+    (2,) frame [j, t + 1], a reset of env j is [j, -1]"""
+
+    def __init__(self, script):
+        self.script, self.t = script, [0, 0, 0]
+        self.actions, self.resets = [], []
+
+    def step(self, j, action):
+        self.actions.append((j, action))
+        rew, done = self.script[j][self.t[j]]
+        self.t[j] += 1
+        return np.array([j, self.t[j]], dtype=np.float64), rew, done
+
+    def reset(self, j):
+        self.resets.append(j)
+        return np.array([j, -1], dtype=np.float64)
+
+
+class _RewQ:
+    """the one-slot queue that holds the episode-reward EMA"""
+
+    def __init__(self, v):
+        self.v, self.puts = v, 0
+
+    def get(self):
+        return self.v
+
+    def put(self, v):
+        self.v, self.puts = v, self.puts + 1
+
+
+def _play_host_steps(pong, cont, env0, B, script, shift=1, steps=4):
+    from a2c_amd.runner import host_env_step
+    pool, q = _FakePool(script), _RewQ(-1.0)
+    np_act = (np.arange(6, dtype=np.float32).reshape(3, 2) if cont else np.array([2, 0, 1], dtype=np.int64))
+    np_frames, np_rew, np_done = np.full((3, 2), 77, np.float32), np.full(3, 77, np.float32), np.full(3, 77, np.float32)
+    ep_rew = np.zeros(3)
+    rows = []
+    for _ in range(steps):
+        host_env_step(pool, env0, B, np_act, np_frames, np_rew, np_done, ep_rew, q, shift, pong, cont)
+        rows.append((np_frames.copy(), np_rew.copy(), np_done.copy(), ep_rew.copy(), q.v))
+    return pool, q, rows
+
+
+def test_host_env_step_pong_reward_ends_the_agents_episode_only():
+    """(a) pong: a non-zero reward folds ep_rew into the EMA and zeroes it; the done row stays 0, the env is not reset"""
+    script = [[(0., False), (1., False), (0., False), (-1., False)]] * 3
+    pool, q, rows = _play_host_steps(True, False, 0, 1, script)
+    ema = -1.0
+    assert rows[0][3][0] == 0. and rows[0][4] == ema
+    ema = .99 * ema + .01 * 1.                                     # step 1: reward 1 ends the episode
+    assert rows[1][4] == ema and rows[1][3][0] == 0. and rows[1][1][0] == 1. and rows[1][2][0] == 0.
+    assert rows[2][4] == ema
+    ema = .99 * ema + .01 * -1.                                    # step 3: reward -1
+    assert rows[3][4] == ema and rows[3][3][0] == 0. and rows[3][2][0] == 0.
+    assert pool.resets == [] and q.puts == 2
+    assert [tuple(r[0][0]) for r in rows] == [(0, 1), (0, 2), (0, 3), (0, 4)]      # the step's own frames
+    # without pong the same rewards only add up
+    pool, q, rows = _play_host_steps(False, False, 0, 1, script)
+    assert q.puts == 0 and q.v == -1.0 and [r[3][0] for r in rows] == [0., 1., 1., 0.]
+
+
+def test_host_env_step_true_done_resets_and_stores_the_reset_frame():
+    """(b) an env done writes done = 1, calls pool.reset(j) and stores that frame, not the step's; ep_rew enters the EMA"""
+    script = [[(.5, False), (.25, True), (2., False), (0., True)]] * 3
+    pool, q, rows = _play_host_steps(False, False, 0, 3, script)
+    assert [tuple(r[2]) for r in rows] == [(0., 0., 0.), (1., 1., 1.), (0., 0., 0.), (1., 1., 1.)]
+    assert pool.resets == [0, 1, 2, 0, 1, 2]
+    for j in range(3):
+        assert [tuple(r[0][j]) for r in rows] == [(j, 1), (j, -1), (j, 3), (j, -1)]
+        assert [r[1][j] for r in rows] == [.5, .25, 2., 0.]
+        assert [r[3][j] for r in rows] == [.5, 0., 2., 0.]
+    ema = -1.0
+    for _ in range(3):
+        ema = .99 * ema + .01 * .75
+    assert rows[1][4] == ema
+    for _ in range(3):
+        ema = .99 * ema + .01 * 2.
+    assert rows[3][4] == ema and q.puts == 6
+
+
+def test_host_env_step_action_conversion():
+    """(c) continuous actions reach the env as float32 (n,) + shift, discrete ones as int + shift"""
+    script = [[(0., False)] * 4] * 3
+    pool, _, _ = _play_host_steps(False, False, 0, 3, script, shift=2, steps=1)
+    assert pool.actions == [(0, 4), (1, 2), (2, 3)] and all(type(a) is int for _, a in pool.actions)
+    pool, _, _ = _play_host_steps(False, True, 0, 3, script, shift=2, steps=1)
+    for j, (jj, a) in enumerate(pool.actions):
+        assert jj == j and a.dtype == np.float32 and a.shape == (2,)
+        assert a.tolist() == [2 * j + 2., 2 * j + 3.]
+
+
+def test_host_env_step_touches_only_its_rows():
+    """(d) env0 > 0: rows env0..env0+B of every view, those envs alone"""
+    script = [[(1., True)] * 4] * 3
+    pool, q, rows = _play_host_steps(False, False, 1, 1, script)
+    assert {j for j, _ in pool.actions} == {1} and set(pool.resets) == {1}
+    for fr, rew, done, ep, _ in rows:
+        assert (fr[[0, 2]] == 77).all() and (rew[[0, 2]] == 77).all() and (done[[0, 2]] == 77).all()
+        assert tuple(fr[1]) == (1, -1) and rew[1] == 1. and done[1] == 1. and (ep == 0).all()
+    pool, q, rows = _play_host_steps(False, False, 1, 2, script, steps=1)
+    assert [j for j, _ in pool.actions] == [1, 2] and (rows[0][0][0] == 77).all() and (rows[0][2][1:] == 1).all()
+
+
 def test_split_count_rule_for_few_tile_products(monkeypatch):
     """ops.pick_splitk: products of a handful of 128 x 128 tiles over a short K (GRUModel's resize_emb at rollout batch) get
     at most 256 / tiles slabs -- the reduce reads every slab back; big products keep the 512-workgroup target; the
