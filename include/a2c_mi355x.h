@@ -292,7 +292,9 @@ typedef struct {
   /* optional stash of the conv activations of this state (post-ReLU, NCHW): a1 (16, OH1, OW1) and a2
    * (32, OH2, OW2) of env b go to a1_out + b*a1_stride / a2_out + b*a2_stride.  The weights do not change
    * between a rollout and the update that consumes it (training.py:150-165), so Updater.update_model's
-   * forward (updater.py:80) would recompute exactly these tensors: it reads the stash instead.           */
+   * forward (updater.py:80) would recompute exactly these tensors: it reads the stash instead.
+   * The rows are written 16 bytes at a time: A2C_ERR_ARG for a stash when OH1*OW1 is not a multiple of 4, a stride
+   * that is not, or a pointer that is not 16-byte aligned (the same for a1_rows / a2_rows of a2c_a3c_rollout).  */
   float *a1_out; int64_t a1_stride;
   float *a2_out; int64_t a2_stride;
   float *heads_out; int64_t heads_out_stride;   /* optional second copy of [logits | value] (same stash) */

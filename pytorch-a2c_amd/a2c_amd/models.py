@@ -368,6 +368,8 @@ class A3CModel(_HipNet):
         weights, same states: training.py:150-165) reads them instead of recomputing 45 % of its FLOPs."""
         if os.environ.get("A2C_NO_STASH") == "1" or not self._step_supported():
             return None
+        if (self._c1.out_shape[1] * self._c1.out_shape[2]) % 4:
+            return None      # the kernels stash float4 by float4 (A2C_ERR_ARG for a conv1 plane that is no multiple): the update recomputes
         ws = self.ws("train")
         # + the heads [logits | value] of every state: the rollout computed them through the composed matrix
         # Wc = [pi;value].proj_matrx, so the update needs neither the 2592 -> 256 forward GEMM nor the embedding

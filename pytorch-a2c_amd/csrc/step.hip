@@ -79,6 +79,7 @@ struct StepP {
   int OH1, OW1, OH2, OW2, PLANE1, PLANE2, F, F4;
   int row_end[NCH];            // chunk k = input rows [row_end[k-1], row_end[k])
   int tile_end[NCH];           // conv1 16-pixel tiles computable once chunk k is in LDS
+  int w2_tap_major;            // step order of wfrag2 as a2c_conv2d_prep_weights lays it for this conv2 (frag2_src)
   RolloutX x;
 };
 
@@ -170,6 +171,15 @@ __device__ __forceinline__ bf16x8 u8x8_bf16(unsigned int lo, unsigned int hi) {
   return __builtin_bit_cast(bf16x8, r);
 }
 __device__ __forceinline__ unsigned short bf16_bits(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
+
+// conv2's A fragments arrive as a2c_conv2d_prep_weights(kind 0) lays them for THIS layer (conv.hip: prep_fwd_kernel): step
+// = (c4*4 + ky)*4 + kx where the row-run kernel takes the layer (its input width OW1 is a multiple of 4), step = tap*4 + c4
+// elsewhere.  Both kernels below index their LDS copy by (c4, ky, kx): float4 q = (step, channel half, lane quad) of that
+// copy is float4 frag2_src(q) of wfrag2.
+__device__ __forceinline__ int frag2_src(int q, int tap_major) {
+  const int s = q >> 5;
+  return tap_major ? (((((s & 15) << 2) | (s >> 4)) << 5) | (q & 31)) : q;
+}
 
 template <bool OUT, bool U8, bool PERSIST, int HNT = HN>      // HNT: heads kept in registers (n_actions + 1 <= HNT)
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void a3c_step_kernel(StepP p) {
@@ -394,7 +404,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #endif
       if (k == 1 && !SKIP(5)) {
         const float4* __restrict__ wf2v = reinterpret_cast<const float4*>(a.wfrag2);
-        w2a = wf2v[tid]; w2b = wf2v[tid + NT]; w2c = wf2v[tid + 2 * NT]; w2d = wf2v[tid + 3 * NT];
+        const int tm = p.w2_tap_major;
+        w2a = wf2v[frag2_src(tid, tm)]; w2b = wf2v[frag2_src(tid + NT, tm)];
+        w2c = wf2v[frag2_src(tid + 2 * NT, tm)]; w2d = wf2v[frag2_src(tid + 3 * NT, tm)];
       }
       for (int tile = (k ? p.tile_end[k - 1] : 0) + w; tile < p.tile_end[k] && !SKIP(1); tile += NT / 64) {
         const int idx = tile * 16 + j;
@@ -703,7 +715,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const float4* __restrict__ wf2v = reinterpret_cast<const float4*>(a.wfrag2);
     float4* __restrict__ f2 = reinterpret_cast<float4*>(fr2);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) f2[tid + q * NT] = wf2v[tid + q * NT];
+    for (int q = 0; q < 4; ++q) f2[tid + q * NT] = wf2v[frag2_src(tid + q * NT, p.w2_tap_major)];
   }
   if (tid < 32) red[HN + tid] = a.bias2[tid];
   if (tid == 0) reinterpret_cast<unsigned int*>(red)[HN + 37] = 0u;        // "the env worker timed out" flag of the polls below
@@ -1316,6 +1328,10 @@ static bool step_shapes(int C, int H, int W, int n_actions, StepP& p) {
   p.OH1 = (H - 8) / 4 + 1; p.OW1 = (W - 8) / 4 + 1;
   if (p.OH1 < 4 || p.OW1 < 4 || p.OW1 % 2) return false;
   p.OH2 = (p.OH1 - 4) / 2 + 1; p.OW2 = (p.OW1 - 4) / 2 + 1;
+  // conv.hip's a2c_conv2d_prep_weights(kind 0) keeps the (c4, ky, kx) order for run_layout() || run3_layout() layers: for this
+  // conv2 (16 -> 32, 4x4 / stride 2, no padding; run3 is 3x3 only) that is "input rows of a multiple of 4 floats".  Restated
+  // here, not shared; tests/test_gpu_step_shapes.py holds the prepared fragments against it on every shape of its table.
+  p.w2_tap_major = p.OW1 % 4 != 0;
   p.PLANE1 = plane_pad(H * W, 0);
   p.PLANE2 = plane_pad(p.OH1 * p.OW1, 32);
   p.F = 32 * p.OH2 * p.OW2;
