@@ -21,7 +21,7 @@ from collections import deque
 import numpy as np
 import torch
 
-from . import breakout, models, point, pong, preprocessing, snake, worlds
+from . import breakout, cartpole, models, point, pong, preprocessing, snake, worlds
 from .runner import DeviceStatsRunner, HostEnvPool, Runner, SequentialEnvironment, StatsRunner
 from .updater import Updater
 from .utils import cuda_if, deque_maxmin, try_key
@@ -57,9 +57,13 @@ _WORLDS = {
     "Breakout": (breakout, "breakout_prep", False, False, ("lives", "max_episode_steps"), True, breakout.RULE_KEYS),
     # the continuous-control world: vector observations, two float actions, Gaussian nets only
     "Point": (point, "null_prep", False, False, ("targets_to_win", "max_episode_steps"), True, point.RULE_KEYS),
+    # the pole on a cart: vector observations, two int actions, the discrete FC nets only
+    "CartPole": (cartpole, "null_prep", False, False, ("max_episode_steps",), True, cartpole.RULE_KEYS),
 }
 # the nets with a Gaussian head (models.py): what a family whose device pool has ``float_actions`` can be trained with
 _GAUSS_MODELS = ("FCModel", "GRUFCModel")
+# the nets that take a vector observation: with a softmax head, what the CartPole worlds can be trained with
+_FC_MODELS = _GAUSS_MODELS
 # the keys of section 6i that shape what a policy is TRAINED on, not the game: evaluation worlds do not get them
 _TRAINING_ONLY = ("episodic_life", "clip_rewards")
 
@@ -114,7 +118,14 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     ``model`` FCModel / GRUFCModel only (anything else is a ValueError before anything is allocated).  ``DevicePointPool``
     reads the float action rows on the device; "Point-host" steps ``PointEnv``s behind ``env_pool`` "serial" (the default)
     or "process_f32"; evaluation on host ``PointEnv``s.
-    ``hyps["eval_pool"] = "device"`` (the four ``*-device`` env types, no ``eval_env``) evaluates on the device instead: a
+    ``env_type`` "CartPole-device" / "CartPole-host" (a2c_amd/cartpole.py; keys ``max_episode_steps``,
+    ``frame_skip`` / ``frame_skip_max`` / ``sticky_num`` / ``sticky_den`` as on the Pong worlds) are the pole on a cart in this
+    project's integer arithmetic ("CartPole-v1" stays gym's): (1, 4) observations with ``prep_fxn="null_prep"``, 2 actions,
+    ``action_shift`` 0 unless given, real dones only, for ``model`` FCModel / GRUFCModel with ``is_discrete=True`` only
+    (anything else is a ValueError before anything is allocated).  ``DeviceCartPolePool`` reads the sampler's int64 actions
+    on the device; "CartPole-host" steps ``CartPoleEnv``s behind the usual pools (the process pool carries their fp32
+    frames); evaluation on host ``CartPoleEnv``s.
+    ``hyps["eval_pool"] = "device"`` (the five ``*-device`` env types, no ``eval_env``) evaluates on the device instead: a
     second pool of ``n_test_eps`` worlds behind a ``DeviceStatsRunner`` (keys ``eval_chunk``, ``max_eval_steps``); the default
     ``"host"`` is the host twins.
     Returns the best evaluation reward."""
@@ -123,9 +134,10 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     if eval_pool not in ("host", "device"):
         raise ValueError(f"a2c_amd: hyps['eval_pool'] is 'host' or 'device', not {eval_pool!r}")
     if eval_pool == "device" and (eval_env is not None or env_fn is not None or hyps.get("env_type") not in (
-            "Snake-device", "Pong-device", "Breakout-device", "Point-device")):
+            "Snake-device", "Pong-device", "Breakout-device", "Point-device", "CartPole-device")):
         raise ValueError("a2c_amd: hyps['eval_pool'] = 'device' evaluates the device worlds (env_type 'Snake-device', "
-                         "'Pong-device', 'Breakout-device' or 'Point-device') and takes no eval_env / env_fn")
+                         "'Pong-device', 'Breakout-device', 'Point-device' or 'CartPole-device') and takes no eval_env / "
+                         "env_fn")
     if env_fn is None and _world_family(hyps.get("env_type")) == "Snake":
         if worlds.repeat_from_hyps(hyps, "Snake")[:2] != (1, 0):
             raise ValueError("a2c_amd: frame_skip / sticky_num are keys of the Pong and Breakout worlds: the Snake worlds "
@@ -144,6 +156,12 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
             if hyps["env_type"] == "Point-host" and try_key(hyps, "env_pool", None) not in (None, "serial", "process_f32"):
                 raise ValueError("a2c_amd: env_type='Point-host' steps behind env_pool='serial' (the default) or 'process_f32' "
                                  "(the int process pool and the thread pool carry int32 actions)")
+        if family == "CartPole":
+            # vector observations and two int actions: the FC nets with their softmax head
+            if hyps.get("model") not in _FC_MODELS or not try_key(hyps, "is_discrete", True):
+                raise ValueError(f"a2c_amd: the CartPole worlds take one of two int actions on (1, 4) observations: model "
+                                 f"{' / '.join(_FC_MODELS)} with is_discrete=True, not {hyps.get('model')!r}"
+                                 + ("" if try_key(hyps, "is_discrete", True) else " with is_discrete=False"))
     if hyps["n_rollouts"] is None:
         hyps["n_rollouts"] = hyps["n_envs"]
     hyps["main_path"] = try_key(hyps, "main_path", "./")
@@ -202,8 +220,8 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                                   n_workers=try_key(hyps, "n_env_workers", None), pong=pong_done,
                                   action_shift=try_key(hyps, "action_shift", 0), frame_bits=bits,
                                   action_dim=n_act if cont_world else None,
-                                  # (null_prep puts an axis in front of the twin's (1, 8) row: the states are the device pool's)
-                                  frame_shape=world_shape if cont_world else None)
+                                  # (null_prep puts an axis in front of a twin's (1, L) row: the states are the device pool's)
+                                  frame_shape=world_shape if len(world_shape) == 2 else None)
     elif env_fn is None:
         hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
         probe = eval_env or SequentialEnvironment(**hyps)             # the probe for shapes (training.py:60-65)
