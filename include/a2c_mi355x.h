@@ -1144,6 +1144,46 @@ int a2c_cartpole_step(int32_t *state, const int64_t *actions, int64_t act_stride
                       float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_rules *rules,
                       const a2c_world_post *post, a2c_stream_t stream);
 
+/* ------------------------------------------------------------------ Pendulum worlds in device memory (csrc/pendulum.hip)
+ * The textbook continuous-control world of the Gaussian nets (FCModel / GRUFCModel with is_discrete = False): the pendulum
+ * swing-up, the textbook equations with gym's constants and Euler order in this project's own integer arithmetic (DESIGN.md
+ * section 6l; the host twin a2c_amd/pendulum.py produces the same integers; parity with gym is not claimed).  The state of
+ * one env is 12 int32 words: theta in [-pi, pi) and theta_dot in [-8, 8] in Q20 (unit 2^-20), 2 spare, then draw counter,
+ * game-frame counter, episode-frame counter, reward since the last done IN UNITS OF 2^-8, the quantised action of the previous
+ * game frame (sticky actions; 0 without them), 3 spare.  The action of env e is ONE float, actions[e * act_ld]:
+ * x = fp32(a + action_shift), q = 0 for a NaN, else rint(clamp(x, -2, 2) * 32) with ties to even, the torque u = q / 32.
+ * One game frame: cost = theta^2 + 0.1 theta_dot^2 + 0.001 u^2 from the values before the frame;
+ * theta_dot = clamp(theta_dot + 0.75 sin theta + 0.15 u, +-8); theta += 0.05 theta_dot (the new one), wrapped once into
+ * [-pi, pi); every product floored by >> 20, sin / cos nested-ratio polynomials, no division.  The frame's reward is the
+ * int -(cost >> 12) in units of 2^-8 (-4166 .. 0); rew[] and the post bookkeeping get the summed ints times 2^-8 as fp32,
+ * exact.  The episode ends after max_episode_steps frames and in no other way (the world restarts: two draws d give
+ * theta = d mod 2 pi - pi and theta_dot = d mod (2^21 + 1) - 2^20).  Draw i of world env_id0 + e is
+ * hash32(seed, env_id, i).  done == reset: real dones only.  An observation is (cos theta, sin theta, theta_dot) times
+ * 2^-20 and a 0, exact in fp32.  World parameter: 1 <= max_episode_steps <= 2^16.  One lane plays one env, 64 envs per
+ * wavefront.
+ * a2c_pendulum_state_bytes: bytes of ONE env's state.                                                                    */
+size_t a2c_pendulum_state_bytes(void);
+/* starts B worlds (counters to 0, then the two draws): state (B rows of 12 words) and obs (B rows of 4 floats, obs_ld
+ * floats apart).  A2C_ERR_ARG without a launch: B <= 0, env_id0 < 0, max_episode_steps out of bounds, a NULL state / obs,
+ * state or obs not 16-byte aligned, obs_ld < 4 or not a multiple of 4.                                                    */
+int a2c_pendulum_reset(int32_t *state, int B, int env_id0, uint32_t seed, int max_episode_steps, float *obs, int64_t obs_ld,
+                       a2c_stream_t stream);
+/* one AGENT step of B worlds by the a2c_world_rules block (NULL: {1, 1, 0, 1, 0, 0}, one game frame), as a2c_point_step:
+ * frame_skip .. frame_skip_max game frames with the action of env e and sticky actions, draws in the order of
+ * a2c_<world>_step_rules; rew is the summed reward, an episode end drops the remaining frames.  ep_count counts the closed
+ * steps; ep_rew_sum gets, per closed step, the reward since the last done FLOORED TO WHOLE reward units (the int >> 8), so
+ * the sum of a pool whose envs all close in one step stays inside an int32: less than one unit per episode below the exact sum.
+ * post == NULL: the plain step; obs is required.  post != NULL: the step + the bookkeeping + the hidden-row reset + the
+ * frame stack of the a2c_world_post contract above (HW = 4) in one launch, bit-identical to the plain step followed by
+ * a2c_rollout_post (h == NULL) or by a2c_rollout_record + a2c_frame_stack_push (h != NULL); obs may be NULL then.
+ * A2C_ERR_ARG without a launch: what a2c_pendulum_reset rejects (a NULL obs excepted with post), act_ld < 1, a NULL
+ * actions / rew / done / reset, actions not 4-byte aligned, a rules block a2c_pong_step_rules rejects (either flag set
+ * included), a post block a2c_<world>_step_post rejects.                                                                  */
+int a2c_pendulum_step(int32_t *state, const float *actions, int64_t act_ld, float action_shift, int B, int env_id0,
+                      uint32_t seed, int max_episode_steps, float *obs, int64_t obs_ld, float *rew, float *done,
+                      float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_rules *rules,
+                      const a2c_world_post *post, a2c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,9 @@ SIGNATURES = {
     "a2c_cartpole_state_bytes": (c_size_t, []),
     "a2c_cartpole_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, P, c_int64, P]),
     "a2c_cartpole_step": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, P, c_int64, P, P, P, P, P, PU, PW, P]),
+    "a2c_pendulum_state_bytes": (c_size_t, []),
+    "a2c_pendulum_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, P, c_int64, P]),
+    "a2c_pendulum_step": (c_int, [P, P, c_int64, c_float, c_int, c_int, c_uint32, c_int, P, c_int64, P, P, P, P, P, PU, PW, P]),
 }
 
 _lib = None

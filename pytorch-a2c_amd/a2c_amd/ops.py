@@ -1480,3 +1480,27 @@ def cartpole_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed
     check(lib().a2c_cartpole_step(_p(state), actions_ptr, act_stride, int(action_shift), B, env_id0, seed, max_episode_steps,
                                   _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum),
                                   _post_ref(rules), _post_ref(post), _st(st)), "a2c_cartpole_step")
+
+
+# ---------------------------------------------------------------- Pendulum worlds in device memory (csrc/pendulum.hip)
+def pendulum_state_bytes():
+    """bytes of one env's state"""
+    return int(lib().a2c_pendulum_state_bytes())
+
+
+def pendulum_reset(state, B, env_id0, seed, max_episode_steps, obs, obs_ld, st=None):
+    _chk_world(state, obs)
+    check(lib().a2c_pendulum_reset(_p(state), B, env_id0, seed, max_episode_steps, _p(obs), obs_ld, _st(st)),
+          "a2c_pendulum_reset")
+
+
+def pendulum_step(state, actions_ptr, act_ld, action_shift, B, env_id0, seed, max_episode_steps, obs, obs_ld, rew, done,
+                  reset, rules=None, post=None, ep_count=None, ep_rew_sum=None, st=None):
+    """actions_ptr: address of env 0's ONE float32 action, ``act_ld`` floats between envs (>= 1); ``action_shift`` a float;
+    ``rules``: a ``world_rules`` block or None (one game frame); ``post``: a ``world_post`` block -- the step + the bookkeeping
+    of the env step + the hidden-row reset + frame_stack_push in one launch (``obs`` may then be None) -- or None.
+    ``ep_rew_sum`` gets whole reward units: every closed episode's sum floored"""
+    _chk_world(state, obs, rew, done, reset, ep_count, ep_rew_sum)
+    check(lib().a2c_pendulum_step(_p(state), actions_ptr, act_ld, float(action_shift), B, env_id0, seed, max_episode_steps,
+                                  _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum),
+                                  _post_ref(rules), _post_ref(post), _st(st)), "a2c_pendulum_step")

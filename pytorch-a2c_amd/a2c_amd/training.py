@@ -21,7 +21,7 @@ from collections import deque
 import numpy as np
 import torch
 
-from . import breakout, cartpole, models, point, pong, preprocessing, snake, worlds
+from . import breakout, cartpole, models, pendulum, point, pong, preprocessing, snake, worlds
 from .runner import DeviceStatsRunner, HostEnvPool, Runner, SequentialEnvironment, StatsRunner
 from .updater import Updater
 from .utils import cuda_if, deque_maxmin, try_key
@@ -59,6 +59,8 @@ _WORLDS = {
     "Point": (point, "null_prep", False, False, ("targets_to_win", "max_episode_steps"), True, point.RULE_KEYS),
     # the pole on a cart: vector observations, two int actions, the discrete FC nets only
     "CartPole": (cartpole, "null_prep", False, False, ("max_episode_steps",), True, cartpole.RULE_KEYS),
+    # the pendulum swing-up: vector observations, one float action, Gaussian nets only
+    "Pendulum": (pendulum, "null_prep", False, False, ("max_episode_steps",), True, pendulum.RULE_KEYS),
 }
 # the nets with a Gaussian head (models.py): what a family whose device pool has ``float_actions`` can be trained with
 _GAUSS_MODELS = ("FCModel", "GRUFCModel")
@@ -66,6 +68,11 @@ _GAUSS_MODELS = ("FCModel", "GRUFCModel")
 _FC_MODELS = _GAUSS_MODELS
 # the keys of section 6i that shape what a policy is TRAINED on, not the game: evaluation worlds do not get them
 _TRAINING_ONLY = ("episodic_life", "clip_rewards")
+
+
+def _float_family(family):
+    """does the family's device pool read float action rows (``float_actions``: Point, Pendulum)?"""
+    return bool(getattr(getattr(_WORLDS[family][0], "Device" + family + "Pool"), "float_actions", False))
 
 
 def _world_family(env_type):
@@ -125,7 +132,13 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     (anything else is a ValueError before anything is allocated).  ``DeviceCartPolePool`` reads the sampler's int64 actions
     on the device; "CartPole-host" steps ``CartPoleEnv``s behind the usual pools (the process pool carries their fp32
     frames); evaluation on host ``CartPoleEnv``s.
-    ``hyps["eval_pool"] = "device"`` (the five ``*-device`` env types, no ``eval_env``) evaluates on the device instead: a
+    ``env_type`` "Pendulum-device" / "Pendulum-host" (a2c_amd/pendulum.py; keys ``max_episode_steps``
+    (default 200, at most 2^16), ``frame_skip`` / ``frame_skip_max`` / ``sticky_num`` / ``sticky_den`` as on the Pong worlds) are
+    the pendulum swing-up in this project's integer arithmetic ("Pendulum-v1" stays gym's): (1, 4) observations with
+    ``prep_fxn="null_prep"``, ``is_discrete=False``, 1 float action (the torque, clamped to +-2), fractional rewards (multiples
+    of 2^-8), only the step cap ends an episode, and the same refusals and pools as the Point worlds: ``model`` FCModel /
+    GRUFCModel only, "Pendulum-host" behind ``env_pool`` "serial" or "process_f32"; evaluation on host ``PendulumEnv``s.
+    ``hyps["eval_pool"] = "device"`` (the six ``*-device`` env types, no ``eval_env``) evaluates on the device instead: a
     second pool of ``n_test_eps`` worlds behind a ``DeviceStatsRunner`` (keys ``eval_chunk``, ``max_eval_steps``); the default
     ``"host"`` is the host twins.
     Returns the best evaluation reward."""
@@ -134,10 +147,10 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     if eval_pool not in ("host", "device"):
         raise ValueError(f"a2c_amd: hyps['eval_pool'] is 'host' or 'device', not {eval_pool!r}")
     if eval_pool == "device" and (eval_env is not None or env_fn is not None or hyps.get("env_type") not in (
-            "Snake-device", "Pong-device", "Breakout-device", "Point-device", "CartPole-device")):
+            "Snake-device", "Pong-device", "Breakout-device", "Point-device", "CartPole-device", "Pendulum-device")):
         raise ValueError("a2c_amd: hyps['eval_pool'] = 'device' evaluates the device worlds (env_type 'Snake-device', "
-                         "'Pong-device', 'Breakout-device', 'Point-device' or 'CartPole-device') and takes no eval_env / "
-                         "env_fn")
+                         "'Pong-device', 'Breakout-device', 'Point-device', 'CartPole-device' or 'Pendulum-device') and takes "
+                         "no eval_env / env_fn")
     if env_fn is None and _world_family(hyps.get("env_type")) == "Snake":
         if worlds.repeat_from_hyps(hyps, "Snake")[:2] != (1, 0):
             raise ValueError("a2c_amd: frame_skip / sticky_num are keys of the Pong and Breakout worlds: the Snake worlds "
@@ -147,15 +160,16 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
         # family does not take them or they are out of bounds
         family = _world_family(hyps["env_type"])
         rules = worlds.rules_from_hyps(hyps, family, _WORLDS[family][6])
-        if family == "Point":
+        if _float_family(family):
             # float actions: the nets with a Gaussian head, never as discrete ones; and no int32 process pool
+            n = _WORLDS[family][0].ACTION_SIZE
             if hyps.get("model") not in _GAUSS_MODELS or try_key(hyps, "is_discrete", False):
-                raise ValueError(f"a2c_amd: the Point worlds take two float actions: model {' / '.join(_GAUSS_MODELS)} with "
-                                 f"is_discrete=False, not {hyps.get('model')!r}"
+                raise ValueError(f"a2c_amd: the {family} worlds take {n} float action{'s' if n > 1 else ''}: model "
+                                 f"{' / '.join(_GAUSS_MODELS)} with is_discrete=False, not {hyps.get('model')!r}"
                                  + (" with is_discrete=True" if try_key(hyps, "is_discrete", False) else ""))
-            if hyps["env_type"] == "Point-host" and try_key(hyps, "env_pool", None) not in (None, "serial", "process_f32"):
-                raise ValueError("a2c_amd: env_type='Point-host' steps behind env_pool='serial' (the default) or 'process_f32' "
-                                 "(the int process pool and the thread pool carry int32 actions)")
+            if hyps["env_type"] == family + "-host" and try_key(hyps, "env_pool", None) not in (None, "serial", "process_f32"):
+                raise ValueError(f"a2c_amd: env_type='{family}-host' steps behind env_pool='serial' (the default) or "
+                                 "'process_f32' (the int process pool and the thread pool carry int32 actions)")
         if family == "CartPole":
             # vector observations and two int actions: the FC nets with their softmax head
             if hyps.get("model") not in _FC_MODELS or not try_key(hyps, "is_discrete", True):
@@ -191,7 +205,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                                  "the process env pool (the device worlds write prepped frames themselves)")
         hyps["prep_fxn"] = "null_prep" if raw else prep_name
         prep = hyps["preprocessor"] = getattr(preprocessing, hyps["prep_fxn"])
-        cont_world = bool(getattr(getattr(mod, "Device" + family + "Pool"), "float_actions", False))
+        cont_world = _float_family(family)
         hyps["is_discrete"], n_act = not cont_world, (mod.ACTION_SIZE if cont_world else mod.N_ACTIONS)
         if cont_world:      # a Box: in this process unless env_pool='process_f32' (as below for every continuous env)
             serial = try_key(hyps, "env_pool", None) != "process_f32"
