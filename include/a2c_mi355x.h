@@ -1184,6 +1184,50 @@ int a2c_pendulum_step(int32_t *state, const float *actions, int64_t act_ld, floa
                       float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_rules *rules,
                       const a2c_world_post *post, a2c_stream_t stream);
 
+/* ------------------------------------------------------------------ running observation / reward normalisation (csrc/vecnorm.hip)
+ * What baselines' VecNormalize does between a vector world and the agent (host twin
+ * a2c_amd/vecnorm.py): running mean and variance of the observations and of the discounted return, observations centred and
+ * scaled, rewards divided by the return's standard deviation, both clipped.  The statistics live in device memory and advance
+ * at every launch, so a captured launch normalises new steps at each replay, as the worlds' counters do.
+ * The state block is 4 + 2 L + B_pool doubles: obs count, obs mean[L], obs var[L], return count, return mean, return var,
+ * ret[B_pool] (the per-env discounted return accumulators).
+ * a2c_vecnorm_state_bytes: bytes of the block, 0 for L outside 1..64 or B_pool < 1.
+ * a2c_vecnorm_init: counts = 1e-4, means = 0, vars = 1, ret = 0 (what baselines' RunningMeanStd starts from).  A2C_ERR_ARG
+ * without a launch: a NULL block, L outside 1..64, B_pool < 1.
+ * a2c_vecnorm_step: one env step of the B envs env0 .. env0+B-1 of a launch, in this order:
+ *   1. observations (out != NULL): x[b][j] = out[b * out_stride + (C-1) * L + j], the NEW plane of env b's next state.  With
+ *      update != 0 the batch is folded into the running moments, per feature: bm = sum x / B, bv = sum (x - bm)^2 / B (two
+ *      passes), delta = bm - mean, tot = count + B, mean += delta * B / tot,
+ *      var = (var * count + bv * B + delta * delta * count * B / tot) / tot, count = tot (every product and quotient left to
+ *      right).  Then x = fp32(clamp((x - mean) / sqrt(var + eps), -clip_obs, clip_obs)) in place, by the UPDATED moments.  The
+ *      older planes are not touched: normalise first, then stack.
+ *   2. rewards (rewards != NULL): e = (slot0 + b) * T + t, r = rewards[e]; ret[env0 + b] = ret[env0 + b] * gamma + r, the B
+ *      values of ret folded into the return moments by the same rule; rewards[e] = fp32(clamp(r / sqrt(ret_var + eps),
+ *      -clip_rew, clip_rew)); then ret[env0 + b] = 0 where dones[e] != 0.
+ *   3. update == 0 (evaluation): observations by the moments as they stand, nothing in the block is written; the reward
+ *      part must be absent.
+ * All arithmetic is fp64 (never contracted), one rounding to fp32 at the store.  ONE workgroup of 256 lanes: lane i sums
+ * envs i, i + 256, ... in order, then a halving tree over the lanes (strides 128 .. 1); the same tree for both passes and every
+ * feature.  No atomics; the result does not depend on scheduling.
+ * A2C_ERR_ARG without a launch: a NULL block or args, B < 1, L outside 1..64, env0 < 0, env0 + B > B_pool, eps <= 0, a clip
+ * <= 0, both parts absent; with out: C < 1, out_stride < C * L; with rewards: a NULL dones, T < 1, t outside 0 .. T-1,
+ * slot0 < 0, update == 0.                                                                                                */
+typedef struct {
+  int32_t B, env0, B_pool;     /* the launch's envs inside the pool the block was made for                          */
+  int32_t L, C;                /* floats of a plane, planes of a state                                               */
+  int32_t update;              /* 0: frozen (evaluation)                                                             */
+  float *out;                  /* next-state rows, out_stride floats apart, or NULL: no observation part             */
+  int64_t out_stride;
+  float *rewards;              /* the rollout buffer's rows, indexed (slot0 + b) * T + t, or NULL: no reward part    */
+  const float *dones;
+  int64_t T, t, slot0;
+  double gamma, eps, clip_obs, clip_rew;
+} a2c_vecnorm_args;
+
+size_t a2c_vecnorm_state_bytes(int L, int B_pool);
+int a2c_vecnorm_init(double *block, int L, int B_pool, a2c_stream_t stream);
+int a2c_vecnorm_step(double *block, const a2c_vecnorm_args *args, a2c_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

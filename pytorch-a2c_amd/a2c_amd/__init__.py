@@ -13,12 +13,13 @@ Sub-modules and names are imported lazily: the env worker processes of the host 
 import importlib
 
 _SUBMODULES = ("_lib", "ops", "utils", "models", "optim", "parallel", "preprocessing", "runner", "updater", "training",
-               "engine", "hostpool", "hostpool_worker", "synthetic")
+               "engine", "hostpool", "hostpool_worker", "synthetic", "vecnorm")
 _NAMES = {
     "A3CModel": "models", "ConvModel": "models", "FCModel": "models", "GRU": "models", "GRUFCModel": "models",
     "GRUModel": "models",
     "Runner": "runner", "StatsRunner": "runner", "DeviceStatsRunner": "runner", "SequentialEnvironment": "runner", "HostEnvPool": "runner",
     "ProcessEnvPool": "hostpool",
+    "RunningNorm": "vecnorm", "DeviceVecNorm": "vecnorm",
     "Updater": "updater",
     "discount": "utils", "sample_action": "utils", "next_state": "utils", "cuda_if": "utils", "try_key": "utils",
     "deque_maxmin": "utils",

@@ -66,10 +66,18 @@ class WorldRules(Structure):
                 ("episodic_life", c_int32), ("clip_rewards", c_int32)]
 
 
+class VecNormArgs(Structure):
+    """a2c_vecnorm_args"""
+    _fields_ = [("B", c_int32), ("env0", c_int32), ("B_pool", c_int32), ("L", c_int32), ("C", c_int32), ("update", c_int32),
+                ("out", P), ("out_stride", c_int64), ("rewards", P), ("dones", P), ("T", c_int64), ("t", c_int64),
+                ("slot0", c_int64), ("gamma", c_double), ("eps", c_double), ("clip_obs", c_double), ("clip_rew", c_double)]
+
+
 PS = POINTER(A3CStepArgs)
 PR = POINTER(A3CRolloutArgs)
 PW = POINTER(WorldPost)
 PU = POINTER(WorldRules)
+PV = POINTER(VecNormArgs)
 
 # name -> (restype, argtypes); one entry per prototype in include/a2c_mi355x.h
 SIGNATURES = {
@@ -244,6 +252,9 @@ SIGNATURES = {
     "a2c_pendulum_state_bytes": (c_size_t, []),
     "a2c_pendulum_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, P, c_int64, P]),
     "a2c_pendulum_step": (c_int, [P, P, c_int64, c_float, c_int, c_int, c_uint32, c_int, P, c_int64, P, P, P, P, P, PU, PW, P]),
+    "a2c_vecnorm_state_bytes": (c_size_t, [c_int, c_int]),
+    "a2c_vecnorm_init": (c_int, [P, c_int, c_int, P]),
+    "a2c_vecnorm_step": (c_int, [P, PV, P]),
 }
 
 _lib = None

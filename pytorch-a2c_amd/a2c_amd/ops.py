@@ -1504,3 +1504,34 @@ def pendulum_step(state, actions_ptr, act_ld, action_shift, B, env_id0, seed, ma
     check(lib().a2c_pendulum_step(_p(state), actions_ptr, act_ld, float(action_shift), B, env_id0, seed, max_episode_steps,
                                   _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum),
                                   _post_ref(rules), _post_ref(post), _st(st)), "a2c_pendulum_step")
+
+
+# ---------------------------------------------------------------- running normalisation (csrc/vecnorm.hip)
+def vecnorm_state_doubles(L, B_pool):
+    """doubles of the state block of a2c_vecnorm_step; raises for an L outside 1..64 or an empty pool"""
+    n = int(lib().a2c_vecnorm_state_bytes(L, B_pool))
+    if n == 0:
+        raise ValueError(f"a2c_vecnorm_state_bytes: unsupported L={L}, B_pool={B_pool} (1 <= L <= 64, B_pool >= 1)")
+    return n // 8
+
+
+def vecnorm_init(block, L, B_pool, st=None):
+    """counts = 1e-4, means = 0, vars = 1, ret = 0"""
+    _chk(block, "block", torch.float64)
+    check(lib().a2c_vecnorm_init(_p(block), L, B_pool, _st(st)), "a2c_vecnorm_init")
+
+
+def vecnorm_args(B, env0, B_pool, L, C=1, update=True, out_ptr=0, out_stride=0, rewards=None, dones=None, T=1, t=0, slot0=0,
+                 gamma=0.99, eps=1e-8, clip_obs=10.0, clip_rew=10.0):
+    """the a2c_vecnorm_args block: ``out_ptr`` the address of the next-state rows (0: no observation part), ``rewards`` /
+    ``dones`` the rollout buffer's rows (None: no reward part)"""
+    _chk(rewards, "rewards"); _chk(dones, "dones")
+    return _lib.VecNormArgs(B=B, env0=env0, B_pool=B_pool, L=L, C=C, update=int(bool(update)), out=out_ptr,
+                            out_stride=out_stride, rewards=_p(rewards), dones=_p(dones), T=T, t=t, slot0=slot0,
+                            gamma=float(gamma), eps=float(eps), clip_obs=float(clip_obs), clip_rew=float(clip_rew))
+
+
+def vecnorm_step(block, args, st=None):
+    """one env step of running normalisation: ``args`` is a ``vecnorm_args`` block"""
+    _chk(block, "block", torch.float64)
+    check(lib().a2c_vecnorm_step(_p(block), _post_ref(args), _st(st)), "a2c_vecnorm_step")

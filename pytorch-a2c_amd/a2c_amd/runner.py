@@ -243,8 +243,16 @@ class Runner:
     training.py:94-101); ``actions`` may stay a host LongTensor like the reference's."""
 
     def __init__(self, datas, hyps, gate_q, stop_q, rew_q, env_pool=None, uniform_fn=None, ingest=None, normal_fn=None,
-                 stash=True, bootstrap=True):
+                 stash=True, bootstrap=True, frozen_norm=None, ranks=None):
         self.hyps, self.datas = hyps, datas
+        # running normalisation (hyps norm_obs / norm_rewards; DESIGN.md section 6m): the DeviceVecNorm block this Runner owns
+        # and advances behind every step's post launch, made in start().  frozen_norm: an evaluation's Runner
+        # (DeviceStatsRunner) normalises its observations by the TRAINING Runner's block instead, and writes nothing to it
+        self.vecnorm, self._norm, self._norm_frozen = frozen_norm, None, frozen_norm is not None
+        self.norm_state = None                # a RunningNorm / its state_dict to start the block from (train(): resume)
+        # ranks: ``Shard.world`` of a sharded run (normalisation is refused above one rank: the ranks' moments would drift
+        # apart); None: the initialised process group's size, 1 without one
+        self.ranks = ranks
         # an evaluation's Runner (DeviceStatsRunner) plays a net between a training rollout and its update: stash=False leaves
         # what that rollout stashed in the net for the update alone; bootstrap=False leaves the last step's rewards / dones
         # rows as the env returned them (no runner.py:236-245) -- device pools with ``device_step_post`` only
@@ -317,6 +325,17 @@ class Runner:
         self.proc_pool = hasattr(pool, "post_actions")
         if not self.bootstrap and not hasattr(pool, "device_step_post"):
             raise ValueError("a2c_amd.Runner: bootstrap=False needs a device env pool with device_step_post")
+        from . import vecnorm as vn
+        if self._norm_frozen:
+            self._norm = dict(obs=True, rewards=False)
+        else:
+            vn.check_runner(hyps, pool, net, getattr(net, "_step_supported", lambda: False)(), ranks=self.ranks)
+            self._norm = vn.norm_settings(hyps)
+            if self._norm is not None:
+                self.vecnorm = vn.DeviceVecNorm(fshape[1], B, hyps["gamma"], eps=self._norm["eps"],
+                                                clip_obs=self._norm["clip_obs"], clip_rew=self._norm["clip_rew"], device=dev)
+                if self.norm_state is not None:
+                    self.vecnorm.load(self.norm_state)
         # continuous nets (is_discrete=False): actions are float rows of n, sampled by a2c_gauss_head
         self.cont = not getattr(net, "is_discrete", True)
         self.n_act = int(net.output_space)
@@ -395,6 +414,9 @@ class Runner:
                                  B, C, self.HW)
         else:
             pool.start(self)
+            if self._norm is not None and self._norm["obs"]:      # the first observation, behind its frame_stack_push
+                self.vecnorm.launch(B, 0, out_ptr=self.bookmark.data_ptr(), out_stride=self.S, C=C,
+                                    update=not self._norm_frozen)
         for p in net.parameters():
             p.requires_grad = False
         self._ready = True
@@ -688,6 +710,7 @@ class Runner:
             fr, rew, done, reset = self._env_step(c, a_ptr, a_stride, t)
             self._post_step(c, t, fr, rew, done, reset, vals.data_ptr(), vals.stride(0),
                             os.environ.get("A2C_NO_POST_FUSE") != "1", st)
+            self._norm_step(c, t, st)
         if self.bootstrap:
             self._bootstrap(c, st)
 
@@ -712,6 +735,18 @@ class Runner:
             ops.frame_stack_push_u8(fr.ptr8, fr.stride, reset, c.sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
         else:
             ops.frame_stack_push(_Ptr(fr.ptr32), reset, c.sp(t), T * S, nxt_ptr, nxt_stride, B, C, HW, st)
+
+    def _norm_step(self, c, t, st):
+        """running normalisation of env step t, behind its post launch: the new plane of the next state
+        and / or row t of the slots' rewards, ONE a2c_vecnorm_step; nothing without the keys.  Only enqueues"""
+        n = self._norm
+        if n is None:
+            return
+        D = self.datas
+        nxt_ptr, nxt_stride = c.nxt(t)
+        self.vecnorm.launch(c.B, c.env0, out_ptr=nxt_ptr if n["obs"] else 0, out_stride=nxt_stride, C=self.C,
+                            rewards=D["rewards"] if n["rewards"] else None, dones=D["dones"] if n["rewards"] else None,
+                            T=c.T, t=t, slot0=c.slot0, update=not self._norm_frozen, st=st)
 
     def _bootstrap(self, c, st):
         """bootstrap (runner.py:236-245): the value of the state after the last step closes the slot's deltas"""
@@ -791,6 +826,7 @@ class Runner:
                                   c.pong, c.sp(t), T * S, nxt_ptr, nxt_stride, self.C,
                                   done_eff=None if h is None else c.done_eff, h=h)
             pool.device_step_post(t, env0, B, (a_ptr, a_stride), post)
+            self._norm_step(c, t, st)
         if self.bootstrap:
             self._bootstrap(c, st)
 
@@ -1259,8 +1295,14 @@ class StatsRunner:
     estimator over the same number of episodes.  ``StatsRunner(hyps, env=one_env)`` keeps the reference's serial
     loop (same episodes in the same order as the reference) for callers that own a single env object."""
 
-    def __init__(self, hyps, env=None, envs=None, uniform_fn=None, normal_fn=None):
+    def __init__(self, hyps, env=None, envs=None, uniform_fn=None, normal_fn=None, norm=None):
         self.hyps = hyps
+        # norm: the training Runner's DeviceVecNorm (or a callable that returns it) under hyps norm_obs: every observation is
+        # normalised by its moments as they stand when the evaluation begins (one snapshot() per rollout), frozen
+        self.norm = norm
+        if bool(try_key(hyps, "norm_obs", False)) and (norm is None or (env is not None and envs is None)):
+            raise ValueError("norm_obs: StatsRunner normalises the observations of lock-step host twins (envs=...) by the "
+                             "training Runner's block: pass norm=runner.vecnorm")
         self.n_episodes = try_key(hyps, "n_test_eps", 15)
         self.uniform_fn = uniform_fn              # (t, E) -> (E,) device uniforms; default torch.rand
         self.normal_fn = normal_fn                # continuous nets: (t, E, 0) -> (E, n) device N(0,1); default torch.randn
@@ -1288,7 +1330,12 @@ class StatsRunner:
         net._refresh(st)
         C = int(hyps["n_frame_stack"])
         shift, pong = hyps["action_shift"], "Pong" in hyps["env_type"]
-        first = [np.asarray(e.reset(), dtype=np.float32) for e in envs]
+        snap = None
+        if self.norm is not None and bool(try_key(hyps, "norm_obs", False)):
+            snap = (self.norm() if callable(self.norm) else self.norm).snapshot()
+        prep = (lambda o: np.asarray(o, dtype=np.float32)) if snap is None else \
+            (lambda o: snap.normalize_obs(np.asarray(o, dtype=np.float32).reshape(-1)))
+        first = [prep(e.reset()) for e in envs]
         HW = first[0].size
         S = C * HW
         pin = torch.cuda.is_available()
@@ -1346,7 +1393,7 @@ class StatsRunner:
                 if done:                                        # this env's episode is over: it stops playing
                     active[j] = False
                 else:
-                    np_frames[j] = np.asarray(obs, dtype=np.float32).reshape(-1)
+                    np_frames[j] = prep(obs).reshape(-1)
             d_frames.copy_(h_frames, non_blocking=True)
             t += 1
         return float(ep_rew.sum()) / E
@@ -1401,7 +1448,12 @@ class DeviceStatsRunner:
 
     ENV_ID0 = 10007
 
-    def __init__(self, hyps, pool, uniform_fn=None, keep_actions=False, normal_fn=None):
+    def __init__(self, hyps, pool, uniform_fn=None, keep_actions=False, normal_fn=None, norm=None):
+        # norm: the training Runner's DeviceVecNorm (or a callable that returns it) under hyps norm_obs: the private Runner
+        # normalises its observations by that block in frozen mode and never writes it; rewards stay the game's
+        self.norm = norm
+        if bool(try_key(hyps, "norm_obs", False)) and norm is None:
+            raise ValueError("norm_obs: DeviceStatsRunner normalises by the training Runner's block: pass norm=runner.vecnorm")
         if not hasattr(pool, "device_step_post"):
             raise ValueError("DeviceStatsRunner: a device env pool with device_step_post (Snake / Pong / Breakout / Point "
                              "worlds)")
@@ -1414,6 +1466,8 @@ class DeviceStatsRunner:
         if self.K < 1 or self.max_steps < 1:
             raise ValueError("DeviceStatsRunner: eval_chunk >= 1 and max_eval_steps >= 1")
         self.hyps = dict(hyps, n_envs=self.E, n_rollouts=self.E, n_tsteps=self.K)
+        self._norm_obs = bool(self.hyps.pop("norm_obs", False))
+        self.hyps.pop("norm_rewards", None)
         self.calls, self.last = 0, None
         self.runner = self.datas = None
         self._chunk = 0
@@ -1438,7 +1492,8 @@ class DeviceStatsRunner:
         self.datas = D
         self.runner = Runner(D, self.hyps, None, None, None, env_pool=self.pool,
                              uniform_fn=None if self.uniform_fn is None else self._uniforms,
-                             normal_fn=None if self.normal_fn is None else self._normals, stash=False, bootstrap=False)
+                             normal_fn=None if self.normal_fn is None else self._normals, stash=False, bootstrap=False,
+                             frozen_norm=None if not self._norm_obs else (self.norm() if callable(self.norm) else self.norm))
         self.ep_rew = torch.zeros(E, **f32)
         self.ep_len, self.active = (torch.zeros(E, dtype=torch.int32, device=dev) for _ in range(2))
         self.n_active = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1453,6 +1508,8 @@ class DeviceStatsRunner:
         r._dev_graphs.clear()          # (graphs of the ids the pool leaves: never replayed again)
         pool.reset_all(env_id0=self.ENV_ID0 + self.calls * self.E)
         ops.frame_stack_push(pool.frames, self._ones, r.bookmark.data_ptr(), r.S, r.bookmark.data_ptr(), r.S, self.E, r.C, r.HW)
+        if r.vecnorm is not None:
+            r.vecnorm.launch(self.E, 0, out_ptr=r.bookmark.data_ptr(), out_stride=r.S, C=r.C, update=False)
         r.val_prev.zero_()
         r.done_eff.zero_()
         if r.h is not None:

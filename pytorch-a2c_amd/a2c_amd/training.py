@@ -21,7 +21,7 @@ from collections import deque
 import numpy as np
 import torch
 
-from . import breakout, cartpole, models, pendulum, point, pong, preprocessing, snake, worlds
+from . import breakout, cartpole, models, pendulum, point, pong, preprocessing, snake, vecnorm, worlds
 from .runner import DeviceStatsRunner, HostEnvPool, Runner, SequentialEnvironment, StatsRunner
 from .updater import Updater
 from .utils import cuda_if, deque_maxmin, try_key
@@ -66,6 +66,8 @@ _WORLDS = {
 _GAUSS_MODELS = ("FCModel", "GRUFCModel")
 # the nets that take a vector observation: with a softmax head, what the CartPole worlds can be trained with
 _FC_MODELS = _GAUSS_MODELS
+# the families with (1, L) observations: what running normalisation (hyps norm_obs / norm_rewards, section 6m) covers
+_VECTOR_WORLDS = ("Point", "CartPole", "Pendulum")
 # the keys of section 6i that shape what a policy is TRAINED on, not the game: evaluation worlds do not get them
 _TRAINING_ONLY = ("episodic_life", "clip_rewards")
 
@@ -79,6 +81,11 @@ def _world_family(env_type):
     """"Pong" of "Pong-device" / "Pong-host"; None for every other env_type"""
     family, _, where = str(env_type).partition("-")
     return family if family in _WORLDS and where in ("device", "host") else None
+
+
+def _norm_tensors(sd):
+    """a RunningNorm state_dict with its float64 arrays as torch tensors: what norm.p / best_norm.p hold"""
+    return {k: (torch.from_numpy(np.array(v, dtype=np.float64)) if isinstance(v, np.ndarray) else v) for k, v in sd.items()}
 
 
 class _PositionalFactory:
@@ -141,6 +148,12 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     ``hyps["eval_pool"] = "device"`` (the six ``*-device`` env types, no ``eval_env``) evaluates on the device instead: a
     second pool of ``n_test_eps`` worlds behind a ``DeviceStatsRunner`` (keys ``eval_chunk``, ``max_eval_steps``); the default
     ``"host"`` is the host twins.
+    ``hyps["norm_obs"]`` / ``hyps["norm_rewards"]`` (``norm_clip_obs`` 10, ``norm_clip_rew`` 10,
+    ``norm_eps`` 1e-8; ``gamma`` is the run's): running normalisation of the observations and of the rewards, baselines'
+    VecNormalize, as one launch behind every env step of the slot -- "Point-device", "CartPole-device" and "Pendulum-device"
+    only (anything else is a ValueError naming the key, before anything is written).  Evaluation normalises its observations
+    by the training block as it stands and never its rewards; ``norm.p`` is written wherever ``optim.p`` is (and read on
+    ``resume``), ``best_norm.p`` beside ``best_net.p``.
     Returns the best evaluation reward."""
     hyps = dict(DEFAULTS, **hyps)
     eval_pool = try_key(hyps, "eval_pool", None) or "host"
@@ -151,6 +164,18 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
         raise ValueError("a2c_amd: hyps['eval_pool'] = 'device' evaluates the device worlds (env_type 'Snake-device', "
                          "'Pong-device', 'Breakout-device', 'Point-device', 'CartPole-device' or 'Pendulum-device') and takes "
                          "no eval_env / env_fn")
+    # running normalisation: the device pools of the vector worlds, evaluated on lock-step twins or on
+    # the device; refused here, before anything is written or allocated, for everything else
+    norm = vecnorm.norm_settings(hyps)
+    if norm is not None:
+        key, family = vecnorm.norm_key(hyps), _world_family(hyps.get("env_type"))
+        if env_fn is not None or family not in _VECTOR_WORLDS or hyps["env_type"] != family + "-device":
+            raise ValueError(f"a2c_amd: {key} normalises inside the rollout slot of a device pool of the vector worlds "
+                             f"(env_type {', '.join(repr(f + '-device') for f in _VECTOR_WORLDS)}), not "
+                             f"{hyps.get('env_type')!r}" + (" with an env_fn" if env_fn is not None else ""))
+        if eval_env is not None:
+            raise ValueError(f"a2c_amd: {key} evaluates on lock-step host twins (eval_pool='host') or on the device "
+                             "(eval_pool='device'); a single eval_env plays the reference's serial loop, which is not normalised")
     if env_fn is None and _world_family(hyps.get("env_type")) == "Snake":
         if worlds.repeat_from_hyps(hyps, "Snake")[:2] != (1, 0):
             raise ValueError("a2c_amd: frame_skip / sticky_num are keys of the Pong and Breakout worlds: the Snake worlds "
@@ -186,6 +211,8 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     np.random.seed(hyps["seed"])
     net_save_file, best_net_file = os.path.join(save_folder, "net.p"), os.path.join(save_folder, "best_net.p")
     optim_save_file, log_file = os.path.join(save_folder, "optim.p"), os.path.join(save_folder, "log.txt")
+    # the normaliser's moments travel with the weights trained under them: norm.p beside optim.p, best_norm.p beside best_net.p
+    norm_save_file, best_norm_file = os.path.join(save_folder, "norm.p"), os.path.join(save_folder, "best_norm.p")
     log = open(log_file, "a" if hyps["resume"] else "w")
     for k in sorted(hyps):
         log.write(k + ":" + str(hyps[k]) + "\n")
@@ -314,6 +341,11 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     gate_q, stop_q, reward_q = queue.Queue(n_rollouts), queue.Queue(n_rollouts), queue.Queue(1)
     reward_q.put(-1)
     runner = Runner(shared_data, hyps, gate_q, stop_q, reward_q, env_pool=pool, uniform_fn=uniform_fn)
+    if norm is not None and hyps["resume"]:
+        runner.norm_state = torch.load(norm_save_file)
+    # (the block is made by the rollout thread's start(): evaluation asks for it when it first runs, an epoch later)
+    eval_norm = (lambda: runner.vecnorm) if norm is not None and norm["obs"] else None
+    norm_sd = None
     thread = threading.Thread(target=runner.run, args=(net,), daemon=True)
     thread.start()
 
@@ -339,12 +371,13 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
         # a second pool of the training pool's kind: same world and seed, n_test_eps worlds (DeviceStatsRunner gives them the
         # env ids of the host twins below, and fresh ones on every later call)
         stats_runner = DeviceStatsRunner(hyps, type(pool)(try_key(hyps, "n_test_eps", 15), device=pool.device, **eval_world),
-                                         uniform_fn=uniform_fn)
+                                         uniform_fn=uniform_fn, norm=eval_norm)
     elif eval_env is not None:
         stats_runner = StatsRunner(hyps, env=eval_env)
     elif family is not None:
         # host twins of worlds the training pool does not play (env ids from 10007 on)
-        stats_runner = StatsRunner(hyps, envs=[mk_env(10007 + j, eval_world) for j in range(try_key(hyps, "n_test_eps", 15))])
+        stats_runner = StatsRunner(hyps, envs=[mk_env(10007 + j, eval_world) for j in range(try_key(hyps, "n_test_eps", 15))],
+                                   norm=eval_norm)
     else:
         stats_runner = StatsRunner(hyps) if env_fn is None else None
     entr_coef_diff, lr_diff = hyps["entr_coef"] - hyps["entr_coef_low"], hyps["lr"] - hyps["lr_low"]
@@ -362,9 +395,15 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
         if on_epoch is not None:
             on_epoch(epoch, updater, shared_data)
         eval_rew = stats_runner.rollout(net) if stats_runner is not None else avg_reward
+        if norm is not None:
+            # the moments as the collected rollouts left them (the rollout thread is idle until the gate re-opens): what this
+            # epoch's saves write; one device read
+            norm_sd = _norm_tensors(runner.vecnorm.state_dict())
         if eval_rew > best_eval_rew:
             best_eval_rew = eval_rew
             updater.save_model(best_net_file, None)
+            if norm_sd is not None:
+                torch.save(norm_sd, best_norm_file)
         for i in range(n_rollouts):                                    # resume data collection
             gate_q.put(i)
         if hyps["decay_lr"]:
@@ -373,6 +412,8 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
             updater.entr_coef = entr_coef_diff * max((1 - T / hyps["max_tsteps"]), 0) + hyps["entr_coef_low"]
         if epoch % 10 == 0:
             updater.save_model(net_save_file, optim_save_file)
+            if norm_sd is not None:
+                torch.save(norm_sd, norm_save_file)
         past_rews.popleft()
         past_rews.append(avg_reward)
         max_rew, min_rew = deque_maxmin(past_rews)
@@ -385,6 +426,8 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                   "Time: {}\n\n".format(float(updater.norm), avg_action, best_eval_rew, max_rew, min_rew,
                                         time.time() - basetime))
     updater.save_model(net_save_file, optim_save_file)
+    if norm_sd is not None:
+        torch.save(norm_sd, norm_save_file)
     log.write("\nBestRew:" + str(best_eval_rew))
     log.close()
     for _i in range(n_rollouts):        # let the rollout the loop re-opened finish, then stop the thread and the env workers

@@ -13,7 +13,11 @@
   * ``--learn N``: a learning record -- ONE ``train()`` run of N epochs on "Pendulum-device" with ``eval_pool="device"`` and a
     fixed seed; the evaluation return after every epoch beside the return of the untrained net on the same kind of
     evaluation worlds (the first epoch's figure is taken after ONE update; ``untrained`` is measured before any) and the
-    -1225 a uniform-random policy averaged in the prototype of the rules.
+    -1225 a uniform-random policy averaged in the prototype of the rules;
+  * ``--norm``: the running-normalisation leg (hyps ``norm_obs`` / ``norm_rewards``) and nothing else: ms per
+    epoch on the "device_graph" path with the keys off and with both on, the samples of the two alternating; GPU microseconds
+    per a2c_vecnorm_step launch (both parts, B = 256, L = 4) inside a replayed hipGraph of 200 launches; with ``--learn N`` the
+    learning record repeated with both keys on.  ``--out profiles/vecnorm_bench.json``.
 
 Method: ONE PROCESS PER SAMPLE.  ``--sample WHAT`` runs one sample in this process (a warm-up that allocates, tunes and
 captures; then ``--epochs`` epochs, or the graph replays, between two HIP events) and prints one JSON line; without it the
@@ -58,21 +62,49 @@ def event_ms(fn, n):
     return a.elapsed_time(b)
 
 
-def hyps_for(n_envs, T, path):
-    return dict(gamma=.99, lambda_=.98, n_tsteps=T, n_rollouts=n_envs, n_envs=n_envs, n_frame_stack=4, action_shift=0,
+NORM_KEYS = dict(norm_obs=True, norm_rewards=True)
+
+
+def hyps_for(n_envs, T, path, norm=False):
+    return dict(NORM_KEYS if norm else {}, gamma=.99, lambda_=.98, n_tsteps=T, n_rollouts=n_envs, n_envs=n_envs, n_frame_stack=4, action_shift=0,
                 render=False, env_type="Pendulum-device" if path.startswith("device") else "Pendulum-host", use_bptt=False,
                 use_nstep_rets=False, norm_advs=True, entr_coef=.005, pi_coef=1.0, val_coef=.5, max_norm=.5, lr=1e-4,
                 optim_type="RMSprop", is_discrete=False, h_size=256, seed=0, rollout_graphs=path != "device_eager")
 
 
-def sample_epoch(model, path, n_envs, T, epochs):
+def sample_vecnorm(B=256, L=4, C=4, T=16, launches=200, replays=50, rounds=3):
+    """GPU microseconds per a2c_vecnorm_step (observations and rewards, update on): `launches` launches captured into one
+    hipGraph, `replays` replays between two HIP events; the median of the rounds"""
+    import torch
+    from a2c_amd import ops
+    from a2c_amd.vecnorm import DeviceVecNorm
+    dv = DeviceVecNorm(L, B, .99)
+    g = torch.Generator(device="cuda").manual_seed(3)
+    out = torch.randn((B, C * L), device="cuda", generator=g)
+    rewards, dones = torch.randn(B * T, device="cuda", generator=g), torch.zeros(B * T, device="cuda")
+
+    def play():
+        for i in range(launches):
+            dv.launch(B, 0, out_ptr=out.data_ptr(), out_stride=C * L, C=C, rewards=rewards, dones=dones, T=T, t=i % T)
+    play()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with ops.graph_capture(graph):
+        play()
+    for _ in range(3):
+        graph.replay()
+    us = [1e3 * event_ms(graph.replay, replays) / (launches * replays) for _ in range(rounds)]
+    return dict(vecnorm_step=statistics.median(us))
+
+
+def sample_epoch(model, path, n_envs, T, epochs, norm=False):
     import torch
     import a2c_amd
     from a2c_amd import preprocessing
     from a2c_amd.pendulum import DevicePendulumPool, PendulumEnv, PendulumFactory
     from a2c_amd.runner import HostEnvPool, Runner, SequentialEnvironment
     from a2c_amd.updater import Updater
-    hyps = hyps_for(n_envs, T, path)
+    hyps = hyps_for(n_envs, T, path, norm)
     torch.manual_seed(0)
     net = getattr(a2c_amd.models, model)([4, 4], 1, h_size=256, is_discrete=False)
     N = n_envs * T
@@ -149,8 +181,10 @@ def sample_kernel(B, steps=200, C=4, replays=50, rounds=3):
     return out
 
 
-def sample_learn(epochs):
-    """one train() run -> the evaluation return per epoch, and the untrained net's on worlds of the same kind"""
+def sample_learn(epochs, norm=False):
+    """one train() run -> the evaluation return per epoch, and the untrained net's on worlds of the same kind (norm: with
+    norm_obs and norm_rewards; the untrained net is then evaluated as every later epoch is, through a frozen block -- a fresh
+    one, count 1e-4, mean 0, var 1, which is where train()'s own block starts)"""
     import time
     import torch
     import a2c_amd
@@ -158,14 +192,19 @@ def sample_learn(epochs):
     from a2c_amd.runner import DeviceStatsRunner
     from a2c_amd.training import DEFAULTS, train
     folder = tempfile.mkdtemp(prefix="pendulum_learn_")
-    hyps = dict(LEARN, exp_name="pendulum_learn", main_path=folder)
+    hyps = dict(LEARN, exp_name="pendulum_learn", main_path=folder, **(NORM_KEYS if norm else {}))
     # the untrained net: train()'s own construction (same seed, same defaults), evaluated as train() evaluates
     full = dict(DEFAULTS, **hyps, is_discrete=False, action_shift=0, state_shape=[hyps["n_frame_stack"], 4], action_size=1)
     torch.manual_seed(hyps["seed"])
     net0 = getattr(a2c_amd.models, hyps["model"])(full["state_shape"], 1, bnorm=False,
                                                   **{k: v for k, v in full.items() if k != "use_bnorm"}).cuda()
     net0._ensure_device()
-    untrained = DeviceStatsRunner(full, DevicePendulumPool(hyps["n_test_eps"], "cuda", seed=hyps["seed"], **WORLD)).rollout(net0)
+    fresh = None
+    if norm:
+        from a2c_amd.vecnorm import DeviceVecNorm
+        fresh = DeviceVecNorm(4, hyps["n_envs"], full["gamma"])
+    untrained = DeviceStatsRunner(full, DevicePendulumPool(hyps["n_test_eps"], "cuda", seed=hyps["seed"], **WORLD),
+                                  norm=fresh).rollout(net0)
     curve = []
 
     class _Tap:
@@ -187,7 +226,7 @@ def sample_learn(epochs):
     finally:
         tr.DeviceStatsRunner = real
     n = max(1, len(curve) // 10)
-    return dict(settings={k: v for k, v in LEARN.items()}, epochs=epochs, seconds=round(time.time() - t0, 1),
+    return dict(settings=dict(LEARN, **(NORM_KEYS if norm else {})), epochs=epochs, seconds=round(time.time() - t0, 1),
                 env_steps=epochs * LEARN["n_envs"] * LEARN["n_tsteps"], untrained=round(float(untrained), 3),
                 uniform_random=UNIFORM_RANDOM, best=round(float(best), 3), first_tenth_mean=round(statistics.mean(curve[:n]), 3),
                 last_tenth_mean=round(statistics.mean(curve[-n:]), 3), eval_return_per_epoch=curve)
@@ -204,6 +243,35 @@ def child(args, what):
     return json.loads(out.strip().splitlines()[-1])
 
 
+def norm_leg(args):
+    """keys off / both on, alternating samples of the device_graph path; the launch; optionally the learning record"""
+    import torch
+    res = {}
+    if args.out and os.path.exists(args.out):      # records this leg does not produce (a comparison with a parent commit,
+        with open(args.out) as f:                  # headline samples; an earlier learning record without --learn) stay
+            res = json.load(f)
+    res.update(device=torch.cuda.get_device_name(0), repeats=args.repeats, n_envs=args.n_envs, n_tsteps=args.n_tsteps,
+               epochs=args.epochs, optim="RMSprop", world=WORLD, path="device_graph", ms_per_epoch={})
+    for model in MODELS:
+        rows = dict(keys_off=[], both_on=[])
+        for _ in range(args.repeats):
+            rows["keys_off"].append(child(args, f"epoch:{model}:device_graph")["ms_per_epoch"])
+            rows["both_on"].append(child(args, f"epoch:{model}:device_graph:norm")["ms_per_epoch"])
+        res["ms_per_epoch"][model] = {k: spread(v) for k, v in rows.items()}
+        print(f"# {model}: {res['ms_per_epoch'][model]}", file=sys.stderr, flush=True)
+    res["vecnorm_step_us"] = spread([child(args, "vecnorm")["vecnorm_step"] for _ in range(args.repeats)])
+    print(f"# a2c_vecnorm_step: {res['vecnorm_step_us']} us", file=sys.stderr, flush=True)
+    if args.learn > 0:
+        res["learning_norm"] = child(args, f"learn:{args.learn}:norm")
+        L = res["learning_norm"]
+        print(f"# learning with both keys, {L['epochs']} epochs in {L['seconds']} s: untrained {L['untrained']}, first tenth "
+              f"{L['first_tenth_mean']}, last tenth {L['last_tenth_mean']}, best {L['best']}", file=sys.stderr, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5, help="samples per figure: one process each")
@@ -213,7 +281,9 @@ def main():
     ap.add_argument("--n-tsteps", type=int, default=16)
     ap.add_argument("--learn", type=int, default=0, help="epochs of the learning record (0: none)")
     ap.add_argument("--only", default=None, help="comma-separated subset of: kernel, learn, " + ", ".join(PATHS))
-    ap.add_argument("--sample", default=None, help="run ONE sample in this process: kernel:B, epoch:MODEL:PATH or learn:N")
+    ap.add_argument("--norm", action="store_true", help="the running-normalisation leg only (see the module docstring)")
+    ap.add_argument("--sample", default=None, help="run ONE sample in this process: kernel:B, vecnorm, epoch:MODEL:PATH[:norm] "
+                                                   "or learn:N[:norm]")
     ap.add_argument("--sample-timeout", type=float, default=600.0)
     ap.add_argument("--out", default=None, help="also write the result to this JSON file")
     args = ap.parse_args()
@@ -223,13 +293,18 @@ def main():
         kind, *rest = args.sample.split(":")
         if kind == "kernel":
             res = sample_kernel(int(rest[0]))
+        elif kind == "vecnorm":
+            res = sample_vecnorm()
         elif kind == "learn":
-            res = sample_learn(int(rest[0]))
+            res = sample_learn(int(rest[0]), norm=rest[1:] == ["norm"])
         else:
-            model, path = rest
-            res = sample_epoch(model, path, args.n_envs, args.n_tsteps, args.epochs if path.startswith("device") else args.host_epochs)
+            model, path = rest[:2]
+            res = sample_epoch(model, path, args.n_envs, args.n_tsteps, args.epochs if path.startswith("device") else args.host_epochs,
+                               norm=rest[2:] == ["norm"])
         print(json.dumps(res))
         return
+    if args.norm:
+        return norm_leg(args)
     only = set(args.only.split(",")) if args.only else {"kernel", "learn", *PATHS}
     res = dict(device=torch.cuda.get_device_name(0), repeats=args.repeats, n_envs=args.n_envs, n_tsteps=args.n_tsteps,
                epochs=args.epochs, host_epochs=args.host_epochs, optim="RMSprop", world=WORLD, point_world=POINT_WORLD, epoch={},
