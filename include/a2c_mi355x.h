@@ -485,6 +485,28 @@ int a2c_gauss_loss_fwd_bwd(const float *heads, int64_t ld_heads, const float *va
                            const double *adv_sums, const double *sums, int64_t n_local, int64_t n_global, int n,
                            float pi_coef, float val_coef, float entr_coef, float *dheads, int64_t ldd, float *dvals,
                            int64_t dval_stride, double *loss_sums, a2c_stream_t stream);
+/* The per-sample Gaussian log-likelihood loss (hyps["gauss_loss"] = "exact"; NOT the reference's),
+ * forward AND backward in ONE launch under the protocol of a2c_loss_fwd_bwd: no batch-wide quantity is needed before the
+ * gradients, so a sharded update has no collective here.  With w_i the advantage (normalised as in a2c_loss_fwd_bwd when
+ * adv_sums != NULL -- every row its own, for n == 1 too), invN = 1/n_global and, per row i and action dim j,
+ *   sigma_ij = softplus(raw_ij) + 1e-4,  u_ij = (a_ij - mu_ij)/sigma_ij,
+ *   logp_i = sum_j (-u_ij^2/2 - log sigma_ij - log(2 pi)/2),   H_i = sum_j (1/2 + log(2 pi)/2 + log sigma_ij),
+ * it writes
+ *   dheads[i*ldd + j]     = dL/dmu_ij  = -pi_coef w_i invN u_ij/sigma_ij,
+ *   dheads[i*ldd + n + j] = dL/draw_ij = dL/dsigma_ij * (raw_ij > 20 ? 1 : e^raw/(e^raw + 1)),
+ *                           dL/dsigma_ij = -pi_coef w_i invN (u_ij^2 - 1)/sigma_ij - entr_coef invN/sigma_ij,
+ *   dvals[i*dval_stride]  = dL/dV_i = val_coef 2 (V_i - R_i) invN,
+ *   loss_sums[0..2] (double) = sum_i w_i logp_i, sum_i (V_i - R_i)^2, -sum_i H_i over the local rows,
+ * the sums in a2c_loss_fwd_bwd's convention: Pi_Loss = -pi_coef mean(w logp), Entropy = entr_coef mean H and
+ * Loss = Pi_Loss + ValLoss - Entropy (the entropy is MAXIMISED, as on the discrete path).  No clamps (sigma >= 1e-4).
+ * Deterministic (fixed-order grid reduction in reduce_scratch; at most 1024 workgroups of 256 rows, grid-stride beyond).
+ * A2C_ERR_ARG, nothing launched: n outside 1 .. A2C_GAUSS_MAX_N, ld_heads or ldd < 2n, ld_act < n, a NULL pointer;
+ * n_local == 0 zeroes loss_sums.                                                                                        */
+int a2c_gauss_nll_fwd_bwd(const float *heads, int64_t ld_heads, const float *vals, int64_t val_stride,
+                          const float *actions, int64_t ld_act, const float *advs, const float *returns,
+                          const double *adv_sums, int64_t n_local, int64_t n_global, int n, float pi_coef,
+                          float val_coef, float entr_coef, float *dheads, int64_t ldd, float *dvals,
+                          int64_t dval_stride, double *loss_sums, double *reduce_scratch, a2c_stream_t stream);
 
 /* ------------------------------------------------------------------ a6: dense layers
  * C[M,N] = (accumulate ? C : 0) + opA(A)[M,K] * opB(B)[K,N] (+ bias[N]) ; then optional ReLU ; then optional

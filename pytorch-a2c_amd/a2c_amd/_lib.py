@@ -121,6 +121,8 @@ SIGNATURES = {
     "a2c_gauss_loss_sums": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, c_int64, c_int64, c_int, P, P, P]),
     "a2c_gauss_loss_fwd_bwd": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, P, c_int64, c_int64, c_int, c_float,
                                         c_float, c_float, P, c_int64, P, c_int64, P, P]),
+    "a2c_gauss_nll_fwd_bwd": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, c_int64, c_int64, c_int, c_float,
+                                       c_float, c_float, P, c_int64, P, c_int64, P, P, P]),
     "a2c_gemm_ws_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "a2c_gemm_x9_ws_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "a2c_gemm_x6_image_bytes": (c_size_t, [c_int64, c_int64]),

@@ -759,6 +759,22 @@ def gauss_loss_fwd_bwd(heads, vals, actions, advs, returns, adv_sums, sums, n_gl
           "a2c_gauss_loss_fwd_bwd")
 
 
+def gauss_nll_fwd_bwd(heads, vals, actions, advs, returns, adv_sums, n_global, n, pi_coef, val_coef, entr_coef, dheads,
+                      dvals, loss_sums, st=None, scratch=None):
+    """the per-sample Gaussian log-likelihood loss (hyps["gauss_loss"] = "exact") in one launch: dheads rows [dmu | draw],
+    dvals and the three loss sums of the local rows (a2c_gauss_nll_fwd_bwd); only stride(0) of the 2-D arguments is used"""
+    _chk(heads, "heads", contig=False); _chk(vals, "vals", contig=False); _chk(actions, "actions", contig=False)
+    _chk(advs, "advs"); _chk(returns, "returns")
+    _chk(dheads, "dheads", contig=False); _chk(dvals, "dvals", contig=False); _chk(loss_sums, "loss_sums", torch.float64)
+    st = st if st is not None else stream()
+    check(lib().a2c_gauss_nll_fwd_bwd(_p(heads), heads.stride(0), _p(vals), vals.stride(0), _p(actions), actions.stride(0),
+                                      _p(advs), _p(returns), _p(adv_sums), heads.shape[0], n_global, n, float(pi_coef),
+                                      float(val_coef), float(entr_coef), _p(dheads), dheads.stride(0), _p(dvals),
+                                      dvals.stride(0), _p(loss_sums),
+                                      _p(scratch if scratch is not None else reduce_scratch(heads.device, st)), st),
+          "a2c_gauss_nll_fwd_bwd")
+
+
 # ---------------------------------------------------------------- dense
 def pick_splitk(M, N, K, target_wgs=512, min_k=32):
     min_k = int(os.environ.get("A2C_SPLITK_MIN_K", min_k))

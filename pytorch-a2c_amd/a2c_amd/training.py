@@ -23,13 +23,14 @@ import torch
 
 from . import breakout, cartpole, models, pendulum, point, pong, preprocessing, snake, vecnorm, worlds
 from .runner import DeviceStatsRunner, HostEnvPool, Runner, SequentialEnvironment, StatsRunner
-from .updater import Updater
+from .updater import Updater, gauss_loss_mode
 from .utils import cuda_if, deque_maxmin, try_key
 
 DEFAULTS = dict(n_frame_stack=4, n_rollouts=None, n_past_rews=25, h_size=256, lr=1e-4, lr_low=1e-12, lambda_=.98,
                 gamma=.99, gamma_high=.995, val_coef=.5, entr_coef=.005, entr_coef_low=.001, pi_coef=1.0, max_norm=.5,
                 resume=False, render=False, decay_lr=False, decay_entr=False, use_nstep_rets=False, norm_advs=True,
-                use_bnorm=False, use_bptt=False, optim_type="RMSprop", n_test_eps=15, max_tsteps=4e7)
+                use_bnorm=False, use_bptt=False, optim_type="RMSprop", n_test_eps=15, max_tsteps=4e7,
+                gauss_loss="reference")
 
 
 def get_exp_num(main_path, exp_name):
@@ -154,8 +155,18 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     only (anything else is a ValueError naming the key, before anything is written).  Evaluation normalises its observations
     by the training block as it stands and never its rewards; ``norm.p`` is written wherever ``optim.p`` is (and read on
     ``resume``), ``best_norm.p`` beside ``best_net.p``.
+    ``hyps["gauss_loss"]``: ``"reference"`` (the default: the reference's Gaussian loss, at parity) or
+    ``"exact"`` (the per-sample Gaussian log-likelihood loss with an entropy bonus, one launch per update), for continuous
+    action spaces only (anything else is a ValueError naming the key); it changes the update alone, not the rollout, the
+    sampling or the evaluation.
     Returns the best evaluation reward."""
     hyps = dict(DEFAULTS, **hyps)
+    # gauss_loss (DESIGN.md section 6n): refused here, before anything is written or allocated, for a value that is neither
+    # "reference" nor "exact" and for "exact" where the action space is known to be discrete (a device world's family, an
+    # env_fn's is_discrete key; a gym env's space is only known from the probe, where the Updater refuses it)
+    world_family = _world_family(hyps.get("env_type")) if env_fn is None else None
+    gauss_loss_mode(hyps, (not _float_family(world_family)) if world_family is not None else
+                    (bool(try_key(hyps, "is_discrete", True)) if env_fn is not None else None))
     eval_pool = try_key(hyps, "eval_pool", None) or "host"
     if eval_pool not in ("host", "device"):
         raise ValueError(f"a2c_amd: hyps['eval_pool'] is 'host' or 'device', not {eval_pool!r}")

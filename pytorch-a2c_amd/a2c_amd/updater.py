@@ -7,7 +7,8 @@ One ``update_model`` call enqueues, on one HIP stream and without host round tri
 final read-back of five scalars:
   fused GAE + returns scan -> model forward (N = n_rollouts*n_tsteps samples, or the BPTT unroll)
   -> advantage statistics -> fused loss forward+backward (continuous actions: Gaussian loss sums [-> all-reduce] ->
-  Gaussian loss forward+backward) -> model backward into the flat gradient
+  Gaussian loss forward+backward; with hyps["gauss_loss"] = "exact" ONE launch, the per-sample Gaussian log-likelihood
+  loss forward+backward, and no all-reduce) -> model backward into the flat gradient
   arena -> [RCCL all-reduce when sharded] -> grad-norm reduction -> fused clip + optimiser step (optim.OPTIMIZERS).
 """
 import sys
@@ -21,6 +22,22 @@ from .utils import try_key
 
 def recurrent_key(shared_data):
     return "h_states" in shared_data
+
+
+GAUSS_LOSSES = ("reference", "exact")
+
+
+def gauss_loss_mode(hyps, is_discrete=None):
+    """hyps["gauss_loss"]: "reference" (the default, also when the key is absent: the reference's Gaussian loss, at parity)
+    or "exact" (the per-sample log-likelihood loss, a2c_gauss_nll_fwd_bwd), for the nets with a
+    Gaussian head only.  ValueError naming the key otherwise; is_discrete None = not known yet."""
+    mode = try_key(hyps, "gauss_loss", "reference")
+    if mode not in GAUSS_LOSSES:
+        raise ValueError(f"a2c_amd: hyps['gauss_loss'] is 'reference' or 'exact', not {mode!r}")
+    if mode == "exact" and is_discrete:
+        raise ValueError("a2c_amd: hyps['gauss_loss'] = 'exact' is the loss of the continuous (Gaussian) nets: it needs "
+                         "is_discrete=False")
+    return mode
 
 
 class _CutShard:
@@ -151,6 +168,7 @@ class Updater:
         self.is_discrete = hyps["is_discrete"]
         if bool(self.is_discrete) != bool(getattr(net, "is_discrete", True)):
             raise ValueError("a2c_amd: hyps['is_discrete'] does not match the net's is_discrete")
+        self.gauss_loss = gauss_loss_mode(hyps, self.is_discrete)
         self.shard = shard if shard is not None else Shard()
         self.optim = self.new_optim(hyps["lr"])
         self.info = {}
@@ -179,7 +197,8 @@ class Updater:
                      err=torch.zeros(1, dtype=torch.int32, device=dev),
                      out5=torch.zeros(5, dtype=torch.float64, device=dev),
                      host=torch.zeros(8, dtype=torch.float64).pin_memory() if torch.cuda.is_available() else None)
-            if not self.is_discrete:    # the six Gaussian loss sums (a2c_gauss_loss_sums), all-reduced when sharded
+            if not self.is_discrete and self.gauss_loss == "reference":
+                # the six Gaussian loss sums (a2c_gauss_loss_sums), all-reduced when sharded
                 b["gsums"] = torch.zeros(6, dtype=torch.float64, device=dev)
             self._bufs = b
         return b
@@ -260,6 +279,12 @@ class Updater:
         if self.is_discrete:
             ops.loss_fwd_bwd(logits, vals, actions, advs, rets, adv_sums, n_global, try_key(hyps, "pi_coef", 1.0),
                              hyps["val_coef"], hyps["entr_coef"], dl, dv, stats[2:5], st, scratch=b["scratch"])
+        elif self.gauss_loss == "exact":
+            # the per-sample log-likelihood loss: every row's gradient from that row and the advantage statistics alone, so
+            # one launch and no collective (the three loss sums travel in the gradient arena's tail below)
+            ops.gauss_nll_fwd_bwd(logits, vals, actions, advs, rets, adv_sums, n_global, net.output_space,
+                                  try_key(hyps, "pi_coef", 1.0), hyps["val_coef"], hyps["entr_coef"], dl, dv, stats[2:5], st,
+                                  scratch=b["scratch"])
         else:
             # the Gaussian loss needs batch-wide sums before any gradient (mse and K of the mu gradient): two launches,
             # the sums all-reduced in between when sharded (a capture is cut there, like at the advantage moments)

@@ -3,7 +3,8 @@
 // softplus(raw) + 1e-4 with torch's threshold 20.  The loss needs batch-wide sums (F.mse_loss reduces over the whole
 // (N, n) block), so it is two launches: a2c_gauss_loss_sums (fp64 partials, fixed-order grid reduction) and
 // a2c_gauss_loss_fwd_bwd (gradients from the -- possibly all-reduced -- sums).  One lane per row; the rows are short
-// (n <= A2C_GAUSS_MAX_N), so every launch is latency bound at the reference's sizes.
+// (n <= A2C_GAUSS_MAX_N), so every launch is latency bound at the reference's sizes.  a2c_gauss_nll_fwd_bwd is the
+// per-sample log-likelihood loss (hyps["gauss_loss"] = "exact"): one launch, no batch-wide sums.
 #include "a2c_common.h"
 
 namespace {
@@ -160,6 +161,59 @@ __global__ __launch_bounds__(256) void gauss_fwd_bwd_kernel(const float* __restr
     dvals[i * dvstride] = val_coef * 2.f * dv * invN;
   }
 }
+// The per-sample Gaussian log-likelihood loss (hyps["gauss_loss"] = "exact"), forward and backward in one pass like
+// loss_kernel (loss.hip): every row's gradient needs only that row and the advantage statistics, so there is no first
+// launch for batch-wide sums.  The row's two sums over the action dims are kept in fp64 (u^2 reaches 1e8 on a tiny-sigma
+// row and would swallow the log sigma terms in fp32); the gradients are fp32.
+__global__ __launch_bounds__(256) void gauss_nll_kernel(const float* __restrict__ heads, long ldh, const float* __restrict__ vals,
+                                                        long vstride, const float* __restrict__ actions, long lda,
+                                                        const float* __restrict__ advs, const float* __restrict__ returns,
+                                                        const double* __restrict__ adv_sums, long n_local, long n_global, int n,
+                                                        float pi_coef, float val_coef, float entr_coef,
+                                                        float* __restrict__ dheads, long ldd, float* __restrict__ dvals,
+                                                        long dvstride, double* loss_sums, double* scratch) {
+  __shared__ double sm[4];
+  constexpr double kHalfLog2Pi = 0.91893853320467274178;
+  const AdvNorm an = adv_norm(adv_sums, n_global);
+  const float invN = 1.0f / (float)n_global;
+  const float gen = entr_coef * invN;
+  double s_pi = 0.0, s_val = 0.0, s_ent = 0.0;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n_local; i += gridDim.x * 256L) {
+    float w = advs[i];
+    if (an.on) w = (w - an.mean) / an.den;
+    const float gpi = -pi_coef * w * invN;
+    const float* row = heads + i * ldh;
+    const float* act = actions + i * lda;
+    float* drow = dheads + i * ldd;
+    double su2 = 0.0, sls = 0.0;         // sum_j u^2, sum_j log sigma
+    for (int j = 0; j < n; ++j) {
+      const float raw = row[n + j];
+      const float sg = gauss_sigma(raw);
+      const float inv_s = 1.f / sg;
+      const float u = (act[j] - row[j]) * inv_s;
+      const float dsig = (gpi * (u * u - 1.f) - gen) * inv_s;
+      float draw = dsig;
+      if (!(raw > 20.f)) {               // softplus backward: g * z / (z + 1), z = exp(raw)
+        const float z = expf(raw);
+        draw = dsig * z / (z + 1.f);
+      }
+      drow[j] = gpi * u * inv_s;
+      drow[n + j] = draw;
+      su2 += (double)(u * u);
+      sls += (double)logf(sg);
+    }
+    const float dv = vals[i * vstride] - returns[i];
+    dvals[i * dvstride] = val_coef * 2.f * dv * invN;
+    s_pi += (double)w * (-0.5 * su2 - sls - (double)n * kHalfLog2Pi);
+    s_val += (double)(dv * dv);
+    s_ent -= (double)n * (0.5 + kHalfLog2Pi) + sls;
+  }
+  s_pi = block_sum_256(s_pi, sm);
+  s_val = block_sum_256(s_val, sm);
+  s_ent = block_sum_256(s_ent, sm);
+  const double v3[3] = {s_pi, s_val, s_ent};
+  grid_sum_ordered<3>(v3, loss_sums, scratch, sm);       // fixed-order second stage: no fp64 atomics
+}
 }  // namespace
 
 extern "C" int a2c_gauss_head_publish(const float* heads, int64_t ld_heads, const float* eps, int64_t ld_eps, float* sigma,
@@ -229,6 +283,28 @@ extern "C" int a2c_gauss_loss_fwd_bwd(const float* heads, int64_t ld_heads, cons
                      (long)ld_heads, vals, (long)val_stride, actions, (long)ld_act, advs, returns, adv_sums, sums,
                      (long)n_local, (long)n_global, n, pi_coef, val_coef, entr_coef, dheads, (long)ldd, dvals,
                      (long)dval_stride, loss_sums);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+extern "C" int a2c_gauss_nll_fwd_bwd(const float* heads, int64_t ld_heads, const float* vals, int64_t val_stride,
+                                     const float* actions, int64_t ld_act, const float* advs, const float* returns,
+                                     const double* adv_sums, int64_t n_local, int64_t n_global, int n, float pi_coef,
+                                     float val_coef, float entr_coef, float* dheads, int64_t ldd, float* dvals,
+                                     int64_t dval_stride, double* loss_sums, double* scratch, a2c_stream_t stream) {
+  if (n_local < 0 || n_global < n_local || n_global < 1 || n < 1 || n > A2C_GAUSS_MAX_N || !loss_sums || !scratch)
+    return A2C_ERR_ARG;
+  if (adv_sums && n_global < 2) return A2C_ERR_ARG;
+  if (n_local == 0) {
+    a2c_zero_async(loss_sums, 3 * sizeof(double), a2c_s(stream));
+    return A2C_OK;
+  }
+  if (!heads || !vals || !actions || !advs || !returns || !dheads || !dvals || ld_heads < 2 * n || ld_act < n || ldd < 2 * n)
+    return A2C_ERR_ARG;
+  hipLaunchKernelGGL(gauss_nll_kernel, dim3(a2c_grid_1d(n_local, 256, A2C_REDUCE_MAX_BLOCKS)), dim3(256), 0, a2c_s(stream),
+                     heads, (long)ld_heads, vals, (long)val_stride, actions, (long)ld_act, advs, returns, adv_sums,
+                     (long)n_local, (long)n_global, n, pi_coef, val_coef, entr_coef, dheads, (long)ldd, dvals,
+                     (long)dval_stride, loss_sums, scratch);
   A2C_CHECK_LAUNCH();
   return A2C_OK;
 }

@@ -17,7 +17,12 @@
   * ``--norm``: the running-normalisation leg (hyps ``norm_obs`` / ``norm_rewards``) and nothing else: ms per
     epoch on the "device_graph" path with the keys off and with both on, the samples of the two alternating; GPU microseconds
     per a2c_vecnorm_step launch (both parts, B = 256, L = 4) inside a replayed hipGraph of 200 launches; with ``--learn N`` the
-    learning record repeated with both keys on.  ``--out profiles/vecnorm_bench.json``.
+    learning record repeated with both keys on.  ``--out profiles/vecnorm_bench.json``;
+  * ``--gauss-loss {reference,exact}``: the value of hyps ``gauss_loss`` in the epoch samples and in
+    ``--learn``; ``--exact`` is the leg that sets the two beside each other and nothing else: ms per epoch on the
+    "device_graph" path under "reference" and under "exact", the samples of the two alternating; with ``--learn N`` the
+    learning record under "exact" (with ``--norm`` too: that record with both normalisation keys on).
+    ``--out profiles/pendulum_exact_bench.json``.
 
 Method: ONE PROCESS PER SAMPLE.  ``--sample WHAT`` runs one sample in this process (a warm-up that allocates, tunes and
 captures; then ``--epochs`` epochs, or the graph replays, between two HIP events) and prints one JSON line; without it the
@@ -65,8 +70,8 @@ def event_ms(fn, n):
 NORM_KEYS = dict(norm_obs=True, norm_rewards=True)
 
 
-def hyps_for(n_envs, T, path, norm=False):
-    return dict(NORM_KEYS if norm else {}, gamma=.99, lambda_=.98, n_tsteps=T, n_rollouts=n_envs, n_envs=n_envs, n_frame_stack=4, action_shift=0,
+def hyps_for(n_envs, T, path, norm=False, gauss_loss="reference"):
+    return dict(NORM_KEYS if norm else {}, gauss_loss=gauss_loss, gamma=.99, lambda_=.98, n_tsteps=T, n_rollouts=n_envs, n_envs=n_envs, n_frame_stack=4, action_shift=0,
                 render=False, env_type="Pendulum-device" if path.startswith("device") else "Pendulum-host", use_bptt=False,
                 use_nstep_rets=False, norm_advs=True, entr_coef=.005, pi_coef=1.0, val_coef=.5, max_norm=.5, lr=1e-4,
                 optim_type="RMSprop", is_discrete=False, h_size=256, seed=0, rollout_graphs=path != "device_eager")
@@ -97,14 +102,14 @@ def sample_vecnorm(B=256, L=4, C=4, T=16, launches=200, replays=50, rounds=3):
     return dict(vecnorm_step=statistics.median(us))
 
 
-def sample_epoch(model, path, n_envs, T, epochs, norm=False):
+def sample_epoch(model, path, n_envs, T, epochs, norm=False, gauss_loss="reference"):
     import torch
     import a2c_amd
     from a2c_amd import preprocessing
     from a2c_amd.pendulum import DevicePendulumPool, PendulumEnv, PendulumFactory
     from a2c_amd.runner import HostEnvPool, Runner, SequentialEnvironment
     from a2c_amd.updater import Updater
-    hyps = hyps_for(n_envs, T, path, norm)
+    hyps = hyps_for(n_envs, T, path, norm, gauss_loss)
     torch.manual_seed(0)
     net = getattr(a2c_amd.models, model)([4, 4], 1, h_size=256, is_discrete=False)
     N = n_envs * T
@@ -181,7 +186,7 @@ def sample_kernel(B, steps=200, C=4, replays=50, rounds=3):
     return out
 
 
-def sample_learn(epochs, norm=False):
+def sample_learn(epochs, norm=False, gauss_loss="reference"):
     """one train() run -> the evaluation return per epoch, and the untrained net's on worlds of the same kind (norm: with
     norm_obs and norm_rewards; the untrained net is then evaluated as every later epoch is, through a frozen block -- a fresh
     one, count 1e-4, mean 0, var 1, which is where train()'s own block starts)"""
@@ -192,7 +197,8 @@ def sample_learn(epochs, norm=False):
     from a2c_amd.runner import DeviceStatsRunner
     from a2c_amd.training import DEFAULTS, train
     folder = tempfile.mkdtemp(prefix="pendulum_learn_")
-    hyps = dict(LEARN, exp_name="pendulum_learn", main_path=folder, **(NORM_KEYS if norm else {}))
+    keys = dict(NORM_KEYS if norm else {}, gauss_loss=gauss_loss)
+    hyps = dict(LEARN, exp_name="pendulum_learn", main_path=folder, **keys)
     # the untrained net: train()'s own construction (same seed, same defaults), evaluated as train() evaluates
     full = dict(DEFAULTS, **hyps, is_discrete=False, action_shift=0, state_shape=[hyps["n_frame_stack"], 4], action_size=1)
     torch.manual_seed(hyps["seed"])
@@ -226,7 +232,7 @@ def sample_learn(epochs, norm=False):
     finally:
         tr.DeviceStatsRunner = real
     n = max(1, len(curve) // 10)
-    return dict(settings=dict(LEARN, **(NORM_KEYS if norm else {})), epochs=epochs, seconds=round(time.time() - t0, 1),
+    return dict(settings=dict(LEARN, **keys), epochs=epochs, seconds=round(time.time() - t0, 1),
                 env_steps=epochs * LEARN["n_envs"] * LEARN["n_tsteps"], untrained=round(float(untrained), 3),
                 uniform_random=UNIFORM_RANDOM, best=round(float(best), 3), first_tenth_mean=round(statistics.mean(curve[:n]), 3),
                 last_tenth_mean=round(statistics.mean(curve[-n:]), 3), eval_return_per_epoch=curve)
@@ -236,9 +242,10 @@ def spread(xs, nd=3):
     return dict(median=round(statistics.median(xs), nd), min=round(min(xs), nd), max=round(max(xs), nd), samples=[round(x, nd) for x in xs])
 
 
-def child(args, what):
+def child(args, what, gauss_loss=None):
     cmd = [sys.executable, os.path.abspath(__file__), "--sample", what, "--epochs", str(args.epochs), "--host-epochs",
-           str(args.host_epochs), "--n-envs", str(args.n_envs), "--n-tsteps", str(args.n_tsteps)]
+           str(args.host_epochs), "--n-envs", str(args.n_envs), "--n-tsteps", str(args.n_tsteps), "--gauss-loss",
+           gauss_loss or args.gauss_loss]
     out = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=args.sample_timeout).stdout
     return json.loads(out.strip().splitlines()[-1])
 
@@ -272,6 +279,40 @@ def norm_leg(args):
     print(json.dumps(res))
 
 
+def exact_leg(args):
+    """gauss_loss "reference" / "exact", alternating samples of the device_graph path; optionally the learning record under
+    "exact" (with --norm: with both normalisation keys on), kept under its own name beside what the file already holds"""
+    import torch
+    res = {}
+    if args.out and os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    res.update(device=torch.cuda.get_device_name(0), world=WORLD)
+
+    def save():
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+    if args.repeats > 0:            # (--repeats 0 --learn N: the learning record alone)
+        res.update(repeats=args.repeats, n_envs=args.n_envs, n_tsteps=args.n_tsteps, epochs=args.epochs, optim="RMSprop",
+                   path="device_graph", ms_per_epoch={})
+        for model in MODELS:
+            rows = dict(reference=[], exact=[])
+            for _ in range(args.repeats):
+                for mode in rows:
+                    rows[mode].append(child(args, f"epoch:{model}:device_graph", mode)["ms_per_epoch"])
+            res["ms_per_epoch"][model] = {k: spread(v) for k, v in rows.items()}
+            print(f"# {model}: {res['ms_per_epoch'][model]}", file=sys.stderr, flush=True)
+            save()
+    if args.learn > 0:
+        name = "learning_exact_norm" if args.norm else "learning_exact"
+        L = res[name] = child(args, f"learn:{args.learn}" + (":norm" if args.norm else ""), "exact")
+        print(f"# {name}, {L['epochs']} epochs in {L['seconds']} s: untrained {L['untrained']}, first tenth "
+              f"{L['first_tenth_mean']}, last tenth {L['last_tenth_mean']}, best {L['best']}", file=sys.stderr, flush=True)
+    save()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5, help="samples per figure: one process each")
@@ -282,6 +323,9 @@ def main():
     ap.add_argument("--learn", type=int, default=0, help="epochs of the learning record (0: none)")
     ap.add_argument("--only", default=None, help="comma-separated subset of: kernel, learn, " + ", ".join(PATHS))
     ap.add_argument("--norm", action="store_true", help="the running-normalisation leg only (see the module docstring)")
+    ap.add_argument("--gauss-loss", default="reference", choices=("reference", "exact"),
+                    help="hyps['gauss_loss'] of the epoch samples and of --learn")
+    ap.add_argument("--exact", action="store_true", help="the gauss_loss leg only (see the module docstring)")
     ap.add_argument("--sample", default=None, help="run ONE sample in this process: kernel:B, vecnorm, epoch:MODEL:PATH[:norm] "
                                                    "or learn:N[:norm]")
     ap.add_argument("--sample-timeout", type=float, default=600.0)
@@ -296,18 +340,21 @@ def main():
         elif kind == "vecnorm":
             res = sample_vecnorm()
         elif kind == "learn":
-            res = sample_learn(int(rest[0]), norm=rest[1:] == ["norm"])
+            res = sample_learn(int(rest[0]), norm=rest[1:] == ["norm"], gauss_loss=args.gauss_loss)
         else:
             model, path = rest[:2]
             res = sample_epoch(model, path, args.n_envs, args.n_tsteps, args.epochs if path.startswith("device") else args.host_epochs,
-                               norm=rest[2:] == ["norm"])
+                               norm=rest[2:] == ["norm"], gauss_loss=args.gauss_loss)
         print(json.dumps(res))
         return
+    if args.exact:
+        return exact_leg(args)
     if args.norm:
         return norm_leg(args)
     only = set(args.only.split(",")) if args.only else {"kernel", "learn", *PATHS}
     res = dict(device=torch.cuda.get_device_name(0), repeats=args.repeats, n_envs=args.n_envs, n_tsteps=args.n_tsteps,
-               epochs=args.epochs, host_epochs=args.host_epochs, optim="RMSprop", world=WORLD, point_world=POINT_WORLD, epoch={},
+               epochs=args.epochs, host_epochs=args.host_epochs, optim="RMSprop", gauss_loss=args.gauss_loss, world=WORLD,
+               point_world=POINT_WORLD, epoch={},
                kernel_us_per_env_step={})
     if args.out and os.path.exists(args.out):      # a run with --only adds to what an earlier run measured
         with open(args.out) as f:
