@@ -177,7 +177,9 @@ int a2c_frame_prep_u8(const uint8_t *raw, int64_t raw_stride, int H, int W, int 
  * (the state the previous slot ended in), nvalid_rows[r*T] = nvalid_carry[r].  a2c_rollout_post_frames: the bookkeeping
  * of a2c_rollout_post[_rec] for env step t WITHOUT a frame-stack copy (the ingest wrote the new frame straight into
  * frames[r][t+C]): rewards / dones / deltas / val_prev [/ hidden-state reset and h_states row], and the valid-plane
- * count of state t+1 (1 after a real done, else min(count + 1, C)) into nvalid_rows[(slot0+b)*T + t+1] / nvalid_carry.
+ * count of state t+1 (1 after a real done, else min(count + 1, 4): the count saturates at 4 whatever C is -- this entry
+ * point is not given C and serves the four-plane store, T + 4 frames per slot, that Runner._frame_store builds only for
+ * n_frame_stack == 4) into nvalid_rows[(slot0+b)*T + t+1] (not written when t == T-1) / nvalid_carry.
  * a2c_frames_to_states: the reference's fp32 `states` rows from the store, on demand: state k (< nt) of slot r (< R)
  * -> out + r*out_slot_stride + k*C*HW floats, valid-plane counts nvalid[r*nvalid_slot_stride + k] (NULL: all valid). */
 int a2c_frame_store_begin(uint8_t *frame_store, int64_t slot_stride, int64_t T, int C, int HW, int32_t *nvalid_rows,

@@ -1179,9 +1179,11 @@ class Runner:
         HBM-bound, and runs 10 % SLOWER from the uint8 store (1.41 vs 1.27 ms at N = 32 768: the uint8 -> fp32
         expansion sits in the commit phase all waves wait on) although it reads 4x fewer bytes.  Valid only while
         EVERY env step since start() went through the persistent kernel (it is the only writer): the first slot finds
-        frames[:, T+3] = the reset frame and one valid plane; any other rollout path switches the store off."""
+        frames[:, T+3] = the reset frame and one valid plane; any other rollout path switches the store off.
+        The store is four planes deep (T + 4 frames per slot, valid-plane counts saturating at 4 in
+        a2c_rollout_post_frames): any other n_frame_stack keeps the fp32 states."""
         on = os.environ.get("A2C_FRAME_STORE") == "1" or bool(try_key(self.hyps, "frame_store", False))
-        if not on or os.environ.get("A2C_NO_FRAME_STORE") == "1" or T < 4 or self.HW % 16 or \
+        if not on or os.environ.get("A2C_NO_FRAME_STORE") == "1" or T < 4 or self.HW % 16 or self.C != 4 or \
                 not self._fstore_ok:
             return None
         fs = self._fstore
