@@ -352,7 +352,12 @@ def test_gemm_f32(tA, tB, M, N, K):
 @pytest.mark.parametrize("M,N,K,sk", [(32, 2000, 28224, 32), (8, 1030, 4104, 5), (33, 1500, 4096, 7), (64, 2048, 2048, 2)])
 def test_gemm_skinny_stream(M, N, K, sk):
     """rollout-batch rows against a large k-contiguous weight matrix (ConvModel proj_matrx at n_envs = 32,
-    models.py:246-264): the LDS-free streaming split-K kernel, ragged M / N and a short last split"""
+    models.py:246-264), ragged M / N and a short last split.  Written for the LDS-free streaming split-K kernel; what serves
+    the cases today (tests/test_gemm_routes.py prints the table): (32, 2000, 28224) and (8, 1030, 4104) run on
+    gemm_nt_kernel<nt::Skinny> -- M <= 32 reaches skinny_stream_kernel<1, 4> only with A2C_NO_GEMM_NT=1, which this test does
+    not set, so A2C_NO_SKINNY_STREAM=1 changes nothing for them --, (33, 1500, 4096) on skinny_stream_kernel<2, 4> and, with
+    the switch, on gemm_kernel, and (64, 2048, 2048) on small_gemm_kernel<true, 8> both times (K <= 4096, fewer than 64 tiles
+    of 128 x 128).  The streaming kernels at their edges are in tests/test_gpu_gemm_routes.py."""
     ops = _ops()
     A, B = rnd((M, K), 90), rnd((N, K), 91)
     want = _gemm_ref(A, B, 0, 1)
@@ -439,7 +444,11 @@ def test_heads_fused_tail_samples_and_publishes(M, K, nslab, A):
 def test_gemm_rollout_batch_forward_against_long_k_contiguous_weights(M, monkeypatch):
     """64 < M <= 256 rows against a big k-contiguous weight matrix (ConvModel's resize_emb at the rollout batch of
     configs 4 / 5): the LDS-DMA kernel (gemm_nt_kernel: all rows in one tile, split K, ragged last column tile, K tail
-    shorter than a 32-deep tile) against fp64 and against the block-tiled kernel it replaces."""
+    shorter than a 32-deep tile) against fp64 and against the block-tiled kernel it replaces.  Which kernel serves which M
+    today (tests/test_gemm_routes.py prints the table): 7 and 32 gemm_nt_kernel<nt::Skinny>, 65, 100 and 256
+    gemm_nt_kernel<nt::Big>, every one at 73 K tiles per split; with A2C_NO_GEMM_NT=1 the comparison call runs on
+    skinny_stream_kernel<1, 4> for 7 and 32 (not on the block-tiled kernel) and on gemm_kernel for the rest.  Short rings and
+    short last splits are in tests/test_gpu_gemm_routes.py."""
     ops = _ops()
     N, K = 300, 14008                    # 3 column tiles (the last 44 wide); N * K >= 2^22; K % 32 == 24
     x = rnd((M, K + 4), 300).to(DEV)     # lda > K
