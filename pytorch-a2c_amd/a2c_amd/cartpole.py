@@ -33,7 +33,7 @@ Observation, 4 floats: the state ints times 2^-20, each exact in fp32 (|q| < 2^2
 import numpy as np
 
 from . import worlds
-from .worlds import DeviceWorldPool, HostWorld, _clamp, check_repeat, check_rules, factory_of
+from .worlds import DeviceLaneWorldPool, HostWorld, _clamp, check_repeat, factory_of
 
 N_ACTIONS = 2
 FRAC = 20
@@ -156,24 +156,14 @@ class CartPoleEnv(HostWorld):
 CartPoleFactory = factory_of(CartPoleEnv)
 
 
-class DeviceCartPolePool(DeviceWorldPool):
+class DeviceCartPolePool(DeviceLaneWorldPool):
     """``n_envs`` CartPole worlds in device memory (the Runner's device-pool protocol).  Env j is the world ``CartPoleEnv(seed,
     env_id=env_id0 + j, ...)``: same draws, same observations.  ``step`` / ``device_step`` take the address of env 0's int64
     action and the element stride between envs.  done == reset: real dones only."""
+    WHAT = "CartPole"
     frame_shape = (1, OBS)
 
     def __init__(self, n_envs, device="cuda", seed=0, max_episode_steps=500, env_id0=0, frame_skip=1, sticky_num=0,
                  sticky_den=1, frame_skip_max=None):
-        from . import ops
-        self.world = check_world(max_episode_steps)
-        self.repeat = check_repeat(frame_skip, sticky_num, sticky_den, "CartPole")
-        self.rules = ops.world_rules(*self.repeat, *check_rules(frame_skip, frame_skip_max, what="CartPole"), always=True)
-        super().__init__(n_envs, device, seed, env_id0, ops.cartpole_state_bytes() // 4)
-
-    def _reset(self):
-        from . import ops
-        ops.cartpole_reset(self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
-
-    def _step(self, head, out, frames, post, sl):
-        from . import ops
-        ops.cartpole_step(*head, *self.world, frames, self.HW, *out, self.rules, post, self.ep_stats[0:1], self.ep_stats[1:2])
+        super().__init__(n_envs, device, seed, env_id0, check_world(max_episode_steps), frame_skip, sticky_num, sticky_den,
+                         frame_skip_max)

@@ -43,7 +43,7 @@ fp32 (|int| <= 2^23) and identical on both sides."""
 import numpy as np
 
 from . import worlds
-from .worlds import DeviceWorldPool, HostWorld, _clamp, check_repeat, check_rules, factory_of
+from .worlds import DeviceLaneWorldPool, HostWorld, _clamp, check_repeat, factory_of
 
 ACTION_SIZE = 1
 FRAC = 20
@@ -195,33 +195,18 @@ class PendulumEnv(HostWorld):
 PendulumFactory = factory_of(PendulumEnv)
 
 
-class DevicePendulumPool(DeviceWorldPool):
+class DevicePendulumPool(DeviceLaneWorldPool):
     """``n_envs`` Pendulum worlds in device memory (the Runner's device-pool protocol).  Env j is the world ``PendulumEnv(seed,
     env_id=env_id0 + j, ...)``: same draws, same observations.  ``float_actions``: ``step`` / ``device_step`` take the address
     of env 0's ONE float32 action and the stride between envs IN FLOATS (a row of a continuous rollout buffer: >= 1), and
     ``action_shift`` is a float.  done == reset: real dones only.  ``episode_stats()`` is whole reward units: the sum of
     every closed episode's reward floored."""
+    WHAT = "Pendulum"
     frame_shape = (1, OBS)
     float_actions = True
     n_act = ACTION_SIZE
 
     def __init__(self, n_envs, device="cuda", seed=0, max_episode_steps=200, env_id0=0, frame_skip=1, sticky_num=0,
                  sticky_den=1, frame_skip_max=None):
-        from . import ops
-        self.world = check_world(max_episode_steps)
-        self.repeat = check_repeat(frame_skip, sticky_num, sticky_den, "Pendulum")
-        self.rules = ops.world_rules(*self.repeat, *check_rules(frame_skip, frame_skip_max, what="Pendulum"), always=True)
-        super().__init__(n_envs, device, seed, env_id0, ops.pendulum_state_bytes() // 4)
-        self.action_shift = 0.0
-
-    def start(self, runner):
-        super().start(runner)
-        self.action_shift = float(runner.hyps["action_shift"])      # (the base class keeps the int of the discrete worlds)
-
-    def _reset(self):
-        from . import ops
-        ops.pendulum_reset(self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
-
-    def _step(self, head, out, frames, post, sl):
-        from . import ops
-        ops.pendulum_step(*head, *self.world, frames, self.HW, *out, self.rules, post, self.ep_stats[0:1], self.ep_stats[1:2])
+        super().__init__(n_envs, device, seed, env_id0, check_world(max_episode_steps), frame_skip, sticky_num, sticky_den,
+                         frame_skip_max)

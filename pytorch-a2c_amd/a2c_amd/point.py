@@ -35,7 +35,7 @@ Observation, 8 floats, each an integer times a power of two, so exact in fp32 an
 import numpy as np
 
 from . import worlds
-from .worlds import DeviceWorldPool, HostWorld, _clamp, check_repeat, check_rules, factory_of
+from .worlds import DeviceLaneWorldPool, HostWorld, _clamp, check_repeat, factory_of
 
 ACTION_SIZE = 2
 P, VMAX, CELL, REACH_BONUS = 4096, 64, 64, 10
@@ -174,32 +174,17 @@ class PointEnv(HostWorld):
 PointFactory = factory_of(PointEnv)
 
 
-class DevicePointPool(DeviceWorldPool):
+class DevicePointPool(DeviceLaneWorldPool):
     """``n_envs`` Point worlds in device memory (the Runner's device-pool protocol).  Env j is the world ``PointEnv(seed,
     env_id=env_id0 + j, ...)``: same draws, same observations.  ``float_actions``: ``step`` / ``device_step`` take the address
     of env 0's two float32 actions and the stride between envs IN FLOATS (a row of a continuous rollout buffer), and
     ``action_shift`` is a float.  done == reset: real dones only."""
+    WHAT = "Point"
     frame_shape = (1, OBS)
     float_actions = True
     n_act = ACTION_SIZE
 
     def __init__(self, n_envs, device="cuda", seed=0, targets_to_win=3, max_episode_steps=1000, env_id0=0, frame_skip=1,
                  sticky_num=0, sticky_den=1, frame_skip_max=None):
-        from . import ops
-        self.world = check_world(targets_to_win, max_episode_steps)
-        self.repeat = check_repeat(frame_skip, sticky_num, sticky_den, "Point")
-        self.rules = ops.world_rules(*self.repeat, *check_rules(frame_skip, frame_skip_max, what="Point"), always=True)
-        super().__init__(n_envs, device, seed, env_id0, ops.point_state_bytes() // 4)
-        self.action_shift = 0.0
-
-    def start(self, runner):
-        super().start(runner)
-        self.action_shift = float(runner.hyps["action_shift"])      # (the base class keeps the int of the discrete worlds)
-
-    def _reset(self):
-        from . import ops
-        ops.point_reset(self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
-
-    def _step(self, head, out, frames, post, sl):
-        from . import ops
-        ops.point_step(*head, *self.world, frames, self.HW, *out, self.rules, post, self.ep_stats[0:1], self.ep_stats[1:2])
+        super().__init__(n_envs, device, seed, env_id0, check_world(targets_to_win, max_episode_steps), frame_skip, sticky_num,
+                         sticky_den, frame_skip_max)

@@ -1,7 +1,8 @@
 """What the worlds that can live in HBM (snake.py, pong.py, breakout.py) share on the Python side: the counter-based draws,
 the bounds of frame skip and sticky actions, ``HostWorld`` -- the agent step of the host twins ``PongEnv`` / ``BreakoutEnv`` --
 and ``DeviceWorldPool``, the Runner's device-pool protocol over ``n_envs`` worlds in device memory (the kernels' side:
-csrc/world.h)."""
+csrc/world.h), with ``DeviceLaneWorldPool``, what the pools of the one-lane-per-env worlds (point.py,
+cartpole.py, pendulum.py; csrc/lane_world.h) share beyond it."""
 import functools
 import math
 
@@ -283,3 +284,32 @@ class DeviceWorldPool:
         if n:
             self.ep_stats.zero_()
         return n, s
+
+
+class DeviceLaneWorldPool(DeviceWorldPool):
+    """The pools of the worlds where ONE LANE plays an env (csrc/lane_world.h: point.py, cartpole.py, pendulum.py), whose library
+    calls differ in their name and in the world's parameters alone.  A subclass sets ``WHAT`` (its name in messages; lower-cased,
+    the prefix of ``ops.<what>_state_bytes / _reset / _step``), ``frame_shape`` and, where the actions are float rows,
+    ``float_actions`` and ``n_act``; its ``__init__`` hands over its checked ``world`` tuple, the parameters in the order the
+    library takes them."""
+    WHAT = "World"
+
+    def __init__(self, n_envs, device, seed, env_id0, world, frame_skip, sticky_num, sticky_den, frame_skip_max):
+        from . import ops
+        self.world = world
+        self.repeat = check_repeat(frame_skip, sticky_num, sticky_den, self.WHAT)
+        self.rules = ops.world_rules(*self.repeat, *check_rules(frame_skip, frame_skip_max, what=self.WHAT), always=True)
+        self._op = {f: getattr(ops, f"{self.WHAT.lower()}_{f}") for f in ("state_bytes", "reset", "step")}
+        super().__init__(n_envs, device, seed, env_id0, self._op["state_bytes"]() // 4)
+        self._shift = float if getattr(self, "float_actions", False) else int
+        self.action_shift = self._shift(0)
+
+    def start(self, runner):
+        super().start(runner)
+        self.action_shift = self._shift(runner.hyps["action_shift"])      # (the base class keeps the int of the discrete worlds)
+
+    def _reset(self):
+        self._op["reset"](self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
+
+    def _step(self, head, out, frames, post, sl):
+        self._op["step"](*head, *self.world, frames, self.HW, *out, self.rules, post, self.ep_stats[0:1], self.ep_stats[1:2])

@@ -3,7 +3,7 @@
 // and Euler order; every value is an integer of ONE format, every product is followed by an arithmetic right shift (a
 // floor), sin and cos are short polynomials, and the one division is a floor division written out (DESIGN.md section 6k
 // lists every intermediate with its bound: none reaches 2^50; host twin: a2c_amd/cartpole.py, same integers).
-// The observation is 4 floats, so cartpole.hip brings kernels of its own: one LANE per env.
+// The observation is 4 floats, so the kernels are lane_world.h's: one LANE per env.
 #pragma once
 #include "world.h"
 

@@ -5,7 +5,7 @@
 // nested-ratio polynomials after a reflection to |x| <= pi / 2, and there is no division (DESIGN.md section 6l bounds every
 // intermediate: none reaches 2^49; host twin: a2c_amd/pendulum.py, same integers).
 // The int reward of a frame is in units of 2^-8: what leaves the kernel as a float is that int times 2^-8, exact.
-// The observation is 4 floats, so pendulum.hip brings kernels of its own: one LANE per env.
+// The observation is 4 floats, so the kernels are lane_world.h's: one LANE per env.
 #pragma once
 #include "world.h"
 

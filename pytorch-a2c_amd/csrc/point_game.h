@@ -1,7 +1,7 @@
 // The Point game of point.hip: PointGame, a point mass chasing targets on a 4096 x 4096 integer field, as the game type G of
 // world.h's agent step (world_agent_step<G>: World, Params, frame, closes), and the quantiser that turns the two float
 // actions of a Gaussian net into the ONE int the agent step carries (host twin: a2c_amd/point.py).
-// The observation is 8 floats, not a picture, so point.hip brings kernels of its own: one LANE per env.
+// The observation is 8 floats, not a picture, so the kernels are lane_world.h's: one LANE per env.
 #pragma once
 #include "world.h"
 
