@@ -1208,6 +1208,55 @@ int a2c_pendulum_step(int32_t *state, const float *actions, int64_t act_ld, floa
                       float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_rules *rules,
                       const a2c_world_post *post, a2c_stream_t stream);
 
+/* ------------------------------------------------------------------ time-limit truncation on the lane worlds
+ * An episode that ends because ep_steps reached max_episode_steps, and for no reason of the game's own, was cut short, not
+ * lost: its targets bootstrap from the value of the state it ended in (hyps["bootstrap_truncated"]).  That state is gone
+ * when the launch returns (the world restarts inside it), so the step reports it:
+ * a2c_<world>_step_trunc(<the arguments of a2c_<world>_step, rules and post included>, tr, stream) is a2c_<world>_step --
+ * every output of that entry point bit-identical: state words, obs, rew, done, reset, the counters, the post block's
+ * bookkeeping, hidden rows and frame stack -- and for env b
+ *   trunc[b * trunc_stride] = 1 when the agent step ended an episode at a game frame where ep_steps >= max_episode_steps held
+ *     and the game's own end condition did not (CartPole: x or theta out of range; Point: targets_to_win reached; Pendulum
+ *     has none), else 0.  Both at the same frame is a terminal end: 0.  With frame skip and sticky actions the frame that
+ *     ends the episode decides.
+ *   final_obs[b * final_ld + 0 .. HW-1] = the observation of the world as it stood after that frame's physics and before the
+ *     restart; where the step ended no episode, the step's own observation.  Every row is written at every launch.
+ * A2C_ERR_ARG without a launch: what a2c_<world>_step rejects, a NULL tr / trunc / final_obs, trunc_stride < 1, final_obs
+ * not 16-byte aligned, final_ld < HW or not a multiple of 4.                                                               */
+typedef struct {
+  float *trunc;                /* B floats, trunc_stride floats apart (a row of the rollout buffer: stride T)        */
+  int64_t trunc_stride;
+  float *final_obs;            /* B rows of HW floats, final_ld floats apart                                          */
+  int64_t final_ld;
+} a2c_world_trunc;
+
+int a2c_point_step_trunc(int32_t *state, const float *actions, int64_t act_ld, float action_shift, int B, int env_id0,
+                         uint32_t seed, int targets_to_win, int max_episode_steps, float *obs, int64_t obs_ld, float *rew,
+                         float *done, float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_rules *rules,
+                         const a2c_world_post *post, const a2c_world_trunc *tr, a2c_stream_t stream);
+int a2c_cartpole_step_trunc(int32_t *state, const int64_t *actions, int64_t act_stride, int action_shift, int B, int env_id0,
+                            uint32_t seed, int max_episode_steps, float *obs, int64_t obs_ld, float *rew, float *done,
+                            float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_rules *rules,
+                            const a2c_world_post *post, const a2c_world_trunc *tr, a2c_stream_t stream);
+int a2c_pendulum_step_trunc(int32_t *state, const float *actions, int64_t act_ld, float action_shift, int B, int env_id0,
+                            uint32_t seed, int max_episode_steps, float *obs, int64_t obs_ld, float *rew, float *done,
+                            float *reset, int32_t *ep_count, int32_t *ep_rew_sum, const a2c_world_rules *rules,
+                            const a2c_world_post *post, const a2c_world_trunc *tr, a2c_stream_t stream);
+/* the state the net would have seen next had the episode not restarted, for every row of a rollout buffer:
+ * out[e] = [planes 1 .. C-1 of states[e], final_obs[e]], rows of C * HW (states, out) and HW (final_obs) floats, dense, as
+ * 16-byte accesses.  N == 0 is a no-op.  A2C_ERR_ARG without a launch: N < 0, C < 1, HW < 4 or not a multiple of 4, a NULL
+ * or not 16-byte aligned pointer, out == states.                                                                          */
+int a2c_final_states(const float *states, const float *final_obs, int C, int HW, int64_t N, float *out, a2c_stream_t stream);
+/* the correction of a truncated step's targets, for both arrays x = rewards, deltas:
+ *   t = gamma * truncs[e];  x_out[e] = (t != 0) ? x[e] + t * vfin[e] : x[e]
+ * in fp32, the product gamma * truncs first, then t * vfin, then the sum, every operation rounded (no FMA): the NumPy
+ * statement np.where(t != 0, x + t * vfin, x) over float32 arrays with t = np.float32(gamma) * truncs gives the same bits.
+ * A row that was not truncated passes through untouched, whatever vfin[e] holds.  The scans cut at done, so adding
+ * gamma * V(final state) to the reward and to the delta of the closing step corrects the discounted return and the GAE
+ * advantage alike.  x_out may be x.  N == 0 is a no-op.  A2C_ERR_ARG without a launch: N < 0 or a NULL pointer.            */
+int a2c_trunc_bootstrap(const float *rewards, const float *deltas, const float *truncs, const float *vfin, float gamma,
+                        int64_t N, float *rewards_out, float *deltas_out, a2c_stream_t stream);
+
 /* ------------------------------------------------------------------ running observation / reward normalisation (csrc/vecnorm.hip)
  * What baselines' VecNormalize does between a vector world and the agent (host twin
  * a2c_amd/vecnorm.py): running mean and variance of the observations and of the discounted return, observations centred and

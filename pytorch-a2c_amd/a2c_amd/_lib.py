@@ -66,6 +66,11 @@ class WorldRules(Structure):
                 ("episodic_life", c_int32), ("clip_rewards", c_int32)]
 
 
+class WorldTrunc(Structure):
+    """a2c_world_trunc"""
+    _fields_ = [("trunc", P), ("trunc_stride", c_int64), ("final_obs", P), ("final_ld", c_int64)]
+
+
 class VecNormArgs(Structure):
     """a2c_vecnorm_args"""
     _fields_ = [("B", c_int32), ("env0", c_int32), ("B_pool", c_int32), ("L", c_int32), ("C", c_int32), ("update", c_int32),
@@ -78,6 +83,7 @@ PR = POINTER(A3CRolloutArgs)
 PW = POINTER(WorldPost)
 PU = POINTER(WorldRules)
 PV = POINTER(VecNormArgs)
+PT = POINTER(WorldTrunc)
 
 # name -> (restype, argtypes); one entry per prototype in include/a2c_mi355x.h
 SIGNATURES = {
@@ -254,6 +260,14 @@ SIGNATURES = {
     "a2c_pendulum_state_bytes": (c_size_t, []),
     "a2c_pendulum_reset": (c_int, [P, c_int, c_int, c_uint32, c_int, P, c_int64, P]),
     "a2c_pendulum_step": (c_int, [P, P, c_int64, c_float, c_int, c_int, c_uint32, c_int, P, c_int64, P, P, P, P, P, PU, PW, P]),
+    "a2c_point_step_trunc": (c_int, [P, P, c_int64, c_float, c_int, c_int, c_uint32, c_int, c_int, P, c_int64, P, P, P, P, P, PU, PW,
+                                     PT, P]),
+    "a2c_cartpole_step_trunc": (c_int, [P, P, c_int64, c_int, c_int, c_int, c_uint32, c_int, P, c_int64, P, P, P, P, P, PU, PW, PT,
+                                        P]),
+    "a2c_pendulum_step_trunc": (c_int, [P, P, c_int64, c_float, c_int, c_int, c_uint32, c_int, P, c_int64, P, P, P, P, P, PU, PW,
+                                        PT, P]),
+    "a2c_final_states": (c_int, [P, P, c_int, c_int, c_int64, P, P]),
+    "a2c_trunc_bootstrap": (c_int, [P, P, P, P, c_float, c_int64, P, P, P]),
     "a2c_vecnorm_state_bytes": (c_size_t, [c_int, c_int]),
     "a2c_vecnorm_init": (c_int, [P, c_int, c_int, P]),
     "a2c_vecnorm_step": (c_int, [P, PV, P]),

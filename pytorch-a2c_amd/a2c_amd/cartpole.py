@@ -33,7 +33,7 @@ Observation, 4 floats: the state ints times 2^-20, each exact in fp32 (|q| < 2^2
 import numpy as np
 
 from . import worlds
-from .worlds import DeviceLaneWorldPool, HostWorld, _clamp, check_repeat, factory_of
+from .worlds import DeviceLaneWorldPool, LaneHostWorld, _clamp, check_repeat, factory_of
 
 N_ACTIONS = 2
 FRAC = 20
@@ -111,12 +111,12 @@ class _Discrete:
     n = N_ACTIONS
 
 
-class CartPoleEnv(HostWorld):
+class CartPoleEnv(LaneHostWorld):
     """One CartPole world on the host.  ``reset()`` -> the (1, 4) float32 observation; ``step(a)`` -> (observation, reward,
     done, info), ``a`` an int (the caller has added its ``action_shift``), taken mod 2.  Like a gym env it does not reset
     itself.  ``events`` counts the episode ends by cause, ``x_limit`` / ``theta_limit`` / ``step_limit`` (the first that holds,
     in this order), and ``episode_end`` (with frame skip or sticky actions also ``cut`` and ``sticky``, as the Pong twin) for
-    tests that must see every rule at work."""
+    tests that must see every rule at work.  ``truncated`` / ``final_obs``: ``worlds.LaneHostWorld``."""
     WHAT, N_ACTIONS = "CartPole", N_ACTIONS
     action_space = _Discrete()
 
@@ -141,6 +141,7 @@ class CartPoleEnv(HostWorld):
                  "step_limit" if self.ep_steps >= self.max_episode_steps else None)
         if cause is not None:
             self.over = True
+            self.limit_alone = cause == "step_limit"
             self.events[cause] += 1
             self.events["episode_end"] += 1
         return 1.0, cause is not None

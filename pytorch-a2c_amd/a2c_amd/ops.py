@@ -1522,6 +1522,69 @@ def pendulum_step(state, actions_ptr, act_ld, action_shift, B, env_id0, seed, ma
                                   _post_ref(rules), _post_ref(post), _st(st)), "a2c_pendulum_step")
 
 
+# ---------------------------------------------------------------- time-limit truncation on the lane worlds
+def world_trunc(trunc_ptr, trunc_stride, final_obs_ptr, final_ld):
+    """the a2c_world_trunc block of a2c_<world>_step_trunc: addresses of env 0's ``truncs`` float and ``final_obs`` row, and the
+    floats between envs (rows of the rollout buffer: T and T * HW)"""
+    return _lib.WorldTrunc(trunc=trunc_ptr, trunc_stride=trunc_stride, final_obs=final_obs_ptr, final_ld=final_ld)
+
+
+def point_step_trunc(state, actions_ptr, act_ld, action_shift, B, env_id0, seed, targets_to_win, max_episode_steps, obs, obs_ld,
+                     rew, done, reset, tr, rules=None, post=None, ep_count=None, ep_rew_sum=None, st=None):
+    """point_step + ``tr``, a ``world_trunc`` block: did the step limit alone end the episode, and the observation it ended in"""
+    _chk_world(state, obs, rew, done, reset, ep_count, ep_rew_sum)
+    check(lib().a2c_point_step_trunc(_p(state), actions_ptr, act_ld, float(action_shift), B, env_id0, seed, targets_to_win,
+                                     max_episode_steps, _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
+                                     _p(ep_rew_sum), _post_ref(rules), _post_ref(post), _post_ref(tr), _st(st)),
+          "a2c_point_step_trunc")
+
+
+def cartpole_step_trunc(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, max_episode_steps, obs, obs_ld, rew,
+                        done, reset, tr, rules=None, post=None, ep_count=None, ep_rew_sum=None, st=None):
+    """cartpole_step + ``tr``, a ``world_trunc`` block"""
+    _chk_world(state, obs, rew, done, reset, ep_count, ep_rew_sum)
+    check(lib().a2c_cartpole_step_trunc(_p(state), actions_ptr, act_stride, int(action_shift), B, env_id0, seed,
+                                        max_episode_steps, _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
+                                        _p(ep_rew_sum), _post_ref(rules), _post_ref(post), _post_ref(tr), _st(st)),
+          "a2c_cartpole_step_trunc")
+
+
+def pendulum_step_trunc(state, actions_ptr, act_ld, action_shift, B, env_id0, seed, max_episode_steps, obs, obs_ld, rew, done,
+                        reset, tr, rules=None, post=None, ep_count=None, ep_rew_sum=None, st=None):
+    """pendulum_step + ``tr``, a ``world_trunc`` block"""
+    _chk_world(state, obs, rew, done, reset, ep_count, ep_rew_sum)
+    check(lib().a2c_pendulum_step_trunc(_p(state), actions_ptr, act_ld, float(action_shift), B, env_id0, seed,
+                                        max_episode_steps, _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
+                                        _p(ep_rew_sum), _post_ref(rules), _post_ref(post), _post_ref(tr), _st(st)),
+          "a2c_pendulum_step_trunc")
+
+
+def final_states(states, final_obs, C, HW, N, out, st=None):
+    """out[e] = [planes 1 .. C-1 of states[e], final_obs[e]]: the state the net would have seen next had the episode of row e
+    not restarted (dense rows)"""
+    _chk(states, "states"); _chk(final_obs, "final_obs"); _chk(out, "out")
+    check(lib().a2c_final_states(_p(states), _p(final_obs), C, HW, N, _p(out), _st(st)), "a2c_final_states")
+
+
+def trunc_bootstrap(rewards, deltas, truncs, vfin, gamma, N, rewards_out, deltas_out, st=None):
+    """x_out = x + (gamma * truncs) * vfin for x = rewards, deltas; untouched where gamma * truncs == 0 (the op order: the
+    header's, ``trunc_bootstrap_host`` below)"""
+    for n, t in (("rewards", rewards), ("deltas", deltas), ("truncs", truncs), ("vfin", vfin), ("rewards_out", rewards_out),
+                 ("deltas_out", deltas_out)):
+        _chk(t, n)
+    check(lib().a2c_trunc_bootstrap(_p(rewards), _p(deltas), _p(truncs), _p(vfin), float(gamma), N, _p(rewards_out),
+                                    _p(deltas_out), _st(st)), "a2c_trunc_bootstrap")
+
+
+def trunc_bootstrap_host(x, truncs, vfin, gamma):
+    """the fp32 host statement of a2c_trunc_bootstrap for one array (NumPy float32, every operation rounded): bit for bit
+    what the kernel writes"""
+    x, truncs, vfin = (np.asarray(v, dtype=np.float32) for v in (x, truncs, vfin))
+    t = np.float32(gamma) * truncs
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.where(t != 0, x + t * vfin, x).astype(np.float32)
+
+
 # ---------------------------------------------------------------- running normalisation (csrc/vecnorm.hip)
 def vecnorm_state_doubles(L, B_pool):
     """doubles of the state block of a2c_vecnorm_step; raises for an L outside 1..64 or an empty pool"""

@@ -43,7 +43,7 @@ fp32 (|int| <= 2^23) and identical on both sides."""
 import numpy as np
 
 from . import worlds
-from .worlds import DeviceLaneWorldPool, HostWorld, _clamp, check_repeat, factory_of
+from .worlds import DeviceLaneWorldPool, LaneHostWorld, _clamp, check_repeat, factory_of
 
 ACTION_SIZE = 1
 FRAC = 20
@@ -144,12 +144,12 @@ class _Box:
     low, high = -MAX_TORQUE, MAX_TORQUE
 
 
-class PendulumEnv(HostWorld):
+class PendulumEnv(LaneHostWorld):
     """One Pendulum world on the host.  ``reset()`` -> the (1, 4) float32 observation; ``step(a)`` -> (observation, reward,
     done, info), ``a`` one float (the caller has added its ``action_shift``).  Like a gym env it does not reset itself.
     ``events`` counts the wraps of th by side (``wrap_pos``: past PI), the frames whose speed was clamped and the episode ends
     (``end_cap``: the only kind; with frame skip or sticky actions also ``cut`` and ``sticky``, as the Pong twin) for tests
-    that must see every rule at work."""
+    that must see every rule at work.  ``truncated`` / ``final_obs``: ``worlds.LaneHostWorld`` (every end is truncated)."""
     WHAT = "Pendulum"
     action_space = _Box()
 
@@ -180,6 +180,7 @@ class PendulumEnv(HostWorld):
         done = self.ep_steps >= self.max_episode_steps
         if done:
             self.over = True
+            self.limit_alone = True
             self.events["end_cap"] += 1
         return -(cost >> REW_SHIFT) * REW_UNIT, done
 

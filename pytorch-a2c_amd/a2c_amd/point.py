@@ -35,7 +35,7 @@ Observation, 8 floats, each an integer times a power of two, so exact in fp32 an
 import numpy as np
 
 from . import worlds
-from .worlds import DeviceLaneWorldPool, HostWorld, _clamp, check_repeat, factory_of
+from .worlds import DeviceLaneWorldPool, LaneHostWorld, _clamp, check_repeat, factory_of
 
 ACTION_SIZE = 2
 P, VMAX, CELL, REACH_BONUS = 4096, 64, 64, 10
@@ -98,11 +98,12 @@ class _Box:
     low, high = -1.0, 1.0
 
 
-class PointEnv(HostWorld):
+class PointEnv(LaneHostWorld):
     """One Point world on the host.  ``reset()`` -> the (1, 8) float32 observation; ``step(a)`` -> (observation, reward,
     done, info), ``a`` two floats (the caller has added its ``action_shift``).  Like a gym env it does not reset itself.
     ``events`` counts wall hits, targets reached and episode ends by targets / by the step cap (with frame skip or sticky
-    actions also ``cut`` and ``sticky``, as the Pong twin) for tests that must see every rule at work."""
+    actions also ``cut`` and ``sticky``, as the Pong twin) for tests that must see every rule at work.  ``truncated`` /
+    ``final_obs``: ``worlds.LaneHostWorld``."""
     WHAT = "Point"
     action_space = _Box()
 
@@ -156,6 +157,7 @@ class PointEnv(HostWorld):
         done = self.got >= self.targets_to_win or self.ep_steps >= self.max_episode_steps
         if done:
             self.over = True
+            self.limit_alone = self.got < self.targets_to_win
             self.events["end_targets" if self.got >= self.targets_to_win else "end_cap"] += 1
         elif d1 == 0:
             self.tx, self.ty = place(self._draw())

@@ -160,6 +160,32 @@ def host_env_step(pool, env0, B, np_act, np_frames, np_rew, np_done, ep_rew, rew
         np_rew[j], np_done[j] = rew, float(reset)
 
 
+def check_bootstrap_truncated(hyps, pool=None, net=None, datas=None, HW=None):
+    """what hyps['bootstrap_truncated'] = True refuses, each with a ValueError naming the key; every
+    argument is optional, so train() asks before anything is allocated and the Runner again with what it was handed.  The
+    lane worlds' device pools (``reports_trunc``) and FCModel only: a recurrent net would need the hidden row the post step
+    zeroes, a picture world a second rendered frame per close, and the host pools carry no such field"""
+    key = "bootstrap_truncated"
+    env_type = hyps.get("env_type")
+    if pool is None:
+        if env_type not in ("Point-device", "CartPole-device", "Pendulum-device"):
+            raise ValueError(f"a2c_amd: {key} bootstraps time-limit episode ends of the lane worlds' device pools (env_type "
+                             f"'Point-device', 'CartPole-device', 'Pendulum-device'), not {env_type!r}")
+    elif not getattr(pool, "reports_trunc", False):
+        raise ValueError(f"a2c_amd: {key} needs a device env pool whose step reports the state an episode ended in "
+                         f"(DevicePointPool, DeviceCartPolePool, DevicePendulumPool), not {type(pool).__name__}")
+    model = type(net).__name__ if net is not None else hyps.get("model")
+    if model is not None and model != "FCModel":
+        raise ValueError(f"a2c_amd: {key} covers FCModel (the hidden row a recurrent net's final state needs is zeroed before "
+                         f"anyone can read it), not {model}")
+    if datas is not None:
+        n = datas["rewards"].numel()
+        for name, shape in (("truncs", (n,)), ("final_obs", (n, HW))):
+            t = datas.get(name)
+            if t is None or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda:
+                raise ValueError(f"a2c_amd: {key} needs shared_data[{name!r}], a float32 device tensor of shape {shape}")
+
+
 def play_graph(cache, key, body):
     """The one graph state machine of the rollout paths.  ``body()`` only enqueues.  First call of ``key``: ``body()`` runs
     eagerly (the conv tile tuners measure on eager calls) and the key is "warm"; second call: captured into a
@@ -231,6 +257,14 @@ class _Slot:
         hd = self.h.shape[1]
         return self.r.datas["h_states"].data_ptr() + 4 * (self.slot0 * self.T + t) * hd, self.T * hd
 
+    def trunc(self, t):
+        """the ``ops.world_trunc`` block of env step t under hyps bootstrap_truncated: row
+        slot0 * T + t of datas['truncs'] / datas['final_obs'], the B slots' rows T and T * HW floats apart; else None"""
+        if not self.r.trunc:
+            return None
+        D, HW, e = self.r.datas, self.r.HW, self.slot0 * self.T + t
+        return ops.world_trunc(D["truncs"].data_ptr() + 4 * e, self.T, D["final_obs"].data_ptr() + 4 * e * HW, self.T * HW)
+
     def acts_to_host_out(self, t, src):
         """a host `actions` tensor like the reference's: step t's rows of the B slots"""
         if self.acts_host_out is not None:
@@ -257,6 +291,7 @@ class Runner:
         # what that rollout stashed in the net for the update alone; bootstrap=False leaves the last step's rewards / dones
         # rows as the env returned them (no runner.py:236-245) -- device pools with ``device_step_post`` only
         self.stash, self.bootstrap = bool(stash), bool(bootstrap)
+        self.trunc = False                    # hyps bootstrap_truncated, once start() has checked it
         self.gate_q, self.stop_q, self.rew_q = gate_q, stop_q, rew_q
         self.obs_deque = deque(maxlen=hyps["n_frame_stack"])     # kept for API parity (single-env helpers)
         self.env_pool = env_pool
@@ -356,6 +391,11 @@ class Runner:
         if self.float_pool and int(pool.n_act) != self.n_act:
             raise ValueError(f"a2c_amd.Runner: the device env pool takes {int(pool.n_act)} float actions, the net has "
                              f"{self.n_act}")
+        # time-limit truncation (hyps bootstrap_truncated): the lane worlds' step also writes row t of
+        # datas['truncs'] / datas['final_obs'] for the update.  An evaluation's Runner (bootstrap=False) never asks
+        self.trunc = bool(try_key(hyps, "bootstrap_truncated", False)) and self.bootstrap
+        if self.trunc:
+            check_bootstrap_truncated(hyps, pool=pool, net=net, datas=self.datas, HW=self.HW)
         f32 = dict(dtype=torch.float32, device=dev)
         self.bookmark = torch.zeros((B, self.S), **f32)                  # state_bookmark of every env
         self.val_prev = torch.zeros(B, **f32)
@@ -685,7 +725,7 @@ class Runner:
         if hasattr(net, "_set_rollout_batch"):
             net._set_rollout_batch(B)
         net._refresh(st)
-        for name in ("states", "rewards", "dones", "deltas"):
+        for name in ("states", "rewards", "dones", "deltas") + (("truncs", "final_obs") if self.trunc else ()):
             ops._chk(D[name], name)
         c = _Slot(self, net, slot0, env0, B, hyps)
         self._stash_used = False
@@ -825,7 +865,7 @@ class Runner:
             post = ops.world_post(vals.data_ptr(), vals.stride(0), c.val_prev, rewards, dones, deltas, T, t, slot0, c.gamma,
                                   c.pong, c.sp(t), T * S, nxt_ptr, nxt_stride, self.C,
                                   done_eff=None if h is None else c.done_eff, h=h)
-            pool.device_step_post(t, env0, B, (a_ptr, a_stride), post)
+            pool.device_step_post(t, env0, B, (a_ptr, a_stride), post, **(dict(trunc=c.trunc(t)) if self.trunc else {}))
             self._norm_step(c, t, st)
         if self.bootstrap:
             self._bootstrap(c, st)
@@ -1203,7 +1243,8 @@ class Runner:
         pool, env0, B = self.env_pool, c.env0, c.B
         if self.device_pool:
             if getattr(pool, "needs_actions", False):      # an action-driven world: where the sampler wrote this step's actions
-                frames, rew, done, reset = pool.device_step(t, env0, B, actions=(a_ptr, a_stride))
+                kw = dict(trunc=c.trunc(t)) if self.trunc else {}
+                frames, rew, done, reset = pool.device_step(t, env0, B, actions=(a_ptr, a_stride), **kw)
                 if c.acts_host_out is not None:            # a host `actions` tensor like the reference's: one D2H per step
                     c.acts_to_host_out(t, c.act.cpu())
             else:
@@ -1470,6 +1511,7 @@ class DeviceStatsRunner:
         self.hyps = dict(hyps, n_envs=self.E, n_rollouts=self.E, n_tsteps=self.K)
         self._norm_obs = bool(self.hyps.pop("norm_obs", False))
         self.hyps.pop("norm_rewards", None)
+        self.hyps.pop("bootstrap_truncated", None)      # (a key of the training targets: an evaluation has none)
         self.calls, self.last = 0, None
         self.runner = self.datas = None
         self._chunk = 0

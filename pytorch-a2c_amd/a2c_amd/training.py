@@ -22,7 +22,8 @@ import numpy as np
 import torch
 
 from . import breakout, cartpole, models, pendulum, point, pong, preprocessing, snake, vecnorm, worlds
-from .runner import DeviceStatsRunner, HostEnvPool, Runner, SequentialEnvironment, StatsRunner
+from .runner import (DeviceStatsRunner, HostEnvPool, Runner, SequentialEnvironment, StatsRunner,
+                     check_bootstrap_truncated)
 from .updater import Updater, gauss_loss_mode
 from .utils import cuda_if, deque_maxmin, try_key
 
@@ -30,7 +31,7 @@ DEFAULTS = dict(n_frame_stack=4, n_rollouts=None, n_past_rews=25, h_size=256, lr
                 gamma=.99, gamma_high=.995, val_coef=.5, entr_coef=.005, entr_coef_low=.001, pi_coef=1.0, max_norm=.5,
                 resume=False, render=False, decay_lr=False, decay_entr=False, use_nstep_rets=False, norm_advs=True,
                 use_bnorm=False, use_bptt=False, optim_type="RMSprop", n_test_eps=15, max_tsteps=4e7,
-                gauss_loss="reference")
+                gauss_loss="reference", bootstrap_truncated=False)
 
 
 def get_exp_num(main_path, exp_name):
@@ -159,6 +160,12 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     ``"exact"`` (the per-sample Gaussian log-likelihood loss with an entropy bonus, one launch per update), for continuous
     action spaces only (anything else is a ValueError naming the key); it changes the update alone, not the rollout, the
     sampling or the evaluation.
+    ``hyps["bootstrap_truncated"]`` (default False: everything as it was): an episode that ends by
+    ``max_episode_steps`` alone is cut short, not lost, so the targets of its closing step use r + gamma * V(the state it ended
+    in) instead of r.  The lane worlds' step reports that state (a2c_<world>_step_trunc into ``truncs`` / ``final_obs`` of the
+    rollout buffer) and the update adds gamma * V of it to the step's reward and delta before the scan.  "Point-device",
+    "CartPole-device" and "Pendulum-device" with FCModel only (anything else -- GRUFCModel, the picture worlds, the ``-host``
+    env types, gym envs, an ``env_fn`` -- is a ValueError naming the key, before anything is written); evaluation is untouched.
     Returns the best evaluation reward."""
     hyps = dict(DEFAULTS, **hyps)
     # gauss_loss (DESIGN.md section 6n): refused here, before anything is written or allocated, for a value that is neither
@@ -167,6 +174,13 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     world_family = _world_family(hyps.get("env_type")) if env_fn is None else None
     gauss_loss_mode(hyps, (not _float_family(world_family)) if world_family is not None else
                     (bool(try_key(hyps, "is_discrete", True)) if env_fn is not None else None))
+    # bootstrap_truncated: refused here, before anything is written or allocated, for everything but the
+    # lane worlds' device pools under FCModel
+    if try_key(hyps, "bootstrap_truncated", False):
+        if env_fn is not None:
+            raise ValueError("a2c_amd: bootstrap_truncated bootstraps time-limit episode ends of the lane worlds' device pools, "
+                             "not an env_fn's envs")
+        check_bootstrap_truncated(hyps)
     eval_pool = try_key(hyps, "eval_pool", None) or "host"
     if eval_pool not in ("host", "device"):
         raise ValueError(f"a2c_amd: hyps['eval_pool'] is 'host' or 'device', not {eval_pool!r}")
@@ -348,6 +362,9 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                    "dones": cuda_if(torch.zeros(shared_len))}
     if net.is_recurrent:
         shared_data["h_states"] = cuda_if(torch.zeros(shared_len, net.h_size))
+    if try_key(hyps, "bootstrap_truncated", False):      # (section 6o: indexed like rewards; one observation per row)
+        shared_data["truncs"] = cuda_if(torch.zeros(shared_len))
+        shared_data["final_obs"] = cuda_if(torch.zeros((shared_len, int(np.prod(pool.frame_shape)))))
     n_rollouts = hyps["n_rollouts"]
     gate_q, stop_q, reward_q = queue.Queue(n_rollouts), queue.Queue(n_rollouts), queue.Queue(1)
     reward_q.put(-1)
@@ -373,6 +390,7 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
                 raise RuntimeError("the rollout thread failed") from runner.error
             return tok
     updater = Updater(net, hyps)
+    updater.vecnorm = eval_norm      # (bootstrap_truncated under norm_obs: the final states pass through the Runner's block)
     if hyps["resume"]:
         updater.optim.load_state_dict(torch.load(optim_save_file))
     for i in range(n_rollouts):

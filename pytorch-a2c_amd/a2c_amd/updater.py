@@ -5,6 +5,7 @@ is_discrete ret_mean ret_std`` (updater.py:9-229).
 
 One ``update_model`` call enqueues, on one HIP stream and without host round trips until the
 final read-back of five scalars:
+  [hyps["bootstrap_truncated"]: final states -> critic forward -> a2c_trunc_bootstrap ->]
   fused GAE + returns scan -> model forward (N = n_rollouts*n_tsteps samples, or the BPTT unroll)
   -> advantage statistics -> fused loss forward+backward (continuous actions: Gaussian loss sums [-> all-reduce] ->
   Gaussian loss forward+backward; with hyps["gauss_loss"] = "exact" ONE launch, the per-sample Gaussian log-likelihood
@@ -169,6 +170,14 @@ class Updater:
         if bool(self.is_discrete) != bool(getattr(net, "is_discrete", True)):
             raise ValueError("a2c_amd: hyps['is_discrete'] does not match the net's is_discrete")
         self.gauss_loss = gauss_loss_mode(hyps, self.is_discrete)
+        # time-limit truncation: the targets of a step whose episode the step limit alone ended
+        # bootstrap from V(final state).  vecnorm: under hyps norm_obs the Runner's DeviceVecNorm (or a callable returning it;
+        # train() sets it), whose apply-only path the final states pass through
+        self.trunc = bool(try_key(hyps, "bootstrap_truncated", False))
+        self.vecnorm = None
+        if self.trunc and type(net).__name__ != "FCModel":
+            raise ValueError("a2c_amd: bootstrap_truncated covers FCModel (the hidden row a recurrent net's final state needs "
+                             f"is zeroed before anyone can read it), not {type(net).__name__}")
         self.shard = shard if shard is not None else Shard()
         self.optim = self.new_optim(hyps["lr"])
         self.info = {}
@@ -197,6 +206,11 @@ class Updater:
                      err=torch.zeros(1, dtype=torch.int32, device=dev),
                      out5=torch.zeros(5, dtype=torch.float64, device=dev),
                      host=torch.zeros(8, dtype=torch.float64).pin_memory() if torch.cuda.is_available() else None)
+            if self.trunc:
+                # the final states (filled in _bootstrap_truncated, where their row length is known), V of them, and the
+                # corrected rewards / deltas: the Updater's own, shared_data is never written
+                b.update(fin=None, vfin=torch.zeros(N, device=dev), rewards_tb=torch.empty(N, device=dev),
+                         deltas_tb=torch.empty(N, device=dev))
             if not self.is_discrete and self.gauss_loss == "reference":
                 # the six Gaussian loss sums (a2c_gauss_loss_sums), all-reduced when sharded
                 b["gsums"] = torch.zeros(6, dtype=torch.float64, device=dev)
@@ -242,6 +256,9 @@ class Updater:
                       shared_data.get("h_states") if recurrent_key(shared_data) else None, *[v for v in b.values() if torch.is_tensor(v)]):
                 if t is not None and t.is_cuda:
                     ops.note_tensor(t)
+
+        if self.trunc:
+            rewards, deltas = self._bootstrap_truncated(shared_data, states, rewards, deltas, N, b, st)
 
         # advantages (gamma*lambda) and discounted returns (gamma) in one pass (updater.py:70-71, 86-88)
         with ops.span("gae_returns_scan"):
@@ -319,6 +336,39 @@ class Updater:
         ops.check(ops.lib().a2c_pack_update_scalars(stats[2:5].data_ptr(), self.optim.grad_norm().data_ptr(),
                                                     b["err"].data_ptr(), b["out5"].data_ptr(), st), "a2c_pack_update_scalars")
         return b["out5"], n_global
+
+    def _bootstrap_truncated(self, shared_data, states, rewards, deltas, N, b, st):
+        """hyps["bootstrap_truncated"], all on the update's stream, before the scan: the state every
+        row's episode would have gone on from (a2c_final_states), under norm_obs through the normaliser's apply-only path --
+        the block AS IT STANDS AT UPDATE TIME, not as it stood at step t: what evaluation does --, one forward through a
+        workspace of its own ("vfin": the "train" forward that follows is not disturbed) for V of them, and
+        a2c_trunc_bootstrap: rewards / deltas + gamma * truncs * V into this Updater's buffers -> (rewards, deltas) for the
+        scan.  The scan cuts at done, so the closing step's reward and delta carry the whole correction"""
+        if "h_states" in shared_data:
+            raise ValueError("a2c_amd: bootstrap_truncated covers feed-forward rollouts (no shared_data['h_states'])")
+        for name in ("truncs", "final_obs"):
+            if name not in shared_data:
+                raise ValueError(f"a2c_amd: bootstrap_truncated needs shared_data[{name!r}] (the Runner fills it)")
+        net, hyps = self.net, self.hyps
+        C, S = int(states.shape[1]), int(states[0].numel())
+        HW = S // C
+        truncs = self._dev(shared_data["truncs"]).reshape(-1)
+        final_obs = self._dev(shared_data["final_obs"]).reshape(N, HW)
+        if b["fin"] is None or tuple(b["fin"].shape) != (N, S):
+            b["fin"] = torch.zeros((N, S), device=net._dev)
+        fin = b["fin"]
+        ops.final_states(states, final_obs, C, HW, N, fin, st)
+        if try_key(hyps, "norm_obs", False):
+            vn = self.vecnorm() if callable(self.vecnorm) else self.vecnorm
+            if vn is None:
+                raise ValueError("a2c_amd: bootstrap_truncated under norm_obs normalises the final states by the Runner's "
+                                 "block: set Updater.vecnorm = runner.vecnorm")
+            vn.launch(N, 0, out_ptr=fin.data_ptr(), out_stride=S, C=C, update=False, st=st)
+        net._refresh(st)
+        vals = net._fwd(fin.data_ptr(), S, N, "vfin", st, False)["vals"]
+        ops.copy_rows(vals.data_ptr(), vals.stride(0), b["vfin"].data_ptr(), 1, N, 1, st)
+        ops.trunc_bootstrap(rewards, deltas, truncs, b["vfin"], hyps["gamma"], N, b["rewards_tb"], b["deltas_tb"], st)
+        return b["rewards_tb"], b["deltas_tb"]
 
     def capture_update(self, shared_data):
         """The enqueue half of update_model as hipGraphs: ONE graph on a single GPU; with a sharded update the captured

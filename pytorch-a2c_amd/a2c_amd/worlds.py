@@ -191,6 +191,23 @@ class HostWorld:
         return False
 
 
+class LaneHostWorld(HostWorld):
+    """``HostWorld`` of the twins of the lane worlds (point.py, cartpole.py, pendulum.py): every ``step()`` also sets
+    ``truncated`` -- the step ended the episode at a game frame where the step limit held and the game's own end condition did
+    not (``_frame`` says so in ``limit_alone``; both at one frame is a terminal end) -- and ``final_obs``, the observation of
+    the world the episode ended in.  A twin does not restart itself, so that is the step's own observation, ended or not: what
+    a2c_<world>_step_trunc reports beside a step whose world HAS restarted.  ``step()``'s return value
+    and ``info`` are what they were."""
+    truncated, final_obs, limit_alone = False, None, False
+
+    def step(self, action):
+        self.limit_alone = False
+        out = super().step(action)
+        self.truncated = bool(out[2] and self.limit_alone)
+        self.final_obs = out[0].copy()
+        return out
+
+
 class WorldFactory:
     """picklable ``env_fn`` for ``SequentialEnvironment`` / the env worker processes: ``env(env_id=..., **world)``"""
 
@@ -250,8 +267,9 @@ class DeviceWorldPool:
         ops.frame_stack_push(self.frames, ones, runner.bookmark.data_ptr(), runner.S, runner.bookmark.data_ptr(), runner.S,
                              self.B, runner.C, runner.HW)
 
-    def _launch(self, actions_ptr, act_stride, env0, B, frames, post):
-        """one launch over envs env0..env0+B: the arguments every world's step begins with, and its three outputs"""
+    def _launch(self, actions_ptr, act_stride, env0, B, frames, post, trunc=None):
+        """one launch over envs env0..env0+B: the arguments every world's step begins with, and its three outputs.  ``trunc``:
+        an ``ops.world_trunc`` block (the lane worlds, hyps bootstrap_truncated: DESIGN.md section 6o) or None"""
         if not self.started:
             raise RuntimeError(f"{type(self).__name__}: reset_all() / start(runner) first")
         if env0 < 0 or B < 1 or env0 + B > self.B:
@@ -259,24 +277,32 @@ class DeviceWorldPool:
         sl = slice(env0, env0 + B)
         head = (self.state[sl], actions_ptr, act_stride, self.action_shift, B, self.env_id0 + env0, self.seed)
         out = (self.rew[sl], self.done[sl], self.reset_mask[sl])
-        self._step(head, out, self.frames[sl] if frames else None, post, sl)
+        if trunc is None:
+            self._step(head, out, self.frames[sl] if frames else None, post, sl)
+        elif not self.reports_trunc:
+            raise ValueError(f"bootstrap_truncated: {type(self).__name__} does not report the state an episode ended in (the "
+                             "lane worlds do: Point, CartPole, Pendulum)")
+        else:
+            self._step(head, out, self.frames[sl] if frames else None, post, sl, trunc=trunc)
         return out
 
-    def step(self, actions_ptr, act_stride, env0=0, B=None):
+    reports_trunc = False          # has a2c_<world>_step_trunc (DeviceLaneWorldPool)
+
+    def step(self, actions_ptr, act_stride, env0=0, B=None, trunc=None):
         """advance envs env0..env0+B by the int64 actions at ``actions_ptr`` (element stride ``act_stride``)"""
         B = self.B - env0 if B is None else B
-        return (self.frames[env0:env0 + B],) + self._launch(actions_ptr, act_stride, env0, B, True, None)
+        return (self.frames[env0:env0 + B],) + self._launch(actions_ptr, act_stride, env0, B, True, None, trunc)
 
-    def device_step(self, t, env0, B, actions=None):
+    def device_step(self, t, env0, B, actions=None, trunc=None):
         if actions is None:
             raise ValueError(f"{type(self).__name__}.device_step needs actions=(address, stride)")
-        return self.step(actions[0], actions[1], env0, B)
+        return self.step(actions[0], actions[1], env0, B, trunc)
 
-    def device_step_post(self, t, env0, B, actions, post, frames=False):
+    def device_step_post(self, t, env0, B, actions, post, frames=False, trunc=None):
         """``device_step`` + the bookkeeping of env step ``t`` + the frame stack in ONE launch (a2c_<world>_step_post): ``post``
         is an ``ops.world_post`` block.  The new frame goes into plane C - 1 of ``post.out``; ``self.frames`` is written as
         well only with ``frames=True`` (the Runner does not read it).  -> (rew, done, reset)"""
-        return self._launch(actions[0], actions[1], env0, B, frames, post)
+        return self._launch(actions[0], actions[1], env0, B, frames, post, trunc)
 
     def episode_stats(self):
         """(dones, sum of the rewards they closed) since the last call; one device read"""
@@ -293,13 +319,14 @@ class DeviceLaneWorldPool(DeviceWorldPool):
     ``float_actions`` and ``n_act``; its ``__init__`` hands over its checked ``world`` tuple, the parameters in the order the
     library takes them."""
     WHAT = "World"
+    reports_trunc = True
 
     def __init__(self, n_envs, device, seed, env_id0, world, frame_skip, sticky_num, sticky_den, frame_skip_max):
         from . import ops
         self.world = world
         self.repeat = check_repeat(frame_skip, sticky_num, sticky_den, self.WHAT)
         self.rules = ops.world_rules(*self.repeat, *check_rules(frame_skip, frame_skip_max, what=self.WHAT), always=True)
-        self._op = {f: getattr(ops, f"{self.WHAT.lower()}_{f}") for f in ("state_bytes", "reset", "step")}
+        self._op = {f: getattr(ops, f"{self.WHAT.lower()}_{f}") for f in ("state_bytes", "reset", "step", "step_trunc")}
         super().__init__(n_envs, device, seed, env_id0, self._op["state_bytes"]() // 4)
         self._shift = float if getattr(self, "float_actions", False) else int
         self.action_shift = self._shift(0)
@@ -311,5 +338,9 @@ class DeviceLaneWorldPool(DeviceWorldPool):
     def _reset(self):
         self._op["reset"](self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
 
-    def _step(self, head, out, frames, post, sl):
-        self._op["step"](*head, *self.world, frames, self.HW, *out, self.rules, post, self.ep_stats[0:1], self.ep_stats[1:2])
+    def _step(self, head, out, frames, post, sl, trunc=None):
+        tail = (self.rules, post, self.ep_stats[0:1], self.ep_stats[1:2])
+        if trunc is None:
+            self._op["step"](*head, *self.world, frames, self.HW, *out, *tail)
+        else:
+            self._op["step_trunc"](*head, *self.world, frames, self.HW, *out, trunc, *tail)

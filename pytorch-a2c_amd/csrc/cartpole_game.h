@@ -60,9 +60,10 @@ struct CartPoleGame {
   }
 
   // One game frame of one world, in registers (no memory access).  a: 0 pushes left, 1 pushes right.  -> the reward, 1;
-  // over: the episode ended and the world has been restarted
+  // over: the episode ended and the world has been restarted; end keeps the world that fell or ran out of frames (lane_world.h)
+  template <typename E>
   static __device__ __forceinline__ int frame(World& w, WorldCount& c, int a, const Params& p, uint32_t seed, uint32_t env,
-                                              bool& over) {
+                                              bool& over, E& end) {
     ++c.steps;
     ++c.ep_steps;
     const int64_t x = w.x, xd = w.xd, th = w.th, thd = w.thd;
@@ -79,7 +80,10 @@ struct CartPoleGame {
     w.th = (int)(th + cp_mul(CP_TAU, thd));
     w.thd = (int)cp_clamp(thd + cp_mul(CP_TAU, thacc), -CP_VMAX, CP_VMAX);
     over = abs(w.x) > CP_X_LIMIT || abs(w.th) > CP_TH_LIMIT || c.ep_steps >= p.max_episode_steps;
-    if (over) new_episode(w, c, p, seed, env);
+    if (over) {
+      end.keep(w, !(abs(w.x) > CP_X_LIMIT || abs(w.th) > CP_TH_LIMIT));
+      new_episode(w, c, p, seed, env);
+    }
     return 1;
   }
 

@@ -76,3 +76,13 @@ extern "C" int a2c_pendulum_step(int32_t* state, const float* actions, int64_t a
   return lane_world_step<PendulumLane>(state, actions, act_ld, action_shift, B, env_id0, seed, {max_episode_steps}, obs, obs_ld,
                                        rew, done, reset, ep_count, ep_rew_sum, rules, post, stream);
 }
+
+// a2c_pendulum_step + the a2c_world_trunc outputs (time-limit truncation)
+extern "C" int a2c_pendulum_step_trunc(int32_t* state, const float* actions, int64_t act_ld, float action_shift, int B,
+                                       int env_id0, uint32_t seed, int max_episode_steps, float* obs, int64_t obs_ld, float* rew,
+                                       float* done, float* reset, int32_t* ep_count, int32_t* ep_rew_sum,
+                                       const a2c_world_rules* rules, const a2c_world_post* post, const a2c_world_trunc* tr,
+                                       a2c_stream_t stream) {
+  return lane_world_step<PendulumLane, true>(state, actions, act_ld, action_shift, B, env_id0, seed, {max_episode_steps}, obs,
+                                             obs_ld, rew, done, reset, ep_count, ep_rew_sum, rules, post, stream, tr);
+}

@@ -87,9 +87,11 @@ struct PendulumGame {
   }
 
   // One game frame of one world, in registers (no memory access).  a: the quantised torque q, -64 .. 64.  -> the reward in
-  // units of 2^-8, -4166 .. 0; over: the episode ended (only the step cap ends one) and the world has been restarted
+  // units of 2^-8, -4166 .. 0; over: the episode ended (only the step cap ends one) and the world has been restarted; end
+  // keeps the world the cap cut short (lane_world.h): every end here is by the limit alone
+  template <typename E>
   static __device__ __forceinline__ int frame(World& w, WorldCount& c, int a, const Params& p, uint32_t seed, uint32_t env,
-                                              bool& over) {
+                                              bool& over, E& end) {
     ++c.steps;
     ++c.ep_steps;
     const int64_t th = w.th, thd = w.thd, u = (int64_t)a * ((int64_t)1 << PD_Q_SHIFT);
@@ -103,7 +105,10 @@ struct PendulumGame {
     w.th = (int)nth;
     w.thd = (int)nthd;
     over = c.ep_steps >= p.max_episode_steps;
-    if (over) new_episode(w, c, p, seed, env);
+    if (over) {
+      end.keep(w, true);
+      new_episode(w, c, p, seed, env);
+    }
     return -(int)(cost >> PD_REW_SHIFT);
   }
 

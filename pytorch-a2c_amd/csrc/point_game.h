@@ -63,9 +63,10 @@ struct PointGame {
   }
 
   // One game frame of one world, in registers (no memory access).  a: the packed pair.  -> the reward; over: the episode
-  // ended and the world has been restarted
+  // ended and the world has been restarted; end keeps the world that won or ran out of frames (lane_world.h)
+  template <typename E>
   static __device__ __forceinline__ int frame(World& w, WorldCount& c, int a, const Params& p, uint32_t seed, uint32_t env,
-                                              bool& over) {
+                                              bool& over, E& end) {
     ++c.steps;
     ++c.ep_steps;
     const int d0 = cells(w);
@@ -76,6 +77,7 @@ struct PointGame {
     const int r = d0 - d1 + (reached ? POINT_REACH_BONUS : 0);
     w.got += reached;
     over = w.got >= p.targets_to_win || c.ep_steps >= p.max_episode_steps;
+    if (over) end.keep(w, w.got < p.targets_to_win);
     if (over) new_episode(w, c, p, seed, env);
     else if (reached) place(world_hash(seed, env, c.draws++), w.tx, w.ty);
     return r;

@@ -69,9 +69,10 @@ struct PongGame {
   }
 
   // One game frame of one world, in registers (wave-uniform; no memory access).  -> the reward; over: the episode ended and
-  // the world has been restarted
+  // the world has been restarted (the picture worlds report nothing about the frame that ended it: world.h, WorldNoEnd)
+  template <typename E>
   static __device__ __forceinline__ int frame(World& w, WorldCount& c, int a, const Params& p, uint32_t seed, uint32_t env,
-                                              bool& over) {
+                                              bool& over, E&) {
     ++c.steps;
     ++c.ep_steps;
     // 1. the agent's paddle

@@ -262,6 +262,29 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, c
                                                   float* __restrict__ y, long n) {
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) y[i] = a[i] + b[i];
 }
+
+// a2c_final_states: quad i of the N * C * Q quads of `out` (Q = HW / 4 quads a plane) comes from planes 1 .. C-1 of its
+// states row, or, in the last plane, from its final_obs row
+__global__ __launch_bounds__(256) void final_states_kernel(const float4* __restrict__ states, const float4* __restrict__ fin,
+                                                           long CQ, long Q, long total, float4* __restrict__ out) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+    const long e = i / CQ, q = i - e * CQ;
+    out[i] = q < CQ - Q ? states[i + Q] : fin[e * Q + (q - (CQ - Q))];
+  }
+}
+
+// a2c_trunc_bootstrap: the header's statement, one rounded operation after the other (x_out may be x: no __restrict__)
+__global__ __launch_bounds__(256) void trunc_bootstrap_kernel(const float* rewards, const float* deltas,
+                                                              const float* __restrict__ truncs, const float* __restrict__ vfin,
+                                                              float gamma, long n, float* rewards_out, float* deltas_out) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) {
+    const float t = __fmul_rn(gamma, truncs[i]);
+    const float r = rewards[i], d = deltas[i];
+    const float add = __fmul_rn(t, vfin[i]);
+    rewards_out[i] = t != 0.f ? __fadd_rn(r, add) : r;
+    deltas_out[i] = t != 0.f ? __fadd_rn(d, add) : d;
+  }
+}
 }  // namespace
 
 extern "C" {
@@ -314,6 +337,29 @@ int a2c_add(const float* a, const float* b, float* y, int64_t n, a2c_stream_t st
   if (n < 0 || (n > 0 && (!a || !b || !y))) return A2C_ERR_ARG;
   if (n == 0) return A2C_OK;
   hipLaunchKernelGGL(add_kernel, dim3(a2c_grid_1d(n, 256)), dim3(256), 0, a2c_s(stream), a, b, y, (long)n);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+int a2c_final_states(const float* states, const float* final_obs, int C, int HW, int64_t N, float* out, a2c_stream_t stream) {
+  if (N < 0 || C < 1 || HW < 4 || HW % 4 != 0) return A2C_ERR_ARG;
+  if (!states || !final_obs || !out || out == states) return A2C_ERR_ARG;
+  if ((((uintptr_t)states | (uintptr_t)final_obs | (uintptr_t)out) & 15u) != 0) return A2C_ERR_ARG;
+  if (N == 0) return A2C_OK;
+  const long Q = HW / 4, CQ = (long)C * Q, total = (long)N * CQ;
+  hipLaunchKernelGGL(final_states_kernel, dim3(a2c_grid_1d(total, 256)), dim3(256), 0, a2c_s(stream),
+                     reinterpret_cast<const float4*>(states), reinterpret_cast<const float4*>(final_obs), CQ, Q, total,
+                     reinterpret_cast<float4*>(out));
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+int a2c_trunc_bootstrap(const float* rewards, const float* deltas, const float* truncs, const float* vfin, float gamma,
+                        int64_t N, float* rewards_out, float* deltas_out, a2c_stream_t stream) {
+  if (N < 0 || !rewards || !deltas || !truncs || !vfin || !rewards_out || !deltas_out) return A2C_ERR_ARG;
+  if (N == 0) return A2C_OK;
+  hipLaunchKernelGGL(trunc_bootstrap_kernel, dim3(a2c_grid_1d(N, 256)), dim3(256), 0, a2c_s(stream), rewards, deltas, truncs,
+                     vfin, gamma, (long)N, rewards_out, deltas_out);
   A2C_CHECK_LAUNCH();
   return A2C_OK;
 }

@@ -5,7 +5,8 @@
 //   WORDS, HW, N_ACTIONS                  int32 state words per env, floats of one frame, actions
 //   World, Params, params_ok(Params)      the world in registers; its parameters, plain data, ONE kernel argument
 //   load, store, new_episode              state words <-> registers (store: lane i writes word i); reset + first serve
-//   frame(w, c, a, gp, seed, env, over)   one game frame in registers -> its reward; over: the episode ended, world restarted
+//   frame(w, c, a, gp, seed, env, over, end)   one game frame in registers -> its reward; over: the episode ended, world
+//                                         restarted; end: a WorldNoEnd / WorldEnd (below; the picture worlds report nothing)
 //   write_frame(w, f, f2, tid, n)         the prepped frame as 16-byte stores by n lanes to f and / or f2 (either may be null)
 //   closes(over, R)                       the `done` of an agent step with summed reward R
 // The Snake worlds keep kernels of their own (cells in LDS, a cooperative step) and use the first two parts only.
@@ -89,6 +90,21 @@ struct WorldCount {
 
 __device__ __forceinline__ int world_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// What G::frame hands back about the frame that ENDS an episode, before it restarts the world (time-limit truncation,
+// DESIGN.md section 6o): frame calls end.keep(w, limit_alone) with the world as the frame's physics left it; limit_alone: the
+// step limit ended the episode and the game's own end condition did not hold at that frame.  WorldNoEnd is the caller that
+// asks for nothing: every existing kernel, whose code it leaves as it was.  WorldEnd<World> keeps both in registers.
+struct WorldNoEnd {
+  template <typename W>
+  __device__ __forceinline__ void keep(const W&, bool) {}
+};
+template <typename W>
+struct WorldEnd {
+  W w;
+  bool limit_alone;
+  __device__ __forceinline__ void keep(const W& x, bool l) { w = x; limit_alone = l; }
+};
+
 template <int N>
 __device__ __forceinline__ int world_action(const int64_t* actions, int64_t act_stride, int action_shift, int e) {
   const int64_t a64 = (actions[(int64_t)e * act_stride] + (int64_t)action_shift) % N;
@@ -111,10 +127,11 @@ static inline bool world_frames_ok(const float* frames, int64_t frame_ld, int HW
 // The reward is booked once per agent step.  Where only an episode end closes (real dones only) this equals booking every game
 // frame and zeroing at the over: the loop breaks at the frame that ends the episode, so the sum at the over is the old
 // ep_rew + R, and the word left behind is 0 after an over and the old ep_rew + R otherwise.
-template <typename G>
+// end: a WorldNoEnd or a WorldEnd (above); the frame that ends the episode fills it.
+template <typename G, typename E>
 __device__ __forceinline__ int world_agent_step(typename G::World& w, WorldCount& c, int a, const typename G::Params& gp,
                                                 uint32_t seed, uint32_t env, int frame_skip, int sticky_num, int sticky_den,
-                                                bool& over, bool& closed, int& closed_rew) {
+                                                bool& over, bool& closed, int& closed_rew, E& end) {
   int R = 0;
   over = false;
   for (int s = 0; s < frame_skip; ++s) {
@@ -123,7 +140,7 @@ __device__ __forceinline__ int world_agent_step(typename G::World& w, WorldCount
       if ((int)(world_hash(seed, env, c.draws++) % (uint32_t)sticky_den) < sticky_num) x = c.prev;
       c.prev = x;
     }
-    R += G::frame(w, c, x, gp, seed, env, over);
+    R += G::frame(w, c, x, gp, seed, env, over, end);
     if (over) {
       c.prev = 0;
       break;
@@ -134,6 +151,14 @@ __device__ __forceinline__ int world_agent_step(typename G::World& w, WorldCount
   closed_rew = c.ep_rew;
   if (closed) c.ep_rew = 0;
   return R;
+}
+
+template <typename G>
+__device__ __forceinline__ int world_agent_step(typename G::World& w, WorldCount& c, int a, const typename G::Params& gp,
+                                                uint32_t seed, uint32_t env, int frame_skip, int sticky_num, int sticky_den,
+                                                bool& over, bool& closed, int& closed_rew) {
+  WorldNoEnd none;
+  return world_agent_step<G>(w, c, a, gp, seed, env, frame_skip, sticky_num, sticky_den, over, closed, closed_rew, none);
 }
 
 // lane 0 of the wave that owns the env: what a step leaves beside the state words

@@ -22,7 +22,11 @@
     ``--learn``; ``--exact`` is the leg that sets the two beside each other and nothing else: ms per epoch on the
     "device_graph" path under "reference" and under "exact", the samples of the two alternating; with ``--learn N`` the
     learning record under "exact" (with ``--norm`` too: that record with both normalisation keys on).
-    ``--out profiles/pendulum_exact_bench.json``.
+    ``--out profiles/pendulum_exact_bench.json``;
+  * ``--bootstrap-truncated``: the leg of hyps ``bootstrap_truncated`` and nothing else: ms per epoch of
+    FCModel on the "device_graph" path with the key off and on, the samples of the two alternating (the key adds one N-row
+    forward and three small launches to the update, and two stores per lane to the world step); with ``--learn N`` the
+    learning record with the key on (``--gauss-loss`` and ``--norm`` as given).  ``--out profiles/pendulum_trunc_bench.json``.
 
 Method: ONE PROCESS PER SAMPLE.  ``--sample WHAT`` runs one sample in this process (a warm-up that allocates, tunes and
 captures; then ``--epochs`` epochs, or the graph replays, between two HIP events) and prints one JSON line; without it the
@@ -70,8 +74,8 @@ def event_ms(fn, n):
 NORM_KEYS = dict(norm_obs=True, norm_rewards=True)
 
 
-def hyps_for(n_envs, T, path, norm=False, gauss_loss="reference"):
-    return dict(NORM_KEYS if norm else {}, gauss_loss=gauss_loss, gamma=.99, lambda_=.98, n_tsteps=T, n_rollouts=n_envs, n_envs=n_envs, n_frame_stack=4, action_shift=0,
+def hyps_for(n_envs, T, path, norm=False, gauss_loss="reference", trunc=False):
+    return dict(NORM_KEYS if norm else {}, **(dict(bootstrap_truncated=True) if trunc else {}), gauss_loss=gauss_loss, gamma=.99, lambda_=.98, n_tsteps=T, n_rollouts=n_envs, n_envs=n_envs, n_frame_stack=4, action_shift=0,
                 render=False, env_type="Pendulum-device" if path.startswith("device") else "Pendulum-host", use_bptt=False,
                 use_nstep_rets=False, norm_advs=True, entr_coef=.005, pi_coef=1.0, val_coef=.5, max_norm=.5, lr=1e-4,
                 optim_type="RMSprop", is_discrete=False, h_size=256, seed=0, rollout_graphs=path != "device_eager")
@@ -102,14 +106,14 @@ def sample_vecnorm(B=256, L=4, C=4, T=16, launches=200, replays=50, rounds=3):
     return dict(vecnorm_step=statistics.median(us))
 
 
-def sample_epoch(model, path, n_envs, T, epochs, norm=False, gauss_loss="reference"):
+def sample_epoch(model, path, n_envs, T, epochs, norm=False, gauss_loss="reference", trunc=False):
     import torch
     import a2c_amd
     from a2c_amd import preprocessing
     from a2c_amd.pendulum import DevicePendulumPool, PendulumEnv, PendulumFactory
     from a2c_amd.runner import HostEnvPool, Runner, SequentialEnvironment
     from a2c_amd.updater import Updater
-    hyps = hyps_for(n_envs, T, path, norm, gauss_loss)
+    hyps = hyps_for(n_envs, T, path, norm, gauss_loss, trunc)
     torch.manual_seed(0)
     net = getattr(a2c_amd.models, model)([4, 4], 1, h_size=256, is_discrete=False)
     N = n_envs * T
@@ -117,6 +121,8 @@ def sample_epoch(model, path, n_envs, T, epochs, norm=False, gauss_loss="referen
              dones=torch.zeros(N, device="cuda"), actions=torch.zeros(N, 1, device="cuda"))
     if net.is_recurrent:
         D["h_states"] = torch.zeros(N, net.h_size, device="cuda")
+    if trunc:
+        D.update(truncs=torch.zeros(N, device="cuda"), final_obs=torch.zeros(N, 4, device="cuda"))
     if path.startswith("device"):
         pool = DevicePendulumPool(n_envs, "cuda", seed=1, **WORLD)
     elif path == "host_serial":
@@ -128,6 +134,7 @@ def sample_epoch(model, path, n_envs, T, epochs, norm=False, gauss_loss="referen
         pool = ProcessEnvPool(SequentialEnvironment, n_envs, env_kwargs=kws, n_workers=8, action_dim=1, frame_shape=(1, 4))
     r = Runner(D, hyps, None, None, None, env_pool=pool)
     upd = Updater(net, hyps)
+    upd.vecnorm = lambda: r.vecnorm
     slots = list(range(n_envs))
 
     def epoch():
@@ -186,7 +193,7 @@ def sample_kernel(B, steps=200, C=4, replays=50, rounds=3):
     return out
 
 
-def sample_learn(epochs, norm=False, gauss_loss="reference"):
+def sample_learn(epochs, norm=False, gauss_loss="reference", trunc=False):
     """one train() run -> the evaluation return per epoch, and the untrained net's on worlds of the same kind (norm: with
     norm_obs and norm_rewards; the untrained net is then evaluated as every later epoch is, through a frozen block -- a fresh
     one, count 1e-4, mean 0, var 1, which is where train()'s own block starts)"""
@@ -197,7 +204,7 @@ def sample_learn(epochs, norm=False, gauss_loss="reference"):
     from a2c_amd.runner import DeviceStatsRunner
     from a2c_amd.training import DEFAULTS, train
     folder = tempfile.mkdtemp(prefix="pendulum_learn_")
-    keys = dict(NORM_KEYS if norm else {}, gauss_loss=gauss_loss)
+    keys = dict(NORM_KEYS if norm else {}, **(dict(bootstrap_truncated=True) if trunc else {}), gauss_loss=gauss_loss)
     hyps = dict(LEARN, exp_name="pendulum_learn", main_path=folder, **keys)
     # the untrained net: train()'s own construction (same seed, same defaults), evaluated as train() evaluates
     full = dict(DEFAULTS, **hyps, is_discrete=False, action_shift=0, state_shape=[hyps["n_frame_stack"], 4], action_size=1)
@@ -313,6 +320,40 @@ def exact_leg(args):
     print(json.dumps(res))
 
 
+def trunc_leg(args):
+    """hyps bootstrap_truncated off / on, alternating samples of FCModel on the device_graph path; optionally the learning
+    record with the key on, kept under its own name beside what the file already holds (a parent commit's figure among it)"""
+    import torch
+    res = {}
+    if args.out and os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    res.update(device=torch.cuda.get_device_name(0), world=WORLD)
+
+    def save():
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+    tag = ":norm" if args.norm else ""
+    if args.repeats > 0:            # (--repeats 0 --learn N: the learning record alone)
+        res.update(repeats=args.repeats, n_envs=args.n_envs, n_tsteps=args.n_tsteps, epochs=args.epochs, optim="RMSprop",
+                   path="device_graph", gauss_loss=args.gauss_loss, norm=bool(args.norm))
+        rows = dict(key_off=[], key_on=[])
+        for _ in range(args.repeats):
+            rows["key_off"].append(child(args, f"epoch:FCModel:device_graph{tag}")["ms_per_epoch"])
+            rows["key_on"].append(child(args, f"epoch:FCModel:device_graph{tag}:trunc")["ms_per_epoch"])
+        res["ms_per_epoch"] = {"FCModel": {k: spread(v) for k, v in rows.items()}}
+        print(f"# FCModel: {res['ms_per_epoch']['FCModel']}", file=sys.stderr, flush=True)
+        save()
+    if args.learn > 0:
+        name = "learning" + ("_exact" if args.gauss_loss == "exact" else "") + ("_norm" if args.norm else "") + "_trunc"
+        L = res[name] = child(args, f"learn:{args.learn}{tag}:trunc")
+        print(f"# {name}, {L['epochs']} epochs in {L['seconds']} s: untrained {L['untrained']}, first tenth "
+              f"{L['first_tenth_mean']}, last tenth {L['last_tenth_mean']}, best {L['best']}", file=sys.stderr, flush=True)
+    save()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5, help="samples per figure: one process each")
@@ -326,8 +367,10 @@ def main():
     ap.add_argument("--gauss-loss", default="reference", choices=("reference", "exact"),
                     help="hyps['gauss_loss'] of the epoch samples and of --learn")
     ap.add_argument("--exact", action="store_true", help="the gauss_loss leg only (see the module docstring)")
-    ap.add_argument("--sample", default=None, help="run ONE sample in this process: kernel:B, vecnorm, epoch:MODEL:PATH[:norm] "
-                                                   "or learn:N[:norm]")
+    ap.add_argument("--bootstrap-truncated", action="store_true",
+                    help="the bootstrap_truncated leg only (see the module docstring)")
+    ap.add_argument("--sample", default=None, help="run ONE sample in this process: kernel:B, vecnorm, "
+                                                   "epoch:MODEL:PATH[:norm][:trunc] or learn:N[:norm][:trunc]")
     ap.add_argument("--sample-timeout", type=float, default=600.0)
     ap.add_argument("--out", default=None, help="also write the result to this JSON file")
     args = ap.parse_args()
@@ -340,13 +383,15 @@ def main():
         elif kind == "vecnorm":
             res = sample_vecnorm()
         elif kind == "learn":
-            res = sample_learn(int(rest[0]), norm=rest[1:] == ["norm"], gauss_loss=args.gauss_loss)
+            res = sample_learn(int(rest[0]), norm="norm" in rest[1:], gauss_loss=args.gauss_loss, trunc="trunc" in rest[1:])
         else:
             model, path = rest[:2]
             res = sample_epoch(model, path, args.n_envs, args.n_tsteps, args.epochs if path.startswith("device") else args.host_epochs,
-                               norm=rest[2:] == ["norm"], gauss_loss=args.gauss_loss)
+                               norm="norm" in rest[2:], gauss_loss=args.gauss_loss, trunc="trunc" in rest[2:])
         print(json.dumps(res))
         return
+    if args.bootstrap_truncated:
+        return trunc_leg(args)
     if args.exact:
         return exact_leg(args)
     if args.norm:
