@@ -52,11 +52,18 @@ Random frame skip, episodic life, reward clipping (a2c_bre
     ``events["life_close"]`` counts the closes), done = 1, ``ep_rew`` zeroed.  The world is not restarted: bricks, lives,
     ``ep_steps`` and its limit carry on, and the ``reset()`` that follows such a done continues the game -- no draw, no
     word changed, the current frame (``continue_episode()`` is its frameless form; ``new_episode()`` stays the full restart);
-  * ``clip_rewards``: the agent step's reward is the sign of its sum; ``ep_rew`` keeps the sum itself."""
+  * ``clip_rewards``: the agent step's reward is the sign of its sum; ``ep_rew`` keeps the sum itself.
+
+``train()``, env_type "Breakout-device" / "Breakout-host" (the record is ``FAMILY`` below): keys ``lives`` (5),
+``max_episode_steps`` (10000), ``frame_skip`` / ``sticky_num`` / ``sticky_den`` / ``frame_skip_max`` as on the Pong worlds, and
+for the TRAINING worlds only ``episodic_life`` and ``clip_rewards`` (evaluation plays whole games for the game's score).
+``prep_fxn="breakout_prep"`` (grey levels 0..255 on the uint8 transport; with ``hyps["device_prep"] = "breakout_prep"`` on
+"Breakout-host" the process pool carries the RAW frames and the device preps them), 4 actions, ``action_shift`` 0 unless
+given, real dones only; evaluation on host ``BreakoutEnv``s."""
 import numpy as np
 
 from . import worlds
-from .worlds import (_M, DeviceWorldPool, HostWorld, _clamp, _env_id0, _i32, check_repeat, check_rules, factory_of,  # noqa: F401
+from .worlds import (_M, DeviceRegisterWorldPool, HostWorld, _clamp, _env_id0, _i32, check_repeat, check_rules,  # noqa: F401
                      hash32)
 
 N_ACTIONS = 4
@@ -85,11 +92,6 @@ RAW_H, RAW_W, RAW_TOP, RAW_LEFT, WALL_TOP = 210, 160, 35, 8, 17
 WALL_RGB, OBJECT_RGB = (142, 142, 142), (200, 72, 72)
 
 
-def repeat_from_hyps(hyps):
-    """(frame_skip, sticky_num, sticky_den) from the hyps (1, 0, 1 where absent); ValueError outside the bounds"""
-    return worlds.repeat_from_hyps(hyps, "Breakout")
-
-
 def check_world(lives=5, max_episode_steps=10000, frame_skip=1, sticky_num=0, sticky_den=1, frame_skip_max=None,
                 episodic_life=False, clip_rewards=False):
     """the bounds a2c_breakout_step / a2c_breakout_step_skip / a2c_breakout_step_rules enforce (A2C_ERR_ARG): same ones for the
@@ -101,20 +103,6 @@ def check_world(lives=5, max_episode_steps=10000, frame_skip=1, sticky_num=0, st
         raise ValueError(f"Breakout: unsupported world lives={n} max_episode_steps={m} (1 <= lives <= {MAX_LIVES}, "
                          f"1 <= max_episode_steps <= {MAX_EPISODE_STEPS})")
     return n, m
-
-
-RULE_KEYS = worlds.RULE_KEYS
-
-
-def rules_from_hyps(hyps):
-    """{frame_skip_max, episodic_life, clip_rewards} from the hyps (frame_skip, False, False where absent)"""
-    return worlds.rules_from_hyps(hyps, "Breakout", RULE_KEYS)
-
-
-def world_from_hyps(hyps):
-    """(lives, max_episode_steps) from the hyps; ValueError outside the bounds"""
-    get = lambda k, dflt: dflt if hyps.get(k) is None else hyps[k]
-    return check_world(get("lives", 5), get("max_episode_steps", 10000))
 
 
 class _ActionSpace:
@@ -277,11 +265,7 @@ class BreakoutEnv(HostWorld):
         self.over = self.closed = False
 
 
-# picklable ``env_fn``: ``BreakoutFactory(env_id=j, **world)()`` is a ``BreakoutEnv``
-BreakoutFactory = factory_of(BreakoutEnv)
-
-
-class DeviceBreakoutPool(DeviceWorldPool):
+class DeviceBreakoutPool(DeviceRegisterWorldPool):
     """``n_envs`` Breakout worlds in device memory (the Runner's device-pool protocol).  Env j is the world
     ``BreakoutEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames; with ``frame_skip`` / ``sticky_num`` /
     ``sticky_den`` other than (1, 0, .) a step is an agent step of a2c_breakout_step_skip, with
@@ -289,29 +273,18 @@ class DeviceBreakoutPool(DeviceWorldPool):
     a2c_breakout_step_rules (section 6i).  ``device_step`` returns ``done`` and ``reset`` as two tensors holding the same
     values, the real done (with ``episodic_life`` also a lost life).  ``episode_stats`` counts those dones and sums the
     (unclipped) rewards they closed."""
+    WHAT, FLAGS = "Breakout", True
     frame_shape = (1, H, W)
 
     def __init__(self, n_envs, device="cuda", seed=0, lives=5, max_episode_steps=10000, env_id0=0, frame_skip=1, sticky_num=0,
                  sticky_den=1, frame_skip_max=None, episodic_life=False, clip_rewards=False):
-        from . import ops
-        self.world = check_world(lives, max_episode_steps)
-        self.repeat = check_repeat(frame_skip, sticky_num, sticky_den, "Breakout")
-        # None: every key of section 6i at its default -- the entry points above; else the block of a2c_breakout_step_rules
-        self.rules = ops.world_rules(*self.repeat, *check_rules(frame_skip, frame_skip_max, episodic_life, clip_rewards,
-                                                                "Breakout", flags=True))
-        self.plain = self.repeat[:2] == (1, 0) and self.rules is None      # today's world: the entry points without frame skip
-        super().__init__(n_envs, device, seed, env_id0, ops.breakout_state_bytes(self.world[0]) // 4)
+        super().__init__(n_envs, device, seed, env_id0, check_world(lives, max_episode_steps), frame_skip, sticky_num, sticky_den,
+                         frame_skip_max, episodic_life, clip_rewards)
 
-    def _reset(self):
-        from . import ops
-        ops.breakout_reset(self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
 
-    def _step(self, head, out, frames, post, sl):
-        from . import ops
-        if self.rules is not None:
-            fn, extra = ops.breakout_step_rules, (self.rules, post)
-        elif post is None:
-            fn, extra = (ops.breakout_step, ()) if self.plain else (ops.breakout_step_skip, self.repeat)
-        else:
-            fn, extra = (ops.breakout_step_post, (post,)) if self.plain else (ops.breakout_step_post_skip, (*self.repeat, post))
-        fn(*head, *self.world, frames, self.HW, *out, *extra, self.ep_stats[0:1], self.ep_stats[1:2])
+# picklable ``env_fn``: ``BreakoutFactory(env_id=j, **world)()`` is a ``BreakoutEnv``
+BreakoutFactory = worlds.factory_of(BreakoutEnv)
+FAMILY = worlds.WorldFamily(__name__, "Breakout", check_world, (("lives", 5), ("max_episode_steps", 10000)), "breakout_prep",
+                            rule_keys=worlds.RULE_KEYS, device_prep="breakout_prep")
+RULE_KEYS, rules_from_hyps, world_from_hyps, repeat_from_hyps = (FAMILY.rule_keys, FAMILY.rules_from_hyps, FAMILY.world_from_hyps,
+                                                                 FAMILY.repeat_from_hyps)

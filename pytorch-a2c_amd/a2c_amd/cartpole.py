@@ -29,11 +29,17 @@ The agent step is that of the Pong worlds (``worlds.HostWorld.advance``; DESIGN.
 ``frame_skip_max`` game frames with one action, the k-draw first, then one sticky draw per frame.  ``episodic_life`` /
 ``clip_rewards`` are keys of the Breakout worlds.
 
-Observation, 4 floats: the state ints times 2^-20, each exact in fp32 (|q| < 2^24) and identical on both sides."""
+Observation, 4 floats: the state ints times 2^-20, each exact in fp32 (|q| < 2^24) and identical on both sides.
+
+``train()``, env_type "CartPole-device" / "CartPole-host" ("CartPole-v1" stays gym's; the record is ``FAMILY`` below): keys
+``max_episode_steps`` (500) and ``frame_skip`` / ``frame_skip_max`` / ``sticky_num`` / ``sticky_den`` as on the Pong worlds;
+``prep_fxn="null_prep"``, 2 actions, ``action_shift`` 0 unless given, ``model`` FCModel / GRUFCModel with ``is_discrete=True``
+only.  "CartPole-host" steps ``CartPoleEnv``s behind the usual pools (the process pool carries their fp32 frames);
+evaluation on host ``CartPoleEnv``s."""
 import numpy as np
 
 from . import worlds
-from .worlds import DeviceLaneWorldPool, LaneHostWorld, _clamp, check_repeat, factory_of
+from .worlds import DeviceLaneWorldPool, LaneHostWorld, _clamp, check_repeat
 
 N_ACTIONS = 2
 FRAC = 20
@@ -93,19 +99,6 @@ def check_world(max_episode_steps=500, frame_skip=1, sticky_num=0, sticky_den=1,
     return (m,)
 
 
-RULE_KEYS = ("frame_skip_max",)
-
-
-def rules_from_hyps(hyps):
-    """{frame_skip_max} from the hyps (frame_skip where absent); ValueError for episodic_life / clip_rewards"""
-    return worlds.rules_from_hyps(hyps, "CartPole", RULE_KEYS)
-
-
-def world_from_hyps(hyps):
-    """(max_episode_steps,) from the hyps; ValueError outside the bounds"""
-    return check_world(500 if hyps.get("max_episode_steps") is None else hyps["max_episode_steps"])
-
-
 class _Discrete:
     """Discrete-like: ``n`` (SequentialEnvironment reads a discrete env from that)"""
     n = N_ACTIONS
@@ -153,10 +146,6 @@ class CartPoleEnv(LaneHostWorld):
     render_rgb = obs
 
 
-# picklable ``env_fn``: ``CartPoleFactory(env_id=j, **world)()`` is a ``CartPoleEnv``
-CartPoleFactory = factory_of(CartPoleEnv)
-
-
 class DeviceCartPolePool(DeviceLaneWorldPool):
     """``n_envs`` CartPole worlds in device memory (the Runner's device-pool protocol).  Env j is the world ``CartPoleEnv(seed,
     env_id=env_id0 + j, ...)``: same draws, same observations.  ``step`` / ``device_step`` take the address of env 0's int64
@@ -168,3 +157,11 @@ class DeviceCartPolePool(DeviceLaneWorldPool):
                  sticky_den=1, frame_skip_max=None):
         super().__init__(n_envs, device, seed, env_id0, check_world(max_episode_steps), frame_skip, sticky_num, sticky_den,
                          frame_skip_max)
+
+
+# picklable ``env_fn``: ``CartPoleFactory(env_id=j, **world)()`` is a ``CartPoleEnv``
+CartPoleFactory = worlds.factory_of(CartPoleEnv)
+FAMILY = worlds.WorldFamily(__name__, "CartPole", check_world, (("max_episode_steps", 500),), "null_prep",
+                            rule_keys=("frame_skip_max",), models=worlds.FC_MODELS,
+                            takes="one of two int actions on (1, 4) observations")
+RULE_KEYS, rules_from_hyps, world_from_hyps = FAMILY.rule_keys, FAMILY.rules_from_hyps, FAMILY.world_from_hyps

@@ -1278,6 +1278,15 @@ def _chk_world(state, frames, rew=None, done=None, reset=None, ep_count=None, ep
     _chk(ep_count, "ep_count", torch.int32); _chk(ep_rew_sum, "ep_rew_sum", torch.int32)
 
 
+def _world_step(name, state, head, frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, tail, st):
+    """the step entry point ``name`` of a Pong / Breakout / lane world, its tensors checked: every one of them takes
+    (state, *head, frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, *tail, stream) -- ``head``: the actions, the env
+    range, the seed and the world's parameters; ``tail``: the frame skip and the argument blocks the entry point adds"""
+    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
+    check(getattr(lib(), name)(_p(state), *head, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
+                               _p(ep_rew_sum), *tail, _st(st)), name)
+
+
 def pong_state_bytes(points_to_win=21):
     """bytes of one env's state; raises for a world the kernels do not support"""
     n = int(lib().a2c_pong_state_bytes(points_to_win))
@@ -1296,10 +1305,9 @@ def pong_reset(state, B, env_id0, seed, points_to_win, max_episode_steps, opp_sk
 def pong_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win, max_episode_steps, opp_skill_num,
               opp_skill_den, frames, frame_ld, rew, done, reset, ep_count=None, ep_rew_sum=None, st=None):
     """actions_ptr: address of env 0's int64 action, ``act_stride`` elements between envs (a row of the rollout buffer)"""
-    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_pong_step(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
-                              max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew), _p(done),
-                              _p(reset), _p(ep_count), _p(ep_rew_sum), _st(st)), "a2c_pong_step")
+    _world_step("a2c_pong_step", state, (actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
+                                         max_episode_steps, opp_skill_num, opp_skill_den),
+                frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, (), st)
 
 
 def pong_step_skip(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win, max_episode_steps,
@@ -1307,11 +1315,9 @@ def pong_step_skip(state, actions_ptr, act_stride, action_shift, B, env_id0, see
                    ep_count=None, ep_rew_sum=None, st=None):
     """pong_step over ``frame_skip`` game frames, each keeping the previous frame's action with probability ``sticky_num`` /
     ``sticky_den``; (1, 0, 1) is pong_step"""
-    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_pong_step_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
-                                   max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew), _p(done),
-                                   _p(reset), _p(ep_count), _p(ep_rew_sum), frame_skip, sticky_num, sticky_den, _st(st)),
-          "a2c_pong_step_skip")
+    _world_step("a2c_pong_step_skip", state, (actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
+                                              max_episode_steps, opp_skill_num, opp_skill_den),
+                frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, (frame_skip, sticky_num, sticky_den), st)
 
 
 # ---------------------------------------------------------------- Breakout worlds in device memory (csrc/breakout.hip)
@@ -1332,20 +1338,17 @@ def breakout_reset(state, B, env_id0, seed, lives, max_episode_steps, frames, fr
 def breakout_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames, frame_ld,
                   rew, done, reset, ep_count=None, ep_rew_sum=None, st=None):
     """actions_ptr: address of env 0's int64 action, ``act_stride`` elements between envs (a row of the rollout buffer)"""
-    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_breakout_step(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
-                                  max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
-                                  _p(ep_rew_sum), _st(st)), "a2c_breakout_step")
+    _world_step("a2c_breakout_step", state, (actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps),
+                frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, (), st)
 
 
 def breakout_step_skip(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames,
                        frame_ld, rew, done, reset, frame_skip, sticky_num, sticky_den, ep_count=None, ep_rew_sum=None, st=None):
     """breakout_step over ``frame_skip`` game frames, each keeping the previous frame's action with probability
     ``sticky_num`` / ``sticky_den``; (1, 0, 1) is breakout_step"""
-    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_breakout_step_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
-                                       max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
-                                       _p(ep_rew_sum), frame_skip, sticky_num, sticky_den, _st(st)), "a2c_breakout_step_skip")
+    _world_step("a2c_breakout_step_skip", state, (actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
+                                                  max_episode_steps),
+                frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, (frame_skip, sticky_num, sticky_den), st)
 
 
 # ---------------------------------------------------------------- world step + bookkeeping + frame stack in one launch
@@ -1380,42 +1383,35 @@ def pong_step_post(state, actions_ptr, act_stride, action_shift, B, env_id0, see
                    opp_skill_num, opp_skill_den, frames, frame_ld, rew, done, reset, post, ep_count=None, ep_rew_sum=None,
                    st=None):
     """pong_step + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
-    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_pong_step_post(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
-                                         max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew),
-                                         _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum), _post_ref(post), _st(st)),
-          "a2c_pong_step_post")
+    _world_step("a2c_pong_step_post", state, (actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
+                                              max_episode_steps, opp_skill_num, opp_skill_den),
+                frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, (_post_ref(post),), st)
 
 
 def breakout_step_post(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames,
                        frame_ld, rew, done, reset, post, ep_count=None, ep_rew_sum=None, st=None):
     """breakout_step + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
-    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_breakout_step_post(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
-                                             max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset),
-                                             _p(ep_count), _p(ep_rew_sum), _post_ref(post), _st(st)), "a2c_breakout_step_post")
+    _world_step("a2c_breakout_step_post", state, (actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
+                                                  max_episode_steps),
+                frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, (_post_ref(post),), st)
 
 
 def pong_step_post_skip(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win, max_episode_steps,
                         opp_skill_num, opp_skill_den, frames, frame_ld, rew, done, reset, frame_skip, sticky_num, sticky_den,
                         post, ep_count=None, ep_rew_sum=None, st=None):
     """pong_step_skip + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
-    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_pong_step_post_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
-                                        max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew),
-                                        _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum), frame_skip, sticky_num, sticky_den,
-                                        _post_ref(post), _st(st)), "a2c_pong_step_post_skip")
+    _world_step("a2c_pong_step_post_skip", state, (actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
+                                                   max_episode_steps, opp_skill_num, opp_skill_den),
+                frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, (frame_skip, sticky_num, sticky_den, _post_ref(post)), st)
 
 
 def breakout_step_post_skip(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames,
                             frame_ld, rew, done, reset, frame_skip, sticky_num, sticky_den, post, ep_count=None,
                             ep_rew_sum=None, st=None):
     """breakout_step_skip + the bookkeeping of the env step + frame_stack_push in one launch; ``frames`` may be None"""
-    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_breakout_step_post_skip(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
-                                            max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset),
-                                            _p(ep_count), _p(ep_rew_sum), frame_skip, sticky_num, sticky_den, _post_ref(post),
-                                            _st(st)), "a2c_breakout_step_post_skip")
+    _world_step("a2c_breakout_step_post_skip", state, (actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
+                                                       max_episode_steps),
+                frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, (frame_skip, sticky_num, sticky_den, _post_ref(post)), st)
 
 
 # ---------------------------------------------------------------- random frame skip, episodic life, reward clipping
@@ -1435,21 +1431,18 @@ def pong_step_rules(state, actions_ptr, act_stride, action_shift, B, env_id0, se
                     ep_rew_sum=None, st=None):
     """pong_step_skip (``post`` None) / pong_step_post_skip by a ``world_rules`` block: the game frames of an agent step drawn
     from frame_skip .. frame_skip_max"""
-    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_pong_step_rules(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
-                                    max_episode_steps, opp_skill_num, opp_skill_den, _p(frames), frame_ld, _p(rew), _p(done),
-                                    _p(reset), _p(ep_count), _p(ep_rew_sum), _post_ref(rules), _post_ref(post), _st(st)),
-          "a2c_pong_step_rules")
+    _world_step("a2c_pong_step_rules", state, (actions_ptr, act_stride, action_shift, B, env_id0, seed, points_to_win,
+                                               max_episode_steps, opp_skill_num, opp_skill_den),
+                frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, (_post_ref(rules), _post_ref(post)), st)
 
 
 def breakout_step_rules(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, lives, max_episode_steps, frames,
                         frame_ld, rew, done, reset, rules, post=None, ep_count=None, ep_rew_sum=None, st=None):
     """breakout_step_skip (``post`` None) / breakout_step_post_skip by a ``world_rules`` block: the game frames of an agent
     step drawn, a lost life closing the step (episodic_life), the reward as a sign (clip_rewards)"""
-    _chk_world(state, frames, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_breakout_step_rules(_p(state), actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
-                                        max_episode_steps, _p(frames), frame_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
-                                        _p(ep_rew_sum), _post_ref(rules), _post_ref(post), _st(st)), "a2c_breakout_step_rules")
+    _world_step("a2c_breakout_step_rules", state, (actions_ptr, act_stride, action_shift, B, env_id0, seed, lives,
+                                                   max_episode_steps),
+                frames, frame_ld, rew, done, reset, ep_count, ep_rew_sum, (_post_ref(rules), _post_ref(post)), st)
 
 
 # ---------------------------------------------------------------- Point worlds in device memory (csrc/point.hip)
@@ -1469,10 +1462,9 @@ def point_step(state, actions_ptr, act_ld, action_shift, B, env_id0, seed, targe
     """actions_ptr: address of env 0's two float32 actions, ``act_ld`` floats between envs (a row of the rollout buffer);
     ``rules``: a ``world_rules`` block or None (one game frame); ``post``: a ``world_post`` block -- the step + the bookkeeping
     of the env step + the hidden-row reset + frame_stack_push in one launch (``obs`` may then be None) -- or None"""
-    _chk_world(state, obs, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_point_step(_p(state), actions_ptr, act_ld, float(action_shift), B, env_id0, seed, targets_to_win,
-                               max_episode_steps, _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum),
-                               _post_ref(rules), _post_ref(post), _st(st)), "a2c_point_step")
+    _world_step("a2c_point_step", state, (actions_ptr, act_ld, float(action_shift), B, env_id0, seed, targets_to_win,
+                                          max_episode_steps),
+                obs, obs_ld, rew, done, reset, ep_count, ep_rew_sum, (_post_ref(rules), _post_ref(post)), st)
 
 
 # ---------------------------------------------------------------- CartPole worlds in device memory (csrc/cartpole.hip)
@@ -1492,10 +1484,8 @@ def cartpole_step(state, actions_ptr, act_stride, action_shift, B, env_id0, seed
     """actions_ptr: address of env 0's int64 action, ``act_stride`` elements between envs; ``rules``: a ``world_rules`` block
     or None (one game frame); ``post``: a ``world_post`` block -- the step + the bookkeeping of the env step + the hidden-row
     reset + frame_stack_push in one launch (``obs`` may then be None) -- or None"""
-    _chk_world(state, obs, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_cartpole_step(_p(state), actions_ptr, act_stride, int(action_shift), B, env_id0, seed, max_episode_steps,
-                                  _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum),
-                                  _post_ref(rules), _post_ref(post), _st(st)), "a2c_cartpole_step")
+    _world_step("a2c_cartpole_step", state, (actions_ptr, act_stride, int(action_shift), B, env_id0, seed, max_episode_steps),
+                obs, obs_ld, rew, done, reset, ep_count, ep_rew_sum, (_post_ref(rules), _post_ref(post)), st)
 
 
 # ---------------------------------------------------------------- Pendulum worlds in device memory (csrc/pendulum.hip)
@@ -1516,10 +1506,8 @@ def pendulum_step(state, actions_ptr, act_ld, action_shift, B, env_id0, seed, ma
     ``rules``: a ``world_rules`` block or None (one game frame); ``post``: a ``world_post`` block -- the step + the bookkeeping
     of the env step + the hidden-row reset + frame_stack_push in one launch (``obs`` may then be None) -- or None.
     ``ep_rew_sum`` gets whole reward units: every closed episode's sum floored"""
-    _chk_world(state, obs, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_pendulum_step(_p(state), actions_ptr, act_ld, float(action_shift), B, env_id0, seed, max_episode_steps,
-                                  _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count), _p(ep_rew_sum),
-                                  _post_ref(rules), _post_ref(post), _st(st)), "a2c_pendulum_step")
+    _world_step("a2c_pendulum_step", state, (actions_ptr, act_ld, float(action_shift), B, env_id0, seed, max_episode_steps),
+                obs, obs_ld, rew, done, reset, ep_count, ep_rew_sum, (_post_ref(rules), _post_ref(post)), st)
 
 
 # ---------------------------------------------------------------- time-limit truncation on the lane worlds (DESIGN.md section 6o)
@@ -1532,31 +1520,25 @@ def world_trunc(trunc_ptr, trunc_stride, final_obs_ptr, final_ld):
 def point_step_trunc(state, actions_ptr, act_ld, action_shift, B, env_id0, seed, targets_to_win, max_episode_steps, obs, obs_ld,
                      rew, done, reset, tr, rules=None, post=None, ep_count=None, ep_rew_sum=None, st=None):
     """point_step + ``tr``, a ``world_trunc`` block: did the step limit alone end the episode, and the observation it ended in"""
-    _chk_world(state, obs, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_point_step_trunc(_p(state), actions_ptr, act_ld, float(action_shift), B, env_id0, seed, targets_to_win,
-                                     max_episode_steps, _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
-                                     _p(ep_rew_sum), _post_ref(rules), _post_ref(post), _post_ref(tr), _st(st)),
-          "a2c_point_step_trunc")
+    _world_step("a2c_point_step_trunc", state, (actions_ptr, act_ld, float(action_shift), B, env_id0, seed, targets_to_win,
+                                                max_episode_steps),
+                obs, obs_ld, rew, done, reset, ep_count, ep_rew_sum, (_post_ref(rules), _post_ref(post), _post_ref(tr)), st)
 
 
 def cartpole_step_trunc(state, actions_ptr, act_stride, action_shift, B, env_id0, seed, max_episode_steps, obs, obs_ld, rew,
                         done, reset, tr, rules=None, post=None, ep_count=None, ep_rew_sum=None, st=None):
     """cartpole_step + ``tr``, a ``world_trunc`` block"""
-    _chk_world(state, obs, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_cartpole_step_trunc(_p(state), actions_ptr, act_stride, int(action_shift), B, env_id0, seed,
-                                        max_episode_steps, _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
-                                        _p(ep_rew_sum), _post_ref(rules), _post_ref(post), _post_ref(tr), _st(st)),
-          "a2c_cartpole_step_trunc")
+    _world_step("a2c_cartpole_step_trunc", state, (actions_ptr, act_stride, int(action_shift), B, env_id0, seed,
+                                                   max_episode_steps),
+                obs, obs_ld, rew, done, reset, ep_count, ep_rew_sum, (_post_ref(rules), _post_ref(post), _post_ref(tr)), st)
 
 
 def pendulum_step_trunc(state, actions_ptr, act_ld, action_shift, B, env_id0, seed, max_episode_steps, obs, obs_ld, rew, done,
                         reset, tr, rules=None, post=None, ep_count=None, ep_rew_sum=None, st=None):
     """pendulum_step + ``tr``, a ``world_trunc`` block"""
-    _chk_world(state, obs, rew, done, reset, ep_count, ep_rew_sum)
-    check(lib().a2c_pendulum_step_trunc(_p(state), actions_ptr, act_ld, float(action_shift), B, env_id0, seed,
-                                        max_episode_steps, _p(obs), obs_ld, _p(rew), _p(done), _p(reset), _p(ep_count),
-                                        _p(ep_rew_sum), _post_ref(rules), _post_ref(post), _post_ref(tr), _st(st)),
-          "a2c_pendulum_step_trunc")
+    _world_step("a2c_pendulum_step_trunc", state, (actions_ptr, act_ld, float(action_shift), B, env_id0, seed,
+                                                   max_episode_steps),
+                obs, obs_ld, rew, done, reset, ep_count, ep_rew_sum, (_post_ref(rules), _post_ref(post), _post_ref(tr)), st)
 
 
 def final_states(states, final_obs, C, HW, N, out, st=None):

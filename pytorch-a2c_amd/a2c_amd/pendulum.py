@@ -39,11 +39,17 @@ The agent step is that of the Pong worlds (``worlds.HostWorld.advance``; DESIGN.
 ``clip_rewards`` are keys of the Breakout worlds.
 
 Observation, 4 floats: (cos th, sin th, thd) times 2^-20 and a 0 (the post form moves planes as 16-byte quads), each exact in
-fp32 (|int| <= 2^23) and identical on both sides."""
+fp32 (|int| <= 2^23) and identical on both sides.
+
+``train()``, env_type "Pendulum-device" / "Pendulum-host" ("Pendulum-v1" stays gym's; the record is ``FAMILY`` below): keys
+``max_episode_steps`` (200, at most 2^16) and ``frame_skip`` / ``frame_skip_max`` / ``sticky_num`` / ``sticky_den`` as on the
+Pong worlds; ``prep_fxn="null_prep"``, ``is_discrete=False``, 1 float action (the torque, clamped to +-2), and the refusals
+and pools of the Point worlds: ``model`` FCModel / GRUFCModel only, "Pendulum-host" behind ``env_pool`` "serial" (the default)
+or "process_f32"; evaluation on host ``PendulumEnv``s."""
 import numpy as np
 
 from . import worlds
-from .worlds import DeviceLaneWorldPool, LaneHostWorld, _clamp, check_repeat, factory_of
+from .worlds import DeviceLaneWorldPool, LaneHostWorld, _clamp, check_repeat
 
 ACTION_SIZE = 1
 FRAC = 20
@@ -116,19 +122,6 @@ def check_world(max_episode_steps=200, frame_skip=1, sticky_num=0, sticky_den=1,
     return (m,)
 
 
-RULE_KEYS = ("frame_skip_max",)
-
-
-def rules_from_hyps(hyps):
-    """{frame_skip_max} from the hyps (frame_skip where absent); ValueError for episodic_life / clip_rewards"""
-    return worlds.rules_from_hyps(hyps, "Pendulum", RULE_KEYS)
-
-
-def world_from_hyps(hyps):
-    """(max_episode_steps,) from the hyps; ValueError outside the bounds"""
-    return check_world(200 if hyps.get("max_episode_steps") is None else hyps["max_episode_steps"])
-
-
 def quantise(a, shift=0.0):
     """the quantiser in NumPy: float actions (any shape) -> int32 q in -64 .. 64.  x = fp32(a + shift), one rounded add; NaN
     -> 0; else rint(clip(x, -2, 2) * 32), ties to even (the product is exact)"""
@@ -192,10 +185,6 @@ class PendulumEnv(LaneHostWorld):
     render_rgb = obs
 
 
-# picklable ``env_fn``: ``PendulumFactory(env_id=j, **world)()`` is a ``PendulumEnv``
-PendulumFactory = factory_of(PendulumEnv)
-
-
 class DevicePendulumPool(DeviceLaneWorldPool):
     """``n_envs`` Pendulum worlds in device memory (the Runner's device-pool protocol).  Env j is the world ``PendulumEnv(seed,
     env_id=env_id0 + j, ...)``: same draws, same observations.  ``float_actions``: ``step`` / ``device_step`` take the address
@@ -211,3 +200,10 @@ class DevicePendulumPool(DeviceLaneWorldPool):
                  sticky_den=1, frame_skip_max=None):
         super().__init__(n_envs, device, seed, env_id0, check_world(max_episode_steps), frame_skip, sticky_num, sticky_den,
                          frame_skip_max)
+
+
+# picklable ``env_fn``: ``PendulumFactory(env_id=j, **world)()`` is a ``PendulumEnv``
+PendulumFactory = worlds.factory_of(PendulumEnv)
+FAMILY = worlds.WorldFamily(__name__, "Pendulum", check_world, (("max_episode_steps", 200),), "null_prep",
+                            rule_keys=("frame_skip_max",), models=worlds.FC_MODELS)
+RULE_KEYS, rules_from_hyps, world_from_hyps = FAMILY.rule_keys, FAMILY.rules_from_hyps, FAMILY.world_from_hyps

@@ -31,11 +31,17 @@ The agent step is that of the Pong worlds (``worlds.HostWorld.advance``; DESIGN.
 frame's own draws.  ``episodic_life`` / ``clip_rewards`` are keys of the Breakout worlds.
 
 Observation, 8 floats, each an integer times a power of two, so exact in fp32 and identical on both sides:
-  [(2px - 4095) / 4096, (2py - 4095) / 4096, vx / 64, vy / 64, (tx - px) / 4096, (ty - py) / 4096, got / 8, 1]"""
+  [(2px - 4095) / 4096, (2py - 4095) / 4096, vx / 64, vy / 64, (tx - px) / 4096, (ty - py) / 4096, got / 8, 1]
+
+``train()``, env_type "Point-device" / "Point-host" (the record is ``FAMILY`` below): keys ``targets_to_win`` (3),
+``max_episode_steps`` (1000) and ``frame_skip`` / ``frame_skip_max`` / ``sticky_num`` / ``sticky_den`` as on the Pong worlds;
+``prep_fxn="null_prep"``, ``is_discrete=False``, 2 float actions, ``model`` FCModel / GRUFCModel only (anything else is a
+ValueError before anything is allocated).  ``DevicePointPool`` reads the float action rows on the device; "Point-host" steps
+``PointEnv``s behind ``env_pool`` "serial" (the default) or "process_f32"; evaluation on host ``PointEnv``s."""
 import numpy as np
 
 from . import worlds
-from .worlds import DeviceLaneWorldPool, LaneHostWorld, _clamp, check_repeat, factory_of
+from .worlds import DeviceLaneWorldPool, LaneHostWorld, _clamp, check_repeat
 
 ACTION_SIZE = 2
 P, VMAX, CELL, REACH_BONUS = 4096, 64, 64, 10
@@ -52,20 +58,6 @@ def check_world(targets_to_win=3, max_episode_steps=1000, frame_skip=1, sticky_n
         raise ValueError(f"Point: unsupported world targets_to_win={n} max_episode_steps={m} (1 <= targets_to_win <= "
                          f"{MAX_TARGETS}, 1 <= max_episode_steps <= {MAX_EPISODE_STEPS})")
     return n, m
-
-
-RULE_KEYS = ("frame_skip_max",)
-
-
-def rules_from_hyps(hyps):
-    """{frame_skip_max} from the hyps (frame_skip where absent); ValueError for episodic_life / clip_rewards"""
-    return worlds.rules_from_hyps(hyps, "Point", RULE_KEYS)
-
-
-def world_from_hyps(hyps):
-    """(targets_to_win, max_episode_steps) from the hyps; ValueError outside the bounds"""
-    get = lambda k, dflt: dflt if hyps.get(k) is None else hyps[k]
-    return check_world(get("targets_to_win", 3), get("max_episode_steps", 1000))
 
 
 def quantise(a, shift=0.0):
@@ -172,10 +164,6 @@ class PointEnv(LaneHostWorld):
     render_rgb = obs
 
 
-# picklable ``env_fn``: ``PointFactory(env_id=j, **world)()`` is a ``PointEnv``
-PointFactory = factory_of(PointEnv)
-
-
 class DevicePointPool(DeviceLaneWorldPool):
     """``n_envs`` Point worlds in device memory (the Runner's device-pool protocol).  Env j is the world ``PointEnv(seed,
     env_id=env_id0 + j, ...)``: same draws, same observations.  ``float_actions``: ``step`` / ``device_step`` take the address
@@ -190,3 +178,10 @@ class DevicePointPool(DeviceLaneWorldPool):
                  sticky_num=0, sticky_den=1, frame_skip_max=None):
         super().__init__(n_envs, device, seed, env_id0, check_world(targets_to_win, max_episode_steps), frame_skip, sticky_num,
                          sticky_den, frame_skip_max)
+
+
+# picklable ``env_fn``: ``PointFactory(env_id=j, **world)()`` is a ``PointEnv``
+PointFactory = worlds.factory_of(PointEnv)
+FAMILY = worlds.WorldFamily(__name__, "Point", check_world, (("targets_to_win", 3), ("max_episode_steps", 1000)), "null_prep",
+                            rule_keys=("frame_skip_max",), models=worlds.FC_MODELS)
+RULE_KEYS, rules_from_hyps, world_from_hyps = FAMILY.rule_keys, FAMILY.rules_from_hyps, FAMILY.world_from_hyps

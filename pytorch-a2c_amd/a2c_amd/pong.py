@@ -43,12 +43,18 @@ Random frame skip (a2c_pong_step_rules): with ``frame_skip
 ``frame_skip``) above ``frame_skip`` the agent step first takes ONE draw ``d``, before its first sticky draw, and plays
 k = frame_skip + d mod (frame_skip_max - frame_skip + 1) game frames: ``frame_skip=2, frame_skip_max=4, sticky_num=1,
 sticky_den=4`` is the stepping rule of ``Pong-v0``.  Episodic life and reward clipping are keys of the Breakout worlds: here
-a point closes every step already and |reward| <= 1."""
+a point closes every step already and |reward| <= 1.
+
+``train()``, env_type "Pong-device" / "Pong-host" (the record is ``FAMILY`` below): keys ``points_to_win`` (21),
+``max_episode_steps`` (10000), ``opp_skill_num`` / ``opp_skill_den`` (3 / 4), ``frame_skip``, ``sticky_num``, ``sticky_den``
+and ``frame_skip_max``, for the training pool and the evaluation worlds alike; ``episodic_life`` / ``clip_rewards`` are a
+ValueError.  ``prep_fxn="pong_prep"`` (the process pool carries the {0, 1} frames packed, one bit per pixel), 3 actions,
+``action_shift`` 0 unless given, the "Pong" done override applies; evaluation on host ``PongEnv``s."""
 import numpy as np
 
 from . import worlds
-from .worlds import (MAX_FRAME_SKIP, MAX_STICKY_DEN, _M, DeviceWorldPool, HostWorld, _clamp, _env_id0, check_repeat,  # noqa: F401
-                     check_rules, factory_of, hash32, repeat_from_hyps)
+from .worlds import (MAX_FRAME_SKIP, MAX_STICKY_DEN, _M, DeviceRegisterWorldPool, HostWorld, _clamp, _env_id0,  # noqa: F401
+                     check_repeat, check_rules, hash32, repeat_from_hyps)
 
 N_ACTIONS = 3
 W = H = 80
@@ -78,21 +84,6 @@ def check_world(points_to_win=21, max_episode_steps=10000, opp_skill_num=3, opp_
                          f"points_to_win <= {MAX_POINTS}, 1 <= max_episode_steps <= {MAX_EPISODE_STEPS}, 1 <= opp_skill_den "
                          f"<= {MAX_SKILL_DEN}, 0 <= opp_skill_num <= opp_skill_den)")
     return p, m, n, d
-
-
-RULE_KEYS = ("frame_skip_max",)
-
-
-def rules_from_hyps(hyps):
-    """{frame_skip_max} from the hyps (frame_skip where absent); ValueError for episodic_life / clip_rewards"""
-    return worlds.rules_from_hyps(hyps, "Pong", RULE_KEYS)
-
-
-def world_from_hyps(hyps):
-    """(points_to_win, max_episode_steps, opp_skill_num, opp_skill_den) from the hyps; ValueError outside the bounds"""
-    get = lambda k, dflt: dflt if hyps.get(k) is None else hyps[k]
-    return check_world(get("points_to_win", 21), get("max_episode_steps", 10000), get("opp_skill_num", 3),
-                       get("opp_skill_den", 4))
 
 
 class _ActionSpace:
@@ -206,11 +197,7 @@ class PongEnv(HostWorld):
         return pic
 
 
-# picklable ``env_fn``: ``PongFactory(env_id=j, **world)()`` is a ``PongEnv``
-PongFactory = factory_of(PongEnv)
-
-
-class DevicePongPool(DeviceWorldPool):
+class DevicePongPool(DeviceRegisterWorldPool):
     """``n_envs`` Pong worlds in device memory (the Runner's device-pool protocol).  Env j is the world
     ``PongEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames; with ``frame_skip`` / ``sticky_num`` / ``sticky_den``
     other than (1, 0, .) a step is an agent step of a2c_pong_step_skip, with ``frame_skip_max`` above
@@ -218,28 +205,18 @@ class DevicePongPool(DeviceWorldPool):
     ``done = (rew != 0) or real done`` (the Pong override of the reference's runner) and ``reset = real done`` as two tensors.
     ``episode_stats`` counts what the Runner's ``rew_q`` counts for a "Pong" env type: every ``done``, with the reward since
     the last one."""
+    WHAT = "Pong"
     frame_shape = (1, H, W)
 
     def __init__(self, n_envs, device="cuda", seed=0, points_to_win=21, max_episode_steps=10000, opp_skill_num=3,
                  opp_skill_den=4, env_id0=0, frame_skip=1, sticky_num=0, sticky_den=1, frame_skip_max=None):
-        from . import ops
-        self.world = check_world(points_to_win, max_episode_steps, opp_skill_num, opp_skill_den)
-        self.repeat = check_repeat(frame_skip, sticky_num, sticky_den)
-        # None: frame_skip_max at its default -- the entry points above; else the block of a2c_pong_step_rules
-        self.rules = ops.world_rules(*self.repeat, *check_rules(frame_skip, frame_skip_max))
-        self.plain = self.repeat[:2] == (1, 0) and self.rules is None      # today's world: the entry points without frame skip
-        super().__init__(n_envs, device, seed, env_id0, ops.pong_state_bytes(self.world[0]) // 4)
+        world = check_world(points_to_win, max_episode_steps, opp_skill_num, opp_skill_den)
+        super().__init__(n_envs, device, seed, env_id0, world, frame_skip, sticky_num, sticky_den, frame_skip_max)
 
-    def _reset(self):
-        from . import ops
-        ops.pong_reset(self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
 
-    def _step(self, head, out, frames, post, sl):
-        from . import ops
-        if self.rules is not None:
-            fn, extra = ops.pong_step_rules, (self.rules, post)
-        elif post is None:
-            fn, extra = (ops.pong_step, ()) if self.plain else (ops.pong_step_skip, self.repeat)
-        else:
-            fn, extra = (ops.pong_step_post, (post,)) if self.plain else (ops.pong_step_post_skip, (*self.repeat, post))
-        fn(*head, *self.world, frames, self.HW, *out, *extra, self.ep_stats[0:1], self.ep_stats[1:2])
+# picklable ``env_fn``: ``PongFactory(env_id=j, **world)()`` is a ``PongEnv``
+PongFactory = worlds.factory_of(PongEnv)
+FAMILY = worlds.WorldFamily(__name__, "Pong", check_world,
+                            (("points_to_win", 21), ("max_episode_steps", 10000), ("opp_skill_num", 3), ("opp_skill_den", 4)),
+                            "pong_prep", rule_keys=("frame_skip_max",), pong_done=True, frame_bits=True)
+RULE_KEYS, rules_from_hyps, world_from_hyps = FAMILY.rule_keys, FAMILY.rules_from_hyps, FAMILY.world_from_hyps

@@ -45,7 +45,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import families, ops
 from .utils import cuda_if, next_state, sample_action, try_key
 
 
@@ -124,6 +124,22 @@ class HostEnvPool:
         return np.asarray(obs), float(rew), bool(done)
 
 
+def gym_env_pool(hyps, n_envs, seed, serial, action_shift, rew_ema0, action_dim=None):
+    """``n_envs`` gym envs made from the hyps like the reference's n_envs processes (training.py:109-121), env j seeded
+    ``seed + j``: in this process (``serial``), else worker processes behind the pinned pool region -- with ``action_dim``
+    the pool of float action vectors.  The one builder of ``Runner._make_pool`` and ``train()``"""
+    kws = [dict({k: v for k, v in hyps.items() if k != "seed"}, seed=seed + j) for j in range(n_envs)]
+    if serial:
+        envs = [SequentialEnvironment(**kw) for kw in kws]
+        return HostEnvPool(envs, frame_shape=np.asarray(envs[0].prep_obs(np.zeros(envs[0].raw_shape, dtype=np.uint8))).shape)
+    from .hostpool import ProcessEnvPool
+    # pong_prep yields {0,1} uint8 planes (preprocessing.py:15-16): one bit per pixel crosses the host link
+    bits = try_key(hyps, "frame_bits", try_key(hyps, "prep_fxn", None) == "pong_prep")
+    return ProcessEnvPool(SequentialEnvironment, n_envs, env_kwargs=kws, n_workers=try_key(hyps, "n_env_workers", None),
+                          action_shift=action_shift, pong="Pong" in hyps["env_type"], rew_ema0=rew_ema0, frame_bits=bool(bits),
+                          action_dim=action_dim)
+
+
 class _Frames:
     """Where the new frames of one env step are on the device: fp32 (B, HW) or uint8 (B, stride bytes)."""
     __slots__ = ("ptr32", "ptr8", "stride")
@@ -168,12 +184,13 @@ def check_bootstrap_truncated(hyps, pool=None, net=None, datas=None, HW=None):
     key = "bootstrap_truncated"
     env_type = hyps.get("env_type")
     if pool is None:
-        if env_type not in ("Point-device", "CartPole-device", "Pendulum-device"):
+        if env_type not in families.LANE_DEVICE_TYPES:
             raise ValueError(f"a2c_amd: {key} bootstraps time-limit episode ends of the lane worlds' device pools (env_type "
-                             f"'Point-device', 'CartPole-device', 'Pendulum-device'), not {env_type!r}")
+                             f"{', '.join(map(repr, families.LANE_DEVICE_TYPES))}), not {env_type!r}")
     elif not getattr(pool, "reports_trunc", False):
         raise ValueError(f"a2c_amd: {key} needs a device env pool whose step reports the state an episode ended in "
-                         f"(DevicePointPool, DeviceCartPolePool, DevicePendulumPool), not {type(pool).__name__}")
+                         f"({', '.join(families.FAMILIES[n].pool.__name__ for n in families.LANE_WORLDS)}), not "
+                         f"{type(pool).__name__}")
     model = type(net).__name__ if net is not None else hyps.get("model")
     if model is not None and model != "FCModel":
         raise ValueError(f"a2c_amd: {key} covers FCModel (the hidden row a recurrent net's final state needs is zeroed before "
@@ -317,21 +334,8 @@ class Runner:
         """n_envs gym envs like the reference's n_envs processes (training.py:109-121): worker processes
         behind the pinned pool region; ``hyps['env_pool'] == 'serial'`` keeps them in this process."""
         hyps = self.hyps
-        n = int(try_key(hyps, "n_envs", 1))
-        kws = []
-        for j in range(n):
-            kw = {k: v for k, v in hyps.items() if k not in ("seed",)}
-            kw["seed"] = try_key(hyps, "seed", 0) + j
-            kws.append(kw)
-        if try_key(hyps, "env_pool", "process") == "serial":
-            envs = [SequentialEnvironment(**kw) for kw in kws]
-            shape = np.asarray(envs[0].prep_obs(np.zeros(envs[0].raw_shape, dtype=np.uint8))).shape
-            return HostEnvPool(envs, frame_shape=shape)
-        from .hostpool import ProcessEnvPool
-        return ProcessEnvPool(SequentialEnvironment, n, env_kwargs=kws, n_workers=try_key(hyps, "n_env_workers", None),
-                              action_shift=hyps["action_shift"], pong="Pong" in hyps["env_type"],
-                              rew_ema0=-1.0,
-                              frame_bits=bool(try_key(hyps, "frame_bits", try_key(hyps, "prep_fxn", None) == "pong_prep")))
+        return gym_env_pool(hyps, int(try_key(hyps, "n_envs", 1)), try_key(hyps, "seed", 0),
+                            try_key(hyps, "env_pool", "process") == "serial", action_shift=hyps["action_shift"], rew_ema0=-1.0)
 
     def start(self, net):
         """Everything Runner.run does before its loop (runner.py:158-168), for all envs."""
@@ -1498,7 +1502,7 @@ class DeviceStatsRunner:
         if bool(try_key(hyps, "norm_obs", False)) and norm is None:
             raise ValueError("norm_obs: DeviceStatsRunner normalises by the training Runner's block: pass norm=runner.vecnorm")
         if not hasattr(pool, "device_step_post"):
-            raise ValueError("DeviceStatsRunner: a device env pool with device_step_post (Snake / Pong / Breakout / Point "
+            raise ValueError(f"DeviceStatsRunner: a device env pool with device_step_post ({' / '.join(families.FAMILIES)} "
                              "worlds)")
         self.pool, self.uniform_fn, self.keep_actions = pool, uniform_fn, bool(keep_actions)
         self.normal_fn = normal_fn                # continuous nets on a float-action pool: (t, E, 0) -> (E, n) device N(0,1)

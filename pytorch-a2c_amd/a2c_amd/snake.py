@@ -20,10 +20,14 @@ resets itself: the frame returned is the reset frame and ``reset == done``.
 
 Randomness is counter based: draw number i of env e is ``hash32(seed, e, i)`` (below); a free cell is the k-th free cell
 in row-major order with ``k = draw mod n_free``.  The body is a time-to-live map: a cell holds 0 (free), -1 (food) or the
-number of steps it stays occupied (head = length)."""
+number of steps it stays occupied (head = length).
+
+``train()``, env_type "Snake-device" / "Snake-host" (the record is ``FAMILY`` below): the reference's keys ``grid_size`` (15;
+an int or [g, g]), ``unit_size`` (4), ``n_foods`` (2); ``prep_fxn="snake_prep"``, 4 actions; one game frame per step, so
+``frame_skip`` / ``sticky_num`` and the three keys of DESIGN.md section 6i are a ValueError; evaluation on host ``SnakeEnv``s."""
 import numpy as np
 
-from .worlds import _M, DeviceWorldPool, _env_id0, _fin, hash32  # noqa: F401
+from .worlds import _M, DeviceWorldPool, WorldFamily, _env_id0, _fin, factory_of, hash32  # noqa: F401
 
 N_ACTIONS = 4
 DR = (-1, 0, 1, 0)
@@ -41,7 +45,7 @@ def check_world(grid_size, unit_size, n_foods):
     return G, u, nf
 
 
-def world_from_hyps(hyps):
+def _world_from_hyps(hyps):
     """(grid_size, unit_size, n_foods) from the reference's keys (``grid_size`` may be an int or [g, g])"""
     g = hyps.get("grid_size", 15)
     if isinstance(g, (list, tuple)):
@@ -145,16 +149,6 @@ class SnakeEnv:
         return np.ascontiguousarray(pic.repeat(self.u, axis=0).repeat(self.u, axis=1))
 
 
-class SnakeFactory:
-    """picklable ``env_fn`` for ``SequentialEnvironment`` / the env worker processes"""
-
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __call__(self, *a, **k):
-        return SnakeEnv(**self.kw)
-
-
 class DeviceSnakePool(DeviceWorldPool):
     """``n_envs`` Snake worlds in device memory (the Runner's device-pool protocol).  Env j is the world
     ``SnakeEnv(seed, env_id=env_id0 + j, ...)``: same draws, same frames (with ``raw_frames`` also the raw RGB ones, ``rgb``)."""
@@ -183,3 +177,16 @@ class DeviceSnakePool(DeviceWorldPool):
             ops.snake_step(*head, self.G, self.u, self.n_foods, *out, frames, rgb, self.ep_stats)
         else:
             ops.snake_step_post(*head, self.G, self.u, self.n_foods, *out, frames, post, rgb, self.ep_stats)
+
+
+def _frame_shape(world):
+    side = world["grid_size"] * world["unit_size"]
+    return 1, side, side
+
+
+# picklable ``env_fn`` for ``SequentialEnvironment`` / the env worker processes: ``SnakeFactory(env_id=j, **world)()``
+SnakeFactory = factory_of(SnakeEnv)
+# the family record (worlds.WorldFamily): one game frame per step, none of the rule keys of DESIGN.md section 6i
+FAMILY = WorldFamily(__name__, "Snake", check_world, (("grid_size", 15), ("unit_size", 4), ("n_foods", 2)), "snake_prep",
+                     repeats=False, world_from_hyps=_world_from_hyps, frame_shape=_frame_shape)
+world_from_hyps = FAMILY.world_from_hyps

@@ -17,6 +17,8 @@ done.  Frozen (``update=False``): observations by the moments as they stand, not
 """
 import numpy as np
 
+from .families import VECTOR_DEVICE_TYPES
+
 LANES = 256
 MAX_L = 64
 COUNT0 = 1e-4
@@ -103,8 +105,8 @@ def check_runner(hyps, pool, net, stepper, ranks=None):
         raise ValueError(f"{key}: every rank of a sharded run would keep moments of its own envs and they would drift apart; "
                          "running normalisation is for one rank")
     if not hasattr(pool, "device_step_post"):
-        raise ValueError(f"{key}: running normalisation lives in the slot of a DEVICE env pool (Point-device, CartPole-device, "
-                         "Pendulum-device); this is a host env pool")
+        raise ValueError(f"{key}: running normalisation lives in the slot of a DEVICE env pool "
+                         f"({', '.join(VECTOR_DEVICE_TYPES)}); this is a host env pool")
     shape = tuple(pool.frame_shape)
     if len(shape) != 2 or shape[0] != 1 or not 1 <= shape[1] <= MAX_L:
         raise ValueError(f"{key}: running normalisation covers the vector worlds, frame_shape (1, L) with L <= {MAX_L}; this "

@@ -1,10 +1,12 @@
 """What the worlds that can live in HBM (snake.py, pong.py, breakout.py) share on the Python side: the counter-based draws,
 the bounds of frame skip and sticky actions, ``HostWorld`` -- the agent step of the host twins ``PongEnv`` / ``BreakoutEnv`` --
 and ``DeviceWorldPool``, the Runner's device-pool protocol over ``n_envs`` worlds in device memory (the kernels' side:
-csrc/world.h), with ``DeviceLaneWorldPool``, what the pools of the one-lane-per-env worlds (point.py,
-cartpole.py, pendulum.py; csrc/lane_world.h) share beyond it."""
+csrc/world.h), with ``DeviceRegisterWorldPool`` (pong.py, breakout.py) and ``DeviceLaneWorldPool``
+(point.py, cartpole.py, pendulum.py; csrc/lane_world.h), what the pools of each kind share beyond it -- and ``WorldFamily``,
+the record every world module binds as ``FAMILY``: what ``train()`` has to know of a family."""
 import functools
 import math
+import sys
 
 _M = 0xFFFFFFFF
 MAX_FRAME_SKIP, MAX_STICKY_DEN = 8, 1 << 16
@@ -74,6 +76,11 @@ def check_rules(frame_skip=1, frame_skip_max=None, episodic_life=False, clip_rew
 
 
 RULE_KEYS = ("frame_skip_max", "episodic_life", "clip_rewards")
+# the keys among them that shape what a policy is TRAINED on, not the game: evaluation worlds do not get them
+TRAINING_ONLY = ("episodic_life", "clip_rewards")
+# the nets that take a vector observation (models.py): what the vector worlds can be trained with -- by their Gaussian head
+# where the pool has ``float_actions``, by their softmax head elsewhere
+FC_MODELS = ("FCModel", "GRUFCModel")
 
 
 def repeat_from_hyps(hyps, what="Pong"):
@@ -223,6 +230,85 @@ def factory_of(env):
     return functools.partial(WorldFactory, env)
 
 
+class WorldFamily:
+    """What a world module states ONCE about its family, env_type "<name>-device" / "<name>-host" of ``train()``: the
+    ``module`` (its ``__name__``), which binds the host twin ``<name>Env``, the device pool ``Device<name>Pool`` and the
+    picklable env_fn ``<name>Factory`` -- ``env`` / ``pool`` / ``factory`` here, read from the module when they are used, so
+    whoever rebinds one there (a test's recording subclass) is seen; the module's ``check_world`` and ``world_keys``, ((hyps
+    key, default), ...) in the order ``check_world`` takes them; ``prep``, the name of its preprocessor; ``rule_keys``, those
+    of RULE_KEYS it takes; ``repeats``: it takes frame_skip / sticky_num / sticky_den; ``models``: the nets it can be trained
+    with (None: any), which ``takes`` puts into words; ``pong_done``: the "Pong" done override; ``frame_bits``: {0, 1} frames
+    cross the process pool one bit per pixel; ``device_prep``: the device preprocessor its raw frames can be left to.  What
+    the pool class says (``float_actions``, ``n_act``, ``frame_shape``, ``reports_trunc``) is read from the pool class."""
+
+    def __init__(self, module, name, check_world, world_keys, prep, rule_keys=(), repeats=True, models=None, takes=None,
+                 pong_done=False, frame_bits=False, device_prep=None, world_from_hyps=None, frame_shape=None):
+        self.module, self.name, self.check_world, self.world_keys = sys.modules[module], name, check_world, tuple(world_keys)
+        self.prep, self.rule_keys, self.repeats, self.models, self.takes = prep, tuple(rule_keys), repeats, models, takes
+        self.pong_done, self.frame_bits, self.device_prep = pong_done, frame_bits, device_prep
+        if world_from_hyps is not None:     # (Snake: the reference's spellings of its keys)
+            self.world_from_hyps = world_from_hyps
+        if frame_shape is not None:         # (Snake: the frame is as large as the world)
+            self.frame_shape = frame_shape
+
+    env = property(lambda self: getattr(self.module, self.name + "Env"))
+    pool = property(lambda self: getattr(self.module, "Device" + self.name + "Pool"))
+    factory = property(lambda self: getattr(self.module, self.name + "Factory"))
+    float_actions = property(lambda self: bool(getattr(self.pool, "float_actions", False)))
+    n_act = property(lambda self: self.pool.n_act if self.float_actions else self.env.action_space.n)
+    reports_trunc = property(lambda self: self.pool.reports_trunc)
+    vector = property(lambda self: len(getattr(self.pool, "frame_shape", ())) == 2)       # (1, L) observations
+
+    def frame_shape(self, world):
+        """the frames of ``world`` (its kwargs) as the device pool writes them"""
+        return self.pool.frame_shape
+
+    def world_from_hyps(self, hyps):
+        """the checked world, in the order of ``world_keys``, from the hyps (defaults where absent or None); ValueError
+        outside the bounds"""
+        return self.check_world(*(d if hyps.get(k) is None else hyps[k] for k, d in self.world_keys))
+
+    def rules_from_hyps(self, hyps):
+        """{key: value} of ``rule_keys`` from the hyps (frame_skip, False, False where absent); ValueError outside the bounds
+        and for a key of RULE_KEYS the family does not take"""
+        return rules_from_hyps(hyps, self.name, self.rule_keys)
+
+    def repeat_from_hyps(self, hyps):
+        """(frame_skip, sticky_num, sticky_den) from the hyps (1, 0, 1 where absent); ValueError outside the bounds"""
+        return repeat_from_hyps(hyps, self.name)
+
+    def check_hyps(self, hyps, host):
+        """what ``train()`` refuses for this family before anything is written or allocated (``host``: the "-host" env type)
+        -> the rules: frame skip where the family has none, the keys of RULE_KEYS it does not take or that are out of bounds,
+        a net that cannot play it, an env pool that cannot carry its actions"""
+        if not self.repeats and self.repeat_from_hyps(hyps)[:2] != (1, 0):
+            raise ValueError(f"a2c_amd: frame_skip / sticky_num are keys of the Pong and Breakout worlds: the {self.name} worlds "
+                             "play one game frame per step")
+        rules = self.rules_from_hyps(hyps)
+        cont = self.float_actions
+        if self.models is not None:
+            wrong = bool(hyps.get("is_discrete", not cont)) == cont
+            if hyps.get("model") not in self.models or wrong:
+                takes = self.takes or f"{self.n_act} float action{'s' if self.n_act > 1 else ''}"
+                raise ValueError(f"a2c_amd: the {self.name} worlds take {takes}: model {' / '.join(self.models)} with "
+                                 f"is_discrete={not cont}, not {hyps.get('model')!r}"
+                                 + (f" with is_discrete={cont}" if wrong else ""))
+        if cont and host and hyps.get("env_pool") not in (None, "serial", "process_f32"):
+            # float actions: no int32 process pool
+            raise ValueError(f"a2c_amd: env_type='{self.name}-host' steps behind env_pool='serial' (the default) or "
+                             "'process_f32' (the int process pool and the thread pool carry int32 actions)")
+        return rules
+
+    def raw_frames(self, hyps, host, serial):
+        """hyps device_prep: do the workers hand on the RAW frames (null_prep) for the device to crop / stride them?"""
+        raw = self.device_prep is not None and hyps.get("device_prep") is not None
+        if raw and (hyps["device_prep"] != self.device_prep or not host or serial):
+            raise ValueError(f"a2c_amd: device_prep on {self.name} worlds is {self.device_prep!r}, on "
+                             f"env_type='{self.name}-host' behind the process env pool (the device worlds write prepped frames "
+                             "themselves)")
+        return raw
+
+
 class DeviceWorldPool:
     """``n_envs`` worlds in device memory (the Runner's device-pool protocol: ``start`` / ``device_step`` /
     ``device_step_post``).  ``needs_actions``: the Runner hands ``device_step`` the address and stride of the int64 actions the
@@ -310,6 +396,44 @@ class DeviceWorldPool:
         if n:
             self.ep_stats.zero_()
         return n, s
+
+
+class DeviceRegisterWorldPool(DeviceWorldPool):
+    """The pools of the register worlds with frame skip (csrc/world.h: pong.py, breakout.py), whose library calls differ in
+    their name and in the world's parameters alone.  A subclass sets ``WHAT`` (its name in messages; lower-cased, the prefix
+    of ``ops.<what>_state_bytes / _reset / _step*``), ``FLAGS`` (it takes episodic_life / clip_rewards) and ``frame_shape``;
+    its ``__init__`` hands over its checked ``world`` tuple, the parameters in the order the library takes them.  A plain world
+    calls _step / _step_post, one with frame skip or sticky actions _step_skip / _step_post_skip, one with a rules block
+     _step_rules: the entry points are looked up once, here."""
+    WHAT, FLAGS = "World", False
+
+    def __init__(self, n_envs, device, seed, env_id0, world, frame_skip, sticky_num, sticky_den, frame_skip_max,
+                 episodic_life=False, clip_rewards=False):
+        from . import ops
+        self.world = world
+        self.repeat = check_repeat(frame_skip, sticky_num, sticky_den, self.WHAT)
+        # None: every key of section 6i at its default -- the entry points without it; else the block of _step_rules
+        self.rules = ops.world_rules(*self.repeat, *check_rules(frame_skip, frame_skip_max, episodic_life, clip_rewards,
+                                                                self.WHAT, flags=self.FLAGS))
+        self.plain = self.repeat[:2] == (1, 0) and self.rules is None      # the world of one game frame per step
+        op = {f: getattr(ops, f"{self.WHAT.lower()}_{f}") for f in ("state_bytes", "reset", "step", "step_skip", "step_post",
+                                                                    "step_post_skip", "step_rules")}
+        self._reset_op, self._rules_op = op["reset"], op["step_rules"]
+        self._step_op, self._post_op = (op["step"], op["step_post"]) if self.plain else (op["step_skip"], op["step_post_skip"])
+        self._skip = () if self.plain else self.repeat
+        super().__init__(n_envs, device, seed, env_id0, op["state_bytes"](self.world[0]) // 4)
+
+    def _reset(self):
+        self._reset_op(self.state, self.B, self.env_id0, self.seed, *self.world, self.frames, self.HW)
+
+    def _step(self, head, out, frames, post, sl):
+        if self.rules is not None:
+            fn, extra = self._rules_op, (self.rules, post)
+        elif post is None:
+            fn, extra = self._step_op, self._skip
+        else:
+            fn, extra = self._post_op, (*self._skip, post)
+        fn(*head, *self.world, frames, self.HW, *out, *extra, self.ep_stats[0:1], self.ep_stats[1:2])
 
 
 class DeviceLaneWorldPool(DeviceWorldPool):
