@@ -510,6 +510,40 @@ int a2c_gauss_nll_fwd_bwd(const float *heads, int64_t ld_heads, const float *val
                           float val_coef, float entr_coef, float *dheads, int64_t ldd, float *dvals,
                           int64_t dval_stride, double *loss_sums, double *reduce_scratch, a2c_stream_t stream);
 
+/* The clipped-ratio (PPO) loss of the multi-epoch update (hyps["ppo_epochs"] >= 2; nothing in the
+ * reference): a2c_loss_fwd_bwd (a2c_ppo_loss_fwd_bwd) and a2c_gauss_nll_fwd_bwd (a2c_gauss_ppo_fwd_bwd) with the policy
+ * term replaced by the clipped surrogate against the log-probabilities logp_old (n_local doubles) of the policy that
+ * collected the rows.  logp_i: lsm[act] (the -1 -> last action rule of a2c_loss_fwd_bwd), or the Gaussian logp_i above,
+ * both evaluated in fp64 from the fp32 inputs (the ratio's exponent; the gradients stay the sibling's fp32 formulas);
+ * w_i: the advantage, normalised when adv_sums != NULL.
+ *   record == 1 (the first epoch: the parameters are the rollout's): logp_old[i] = logp_i is WRITTEN and r_i = 1: dlogits /
+ *     dheads, dvals, loss_sums[1] and loss_sums[2] are bit for bit what the sibling writes (the surrogate's gradient at
+ *     r = 1 is the policy gradient); loss_sums[0] = sum w_i, loss_sums[3] = loss_sums[4] = 0.
+ *   record == 0: logp_old is READ; in fp64 r_i = exp(logp_i - logp_old[i]),
+ *     surr_i = min(r_i w_i, clamp(r_i, 1 - clip, 1 + clip) w_i),
+ *     keep_i = !((w_i > 0 && r_i > 1 + clip) || (w_i < 0 && r_i < 1 - clip));
+ *     the sibling's gradient formulas with g_i = -pi_coef w_i invN replaced by float(g_i r_i) where keep_i and by
+ *     exactly 0 where not (a select, not a product: an overflowed r_i on a clipped row makes no NaN); the entropy and value
+ *     parts unchanged;  loss_sums[0..4] = sum surr_i, sum (V - R)^2, the sibling's entropy sum, sum (1 - keep_i),
+ *     sum ((r_i - 1) - log r_i).  A row with r_i == 1 gets the record-mode outputs bit for bit.
+ * Pi_Loss = -pi_coef loss_sums[0] / n_global as for the sibling; loss_sums[3] / n_global is the clipped fraction and
+ * loss_sums[4] / n_global an estimate of KL(old || new).  Deterministic (five fp64 partials per workgroup in
+ * reduce_scratch: at most 512 workgroups of 256 rows, grid-stride beyond).  A2C_ERR_ARG, nothing launched: whatever the
+ * sibling rejects, clip not finite or <= 0, record other than 0 / 1, logp_old == NULL; n_local == 0 zeroes the five
+ * loss_sums and writes nothing else.                                                                                    */
+int a2c_ppo_loss_fwd_bwd(const float *logits, int64_t ld_logits, const float *vals, int64_t val_stride,
+                         const int64_t *actions, const float *advs, const float *returns,
+                         const double *adv_sums, int64_t n_local, int64_t n_global, int A,
+                         float pi_coef, float val_coef, float entr_coef, float clip, int record, double *logp_old,
+                         float *dlogits, int64_t ldd, float *dvals, int64_t dval_stride, double *loss_sums,
+                         double *reduce_scratch, a2c_stream_t stream);
+int a2c_gauss_ppo_fwd_bwd(const float *heads, int64_t ld_heads, const float *vals, int64_t val_stride,
+                          const float *actions, int64_t ld_act, const float *advs, const float *returns,
+                          const double *adv_sums, int64_t n_local, int64_t n_global, int n, float pi_coef,
+                          float val_coef, float entr_coef, float clip, int record, double *logp_old, float *dheads,
+                          int64_t ldd, float *dvals, int64_t dval_stride, double *loss_sums, double *reduce_scratch,
+                          a2c_stream_t stream);
+
 /* ------------------------------------------------------------------ a6: dense layers
  * C[M,N] = (accumulate ? C : 0) + opA(A)[M,K] * opB(B)[K,N] (+ bias[N]) ; then optional ReLU ; then optional
  * multiply by (mask[m*ldmask+n] > 0) (the ReLU derivative of the layer below, fused into

@@ -129,6 +129,10 @@ SIGNATURES = {
                                         c_float, c_float, P, c_int64, P, c_int64, P, P]),
     "a2c_gauss_nll_fwd_bwd": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, c_int64, c_int64, c_int, c_float,
                                        c_float, c_float, P, c_int64, P, c_int64, P, P, P]),
+    "a2c_ppo_loss_fwd_bwd": (c_int, [P, c_int64, P, c_int64, P, P, P, P, c_int64, c_int64, c_int, c_float, c_float,
+                                      c_float, c_float, c_int, P, P, c_int64, P, c_int64, P, P, P]),
+    "a2c_gauss_ppo_fwd_bwd": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, c_int64, c_int64, c_int, c_float,
+                                       c_float, c_float, c_float, c_int, P, P, c_int64, P, c_int64, P, P, P]),
     "a2c_gemm_ws_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "a2c_gemm_x9_ws_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "a2c_gemm_x6_image_bytes": (c_size_t, [c_int64, c_int64]),

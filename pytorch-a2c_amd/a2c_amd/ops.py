@@ -775,6 +775,41 @@ def gauss_nll_fwd_bwd(heads, vals, actions, advs, returns, adv_sums, n_global, n
           "a2c_gauss_nll_fwd_bwd")
 
 
+def ppo_loss_fwd_bwd(logits, vals, actions, advs, returns, adv_sums, n_global, pi_coef, val_coef, entr_coef, clip, record,
+                     logp_old, dlogits, dvals, loss_sums, st=None, scratch=None):
+    """loss_fwd_bwd with the clipped-ratio (PPO) policy term (a2c_ppo_loss_fwd_bwd; the row rule: ``ppo_rows_host``):
+    record = True writes logp_old (N,) float64 and the gradients of loss_fwd_bwd, record = False reads it; loss_sums (5,)"""
+    _chk(logits, "logits", contig=False); _chk(vals, "vals", contig=False)
+    _chk(actions, "actions", torch.int64)
+    _chk(advs, "advs"); _chk(returns, "returns"); _chk(dlogits, "dlogits", contig=False)
+    _chk(dvals, "dvals", contig=False); _chk(loss_sums, "loss_sums", torch.float64); _chk(logp_old, "logp_old", torch.float64)
+    n, A = logits.shape
+    st = st if st is not None else stream()
+    check(lib().a2c_ppo_loss_fwd_bwd(_p(logits), logits.stride(0), _p(vals), vals.stride(0), _p(actions), _p(advs),
+                                     _p(returns), _p(adv_sums), n, n_global, A, float(pi_coef), float(val_coef),
+                                     float(entr_coef), float(clip), int(record), _p(logp_old), _p(dlogits), dlogits.stride(0),
+                                     _p(dvals), dvals.stride(0), _p(loss_sums),
+                                     _p(scratch if scratch is not None else reduce_scratch(logits.device, st)), st),
+          "a2c_ppo_loss_fwd_bwd")
+
+
+def gauss_ppo_fwd_bwd(heads, vals, actions, advs, returns, adv_sums, n_global, n, pi_coef, val_coef, entr_coef, clip, record,
+                      logp_old, dheads, dvals, loss_sums, st=None, scratch=None):
+    """gauss_nll_fwd_bwd with the clipped-ratio (PPO) policy term (a2c_gauss_ppo_fwd_bwd; the row rule: ``ppo_rows_host``):
+    record = True writes logp_old (N,) float64 and the gradients of gauss_nll_fwd_bwd, record = False reads it; loss_sums
+    (5,); only stride(0) of the 2-D arguments is used"""
+    _chk(heads, "heads", contig=False); _chk(vals, "vals", contig=False); _chk(actions, "actions", contig=False)
+    _chk(advs, "advs"); _chk(returns, "returns"); _chk(logp_old, "logp_old", torch.float64)
+    _chk(dheads, "dheads", contig=False); _chk(dvals, "dvals", contig=False); _chk(loss_sums, "loss_sums", torch.float64)
+    st = st if st is not None else stream()
+    check(lib().a2c_gauss_ppo_fwd_bwd(_p(heads), heads.stride(0), _p(vals), vals.stride(0), _p(actions), actions.stride(0),
+                                      _p(advs), _p(returns), _p(adv_sums), heads.shape[0], n_global, n, float(pi_coef),
+                                      float(val_coef), float(entr_coef), float(clip), int(record), _p(logp_old), _p(dheads),
+                                      dheads.stride(0), _p(dvals), dvals.stride(0), _p(loss_sums),
+                                      _p(scratch if scratch is not None else reduce_scratch(heads.device, st)), st),
+          "a2c_gauss_ppo_fwd_bwd")
+
+
 # ---------------------------------------------------------------- dense
 def pick_splitk(M, N, K, target_wgs=512, min_k=32):
     min_k = int(os.environ.get("A2C_SPLITK_MIN_K", min_k))
@@ -1565,6 +1600,20 @@ def trunc_bootstrap_host(x, truncs, vfin, gamma):
     t = np.float32(gamma) * truncs
     with np.errstate(invalid="ignore", over="ignore"):
         return np.where(t != 0, x + t * vfin, x).astype(np.float32)
+
+
+def ppo_rows_host(logp, logp_old, w, clip):
+    """the row rule of the two clipped-ratio loss kernels in NumPy float64 (clip as the float32 the kernels receive):
+    r = exp(logp - logp_old), surr = min(r w, clamp(r, 1 - clip, 1 + clip) w) and keep = the clip does not bind, i.e.
+    not (w > 0 and r > 1 + clip or w < 0 and r < 1 - clip): where keep is False d surr / d logp = 0 and the kernels write a
+    policy gradient of exactly zero -> (r, surr, keep)"""
+    logp, logp_old, w = (np.asarray(v, dtype=np.float64) for v in (logp, logp_old, w))
+    c = float(np.float32(clip))
+    with np.errstate(over="ignore", invalid="ignore"):
+        r = np.exp(logp - logp_old)
+        surr = np.minimum(r * w, np.clip(r, 1.0 - c, 1.0 + c) * w)
+    keep = ~(((w > 0) & (r > 1.0 + c)) | ((w < 0) & (r < 1.0 - c)))
+    return r, surr, keep
 
 
 # ---------------------------------------------------------------- running normalisation (csrc/vecnorm.hip)

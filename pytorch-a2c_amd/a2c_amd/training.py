@@ -25,7 +25,7 @@ from . import models, preprocessing, vecnorm
 from .families import DEVICE_TYPES, FAMILIES, VECTOR_WORLDS, family_of
 from .runner import (DeviceStatsRunner, HostEnvPool, Runner, SequentialEnvironment, StatsRunner,
                      check_bootstrap_truncated, gym_env_pool)
-from .updater import Updater, gauss_loss_mode
+from .updater import Updater, gauss_loss_mode, ppo_refusal, ppo_settings
 from .worlds import TRAINING_ONLY
 from .utils import cuda_if, deque_maxmin, try_key
 
@@ -33,7 +33,7 @@ DEFAULTS = dict(n_frame_stack=4, n_rollouts=None, n_past_rews=25, h_size=256, lr
                 gamma=.99, gamma_high=.995, val_coef=.5, entr_coef=.005, entr_coef_low=.001, pi_coef=1.0, max_norm=.5,
                 resume=False, render=False, decay_lr=False, decay_entr=False, use_nstep_rets=False, norm_advs=True,
                 use_bnorm=False, use_bptt=False, optim_type="RMSprop", n_test_eps=15, max_tsteps=4e7,
-                gauss_loss="reference", bootstrap_truncated=False)
+                gauss_loss="reference", bootstrap_truncated=False, ppo_epochs=1, ppo_clip=0.2)
 
 
 def get_exp_num(main_path, exp_name):
@@ -85,8 +85,15 @@ def _complete_hyps(hyps, env_fn, eval_env):
     # known to be discrete (a device world's family, an env_fn's is_discrete key; a gym env's space is only known from the
     # probe, where the Updater refuses it)
     fam = family_of(hyps.get("env_type")) if env_fn is None else None
-    gauss_loss_mode(hyps, (not fam.float_actions) if fam is not None else
-                    (bool(try_key(hyps, "is_discrete", True)) if env_fn is not None else None))
+    discrete = ((not fam.float_actions) if fam is not None else
+                (bool(try_key(hyps, "is_discrete", True)) if env_fn is not None else None))
+    gauss_loss_mode(hyps, discrete)
+    # ppo_epochs / ppo_clip: bad values, and for ppo_epochs >= 2 what hyps already tells -- a net other
+    # than FCModel / GRUFCModel, a continuous action space under the reference's Gaussian loss; the Updater refuses the rest
+    model = hyps.get("model")
+    why = ppo_refusal(ppo_settings(hyps)[0], model if isinstance(model, str) else None, discrete, hyps["gauss_loss"])
+    if why is not None:
+        raise ValueError(why)
     # bootstrap_truncated: everything but the lane worlds' device pools under FCModel
     if try_key(hyps, "bootstrap_truncated", False):
         if env_fn is not None:
@@ -274,6 +281,13 @@ def train(_, hyps, verbose=True, env_fn=None, eval_env=None, max_epochs=None, un
     rollout buffer) and the update adds gamma * V of it to the step's reward and delta before the scan.  "Point-device",
     "CartPole-device" and "Pendulum-device" with FCModel only (anything else -- GRUFCModel, the picture worlds, the ``-host``
     env types, gym envs, an ``env_fn`` -- is a ValueError naming the key, before anything is written); evaluation is untouched.
+    ``hyps["ppo_epochs"]`` = K (int >= 1; default 1: everything as it was) and ``hyps["ppo_clip"]``
+    (float > 0, default 0.2): with K >= 2 every rollout is used for K gradient steps on the same rows, advantages and
+    returns instead of one -- the first the plain policy-gradient step, which also records every row's log-probability, the
+    later ones under PPO's clipped-ratio objective against it (one whole-batch step per epoch: no minibatches, no value
+    clipping, no KL early stopping); ``info`` gains ``ClipFrac`` and ``ApproxKL`` of the last epoch.  FCModel and GRUFCModel,
+    discrete actions or Gaussian ones under ``gauss_loss="exact"``, one GPU (anything else is a ValueError naming the key);
+    the rollout, the worlds and the evaluation are untouched.
     Returns the best evaluation reward."""
     hyps, fam, rules, norm = _complete_hyps(hyps, env_fn, eval_env)
     hyps["exp_num"] = get_exp_num(hyps["main_path"], hyps["exp_name"])

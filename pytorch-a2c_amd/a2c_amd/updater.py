@@ -12,6 +12,7 @@ final read-back of five scalars:
   loss forward+backward, and no all-reduce) -> model backward into the flat gradient
   arena -> [RCCL all-reduce when sharded] -> grad-norm reduction -> fused clip + optimiser step (optim.OPTIMIZERS).
 """
+import math
 import sys
 
 import torch
@@ -39,6 +40,34 @@ def gauss_loss_mode(hyps, is_discrete=None):
         raise ValueError("a2c_amd: hyps['gauss_loss'] = 'exact' is the loss of the continuous (Gaussian) nets: it needs "
                          "is_discrete=False")
     return mode
+
+
+def ppo_settings(hyps):
+    """hyps["ppo_epochs"] (int >= 1, default 1: today's one gradient step per rollout) and hyps["ppo_clip"] (float > 0,
+    default 0.2) of the clipped multi-epoch update -> (epochs, clip); ValueError naming the key"""
+    epochs, clip = try_key(hyps, "ppo_epochs", 1), try_key(hyps, "ppo_clip", 0.2)
+    if isinstance(epochs, bool) or not isinstance(epochs, int) or epochs < 1:
+        raise ValueError(f"a2c_amd: hyps['ppo_epochs'] is an int >= 1, not {epochs!r}")
+    if isinstance(clip, bool) or not isinstance(clip, (int, float)) or not math.isfinite(clip) or clip <= 0:
+        raise ValueError(f"a2c_amd: hyps['ppo_clip'] is a finite float > 0, not {clip!r}")
+    return epochs, float(clip)
+
+
+PPO_NETS = ("FCModel", "GRUFCModel")
+
+
+def ppo_refusal(epochs, net_name, is_discrete, gauss_loss):
+    """why hyps["ppo_epochs"] = epochs >= 2 cannot run on this net / loss (None: it can); net_name or is_discrete None = not
+    known yet"""
+    if epochs < 2:
+        return None
+    if net_name is not None and net_name not in PPO_NETS:
+        return (f"a2c_amd: hyps['ppo_epochs'] >= 2 covers FCModel and GRUFCModel (the pixel nets' first forward comes from "
+                f"the rollout's stash), not {net_name}")
+    if is_discrete is not None and not is_discrete and gauss_loss != "exact":
+        return ("a2c_amd: hyps['ppo_epochs'] >= 2 on a continuous net needs hyps['gauss_loss'] = 'exact': the reference's "
+                "Gaussian loss is not a policy gradient, so it has no ratio to clip")
+    return None
 
 
 class _CutShard:
@@ -96,7 +125,7 @@ class _GraphedUpdate:
         # mark_dirty cleared all of the stash, not only its rows)
         net._dirty = dirty
         net._set_route_state(route)
-        upd.optim._steps -= 1
+        upd.optim._steps -= upd.ppo_epochs      # (one optimiser step per epoch was counted while capturing)
 
     def _stale_route(self):
         """the rollout before this replay left the net on another route than the captured one (a partial or split rollout: no
@@ -137,7 +166,7 @@ class _GraphedUpdate:
             g.replay()
             if i < len(self.colls):
                 upd.shard.allreduce_(self.colls[i])
-        upd.optim._steps += 1
+        upd.optim._steps += upd.ppo_epochs
         upd.net.mark_dirty()
         # (the captured tail re-derived the inference weights: _enqueue_update's net._refresh -- unless the net derives more now)
         upd.net._dirty = self._stale_prep()
@@ -155,7 +184,7 @@ class _GraphedUpdate:
             g.replay()
             if i < len(self.colls):
                 upd.shard.allreduce_(self.colls[i])
-        upd.optim._steps += 1
+        upd.optim._steps += upd.ppo_epochs
         upd.net.mark_dirty()
         upd.net._dirty = self._stale_prep()
         return upd._post_async(self.dev, self.n_global)
@@ -179,6 +208,13 @@ class Updater:
             raise ValueError("a2c_amd: bootstrap_truncated covers FCModel (the hidden row a recurrent net's final state needs "
                              f"is zeroed before anyone can read it), not {type(net).__name__}")
         self.shard = shard if shard is not None else Shard()
+        # the clipped multi-epoch update: ppo_epochs == 1 is the one-step update, untouched
+        self.ppo_epochs, self.ppo_clip = ppo_settings(hyps)
+        why = ppo_refusal(self.ppo_epochs, type(net).__name__, self.is_discrete, self.gauss_loss)
+        if why is None and self.ppo_epochs > 1 and self.shard.active:
+            why = "a2c_amd: hyps['ppo_epochs'] >= 2 does not cover a sharded update (an active Shard)"
+        if why is not None:
+            raise ValueError(why)
         self.optim = self.new_optim(hyps["lr"])
         self.info = {}
         self.flat_scan_fallback = False     # last update: a slot did not end with done == 1 -> flat scans were used
@@ -214,6 +250,12 @@ class Updater:
             if not self.is_discrete and self.gauss_loss == "reference":
                 # the six Gaussian loss sums (a2c_gauss_loss_sums), all-reduced when sharded
                 b["gsums"] = torch.zeros(6, dtype=torch.float64, device=dev)
+            if self.ppo_epochs > 1:
+                # the behaviour policy's log-probability of every row (epoch 0 writes it), the five loss sums of the
+                # clipped loss, and the update's scalars + [sum (1 - keep), sum ((r - 1) - log r)] for the ONE read-back
+                b.update(logp_old=torch.zeros(N, dtype=torch.float64, device=dev),
+                         ppo_sums=torch.zeros(5, dtype=torch.float64, device=dev),
+                         out8=torch.zeros(8, dtype=torch.float64, device=dev))
             self._bufs = b
         return b
 
@@ -292,6 +334,9 @@ class Updater:
             ops.moments(advs, adv_sums, st, scratch=b["scratch"])
             sh.allreduce_(adv_sums)
 
+        if self.ppo_epochs > 1:
+            return self._ppo_epochs(shared_data, states, dones, actions, advs, rets, adv_sums, N, R, T, n_global, b, st)
+
         db, dl, dv = net.dheads("train", N)
         if self.is_discrete:
             ops.loss_fwd_bwd(logits, vals, actions, advs, rets, adv_sums, n_global, try_key(hyps, "pi_coef", 1.0),
@@ -336,6 +381,52 @@ class Updater:
         ops.check(ops.lib().a2c_pack_update_scalars(stats[2:5].data_ptr(), self.optim.grad_norm().data_ptr(),
                                                     b["err"].data_ptr(), b["out5"].data_ptr(), st), "a2c_pack_update_scalars")
         return b["out5"], n_global
+
+    def _ppo_epochs(self, shared_data, states, dones, actions, advs, rets, adv_sums, N, R, T, n_global, b, st):
+        """hyps["ppo_epochs"] = K >= 2, from behind the advantage moments of _enqueue_update on: K
+        times [clipped loss -> backward -> clip + optimiser step] on the same rows, advantages and returns.  Epoch 0 uses
+        the forward that is already there and RECORDS every row's log-probability (the parameters are the rollout's: its
+        ratio is 1 and its gradient the policy gradient); the later epochs run the forward again and read it."""
+        hyps, net = self.hyps, self.net
+        recurrent = "h_states" in shared_data
+        use_bptt = recurrent and bool(hyps["use_bptt"])
+        h_states = self._dev(shared_data["h_states"]) if recurrent else None
+        S = states[0].numel()
+        sums = b["ppo_sums"]
+        coefs = (try_key(hyps, "pi_coef", 1.0), hyps["val_coef"], hyps["entr_coef"], self.ppo_clip)
+        for epoch in range(self.ppo_epochs):
+            if epoch:
+                if use_bptt:
+                    net.bptt_forward(states, h_states, dones, R, T, "train", st)
+                elif recurrent:
+                    net._refresh(st)
+                    net._fwd(states.data_ptr(), S, N, "train", st, True, h_in=h_states)
+                else:
+                    net._refresh(st)
+                    net._fwd(states.data_ptr(), S, N, "train", st, True)
+            hb, logits, vals = net._heads("train", N)
+            db, dl, dv = net.dheads("train", N)
+            if self.is_discrete:
+                ops.ppo_loss_fwd_bwd(logits, vals, actions, advs, rets, adv_sums, n_global, *coefs, epoch == 0, b["logp_old"],
+                                     dl, dv, sums, st, scratch=b["scratch"])
+            else:
+                ops.gauss_ppo_fwd_bwd(logits, vals, actions, advs, rets, adv_sums, n_global, net.output_space, *coefs,
+                                      epoch == 0, b["logp_old"], dl, dv, sums, st, scratch=b["scratch"])
+            if use_bptt:
+                net.bptt_backward(states, dones, R, T, "train", st)
+            else:
+                net._bwd(states.data_ptr(), S, N, "train", st)
+            net._arena.attach_grads()
+            with ops.span("clip_optimizer"):
+                self.optim.step(max_norm=hyps["max_norm"], st=st)
+            self.optim.zero_grad()
+        net._refresh(st)
+        # the last epoch's five scalars as in _enqueue_update, the clip count and the KL sum behind them: one vector, one read
+        out = b["out8"]
+        ops.check(ops.lib().a2c_pack_update_scalars(sums.data_ptr(), self.optim.grad_norm().data_ptr(), b["err"].data_ptr(),
+                                                    out.data_ptr(), st), "a2c_pack_update_scalars")
+        out[5:7].copy_(sums[3:5])
+        return out, n_global
 
     def _bootstrap_truncated(self, shared_data, states, rewards, deltas, N, b, st):
         """hyps["bootstrap_truncated"], all on the update's stream, before the scan: the state every
@@ -425,6 +516,9 @@ class Updater:
         self.norm = float(host[3])
         self.info = {"Loss": pi_loss + val_loss - entr_loss, "Pi_Loss": pi_loss, "ValLoss": val_loss,
                      "Entropy": entr_loss, "GradNorm": self.norm}
+        if self.ppo_epochs > 1:         # the last epoch's: the share of rows the clip stopped, and mean((r - 1) - log r)
+            self.info["ClipFrac"] = float(host[5]) / n_global
+            self.info["ApproxKL"] = float(host[6]) / n_global
         return self.info
 
     def _norm_returns(self, rets, stats, n_global, st):

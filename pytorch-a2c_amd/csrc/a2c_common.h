@@ -82,6 +82,25 @@ __device__ __forceinline__ void grid_sum_ordered(const double (&v)[NV], double* 
   if (threadIdx.x == 0) *reinterpret_cast<unsigned int*>(scratch) = 0u;
 }
 
+// The clipped-ratio (PPO) row rule of a2c_ppo_loss_fwd_bwd / a2c_gauss_ppo_fwd_bwd (ops.ppo_rows_host is its host statement),
+// in fp64: d = logp - logp_old, r = e^d, surr = min(r w, clamp(r, 1 - clip, 1 + clip) w), keep = the clip does not bind
+// (d surr / d logp != 0 for w != 0), kl = (r - 1) - log r >= 0.  Five partials per workgroup: a grid cap of their own.
+#define A2C_PPO_MAX_BLOCKS 512
+static_assert(8 + 5 * A2C_PPO_MAX_BLOCKS <= A2C_REDUCE_SCRATCH_DOUBLES, "ppo loss sums: reduce scratch too small");
+struct PpoRow {
+  double r, surr, kl;
+  bool keep;
+};
+__device__ __forceinline__ PpoRow ppo_row(double d, float w, float clip) {
+  PpoRow p;
+  const double lo = 1.0 - (double)clip, hi = 1.0 + (double)clip, wd = (double)w;
+  p.r = exp(d);
+  p.surr = fmin(p.r * wd, fmin(fmax(p.r, lo), hi) * wd);
+  p.keep = !((w > 0.f && p.r > hi) || (w < 0.f && p.r < lo));
+  p.kl = expm1(d) - d;
+  return p;
+}
+
 // Small device buffers (error flags, reduction sums; <= 256 B, 4-byte multiples) are cleared by a one-wave kernel,
 // not by hipMemsetAsync: as a NODE of a captured hipGraph the memset was observed to leave 0x01010101 in a
 // 4-byte flag on some replays (ROCm 7.2, gfx950), which a kernel node never does.

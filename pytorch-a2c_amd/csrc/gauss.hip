@@ -165,6 +165,46 @@ __global__ __launch_bounds__(256) void gauss_fwd_bwd_kernel(const float* __restr
 // loss_kernel (loss.hip): every row's gradient needs only that row and the advantage statistics, so there is no first
 // launch for batch-wide sums.  The row's two sums over the action dims are kept in fp64 (u^2 reaches 1e8 on a tiny-sigma
 // row and would swallow the log sigma terms in fp32); the gradients are fp32.
+constexpr double kHalfLog2Pi = 0.91893853320467274178;
+
+// one row's gradients [dmu | draw] from its policy weight gpi (-pi_coef w / N; times the ratio, or 0: gauss_ppo_kernel) and
+// gen = entr_coef / N; su2 = sum_j u^2, sls = sum_j log sigma.  The ONE row body of gauss_nll_kernel and gauss_ppo_kernel.
+__device__ __forceinline__ void gauss_nll_row(const float* __restrict__ row, const float* __restrict__ act, int n, float gpi,
+                                              float gen, float* __restrict__ drow, double& su2, double& sls) {
+  su2 = 0.0;
+  sls = 0.0;
+  for (int j = 0; j < n; ++j) {
+    const float raw = row[n + j];
+    const float sg = gauss_sigma(raw);
+    const float inv_s = 1.f / sg;
+    const float u = (act[j] - row[j]) * inv_s;
+    const float dsig = (gpi * (u * u - 1.f) - gen) * inv_s;
+    float draw = dsig;
+    if (!(raw > 20.f)) {               // softplus backward: g * z / (z + 1), z = exp(raw)
+      const float z = expf(raw);
+      draw = dsig * z / (z + 1.f);
+    }
+    drow[j] = gpi * u * inv_s;
+    drow[n + j] = draw;
+    su2 += (double)(u * u);
+    sls += (double)logf(sg);
+  }
+}
+
+// logp of one row before any of its gradients can be written (gauss_ppo_kernel's first pass over the n dims): fp64 from the
+// fp32 heads and actions on, sigma included, so that the ratio's exponent carries no fp32 rounding (|logp| reaches 1e3 at
+// n = 64, where an fp32 ulp is 1e-4)
+__device__ __forceinline__ double gauss_row_logp(const float* __restrict__ row, const float* __restrict__ act, int n) {
+  double lp = 0.0;
+  for (int j = 0; j < n; ++j) {
+    const double raw = (double)row[n + j];
+    const double sg = (raw > 20.0 ? raw : log1p(exp(raw))) + 1e-4;
+    const double u = ((double)act[j] - (double)row[j]) / sg;
+    lp -= 0.5 * u * u + log(sg);
+  }
+  return lp - (double)n * kHalfLog2Pi;
+}
+
 __global__ __launch_bounds__(256) void gauss_nll_kernel(const float* __restrict__ heads, long ldh, const float* __restrict__ vals,
                                                         long vstride, const float* __restrict__ actions, long lda,
                                                         const float* __restrict__ advs, const float* __restrict__ returns,
@@ -173,7 +213,6 @@ __global__ __launch_bounds__(256) void gauss_nll_kernel(const float* __restrict_
                                                         float* __restrict__ dheads, long ldd, float* __restrict__ dvals,
                                                         long dvstride, double* loss_sums, double* scratch) {
   __shared__ double sm[4];
-  constexpr double kHalfLog2Pi = 0.91893853320467274178;
   const AdvNorm an = adv_norm(adv_sums, n_global);
   const float invN = 1.0f / (float)n_global;
   const float gen = entr_coef * invN;
@@ -182,26 +221,8 @@ __global__ __launch_bounds__(256) void gauss_nll_kernel(const float* __restrict_
     float w = advs[i];
     if (an.on) w = (w - an.mean) / an.den;
     const float gpi = -pi_coef * w * invN;
-    const float* row = heads + i * ldh;
-    const float* act = actions + i * lda;
-    float* drow = dheads + i * ldd;
-    double su2 = 0.0, sls = 0.0;         // sum_j u^2, sum_j log sigma
-    for (int j = 0; j < n; ++j) {
-      const float raw = row[n + j];
-      const float sg = gauss_sigma(raw);
-      const float inv_s = 1.f / sg;
-      const float u = (act[j] - row[j]) * inv_s;
-      const float dsig = (gpi * (u * u - 1.f) - gen) * inv_s;
-      float draw = dsig;
-      if (!(raw > 20.f)) {               // softplus backward: g * z / (z + 1), z = exp(raw)
-        const float z = expf(raw);
-        draw = dsig * z / (z + 1.f);
-      }
-      drow[j] = gpi * u * inv_s;
-      drow[n + j] = draw;
-      su2 += (double)(u * u);
-      sls += (double)logf(sg);
-    }
+    double su2, sls;                     // sum_j u^2, sum_j log sigma
+    gauss_nll_row(heads + i * ldh, actions + i * lda, n, gpi, gen, dheads + i * ldd, su2, sls);
     const float dv = vals[i * vstride] - returns[i];
     dvals[i * dvstride] = val_coef * 2.f * dv * invN;
     s_pi += (double)w * (-0.5 * su2 - sls - (double)n * kHalfLog2Pi);
@@ -213,6 +234,53 @@ __global__ __launch_bounds__(256) void gauss_nll_kernel(const float* __restrict_
   s_ent = block_sum_256(s_ent, sm);
   const double v3[3] = {s_pi, s_val, s_ent};
   grid_sum_ordered<3>(v3, loss_sums, scratch, sm);       // fixed-order second stage: no fp64 atomics
+}
+
+// The clipped-ratio (PPO) loss of the multi-epoch update (hyps["ppo_epochs"] >= 2) on gauss_nll_kernel's
+// rows: two passes over a row's n dims (logp first: the ratio scales every gradient of the row), the second one
+// gauss_nll_row with the policy weight times r inside the clip range and exactly zero where the clip binds.  RECORD: the
+// first epoch, r = 1 -- writes logp_old and gauss_nll_kernel's gradients bit for bit.
+template <bool RECORD>
+__global__ __launch_bounds__(256) void gauss_ppo_kernel(const float* __restrict__ heads, long ldh, const float* __restrict__ vals,
+                                                        long vstride, const float* __restrict__ actions, long lda,
+                                                        const float* __restrict__ advs, const float* __restrict__ returns,
+                                                        const double* __restrict__ adv_sums, long n_local, long n_global, int n,
+                                                        float pi_coef, float val_coef, float entr_coef, float clip,
+                                                        double* __restrict__ logp_old, float* __restrict__ dheads, long ldd,
+                                                        float* __restrict__ dvals, long dvstride, double* loss_sums,
+                                                        double* scratch) {
+  __shared__ double sm[4];
+  const AdvNorm an = adv_norm(adv_sums, n_global);
+  const float invN = 1.0f / (float)n_global;
+  const float gen = entr_coef * invN;
+  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n_local; i += gridDim.x * 256L) {
+    float w = advs[i];
+    if (an.on) w = (w - an.mean) / an.den;
+    float gpi = -pi_coef * w * invN;
+    const float* row = heads + i * ldh;
+    const float* act = actions + i * lda;
+    const double logp = gauss_row_logp(row, act, n);
+    if (RECORD) {
+      logp_old[i] = logp;
+      s[0] += (double)w;
+    } else {
+      const PpoRow pr = ppo_row(logp - logp_old[i], w, clip);
+      gpi = pr.keep ? (float)((double)gpi * pr.r) : 0.f;      // one rounding; r == 1 leaves gpi as it is
+      s[0] += pr.surr;
+      s[3] += pr.keep ? 0.0 : 1.0;
+      s[4] += pr.kl;
+    }
+    double su2, sls;
+    gauss_nll_row(row, act, n, gpi, gen, dheads + i * ldd, su2, sls);
+    const float dv = vals[i * vstride] - returns[i];
+    dvals[i * dvstride] = val_coef * 2.f * dv * invN;
+    s[1] += (double)(dv * dv);
+    s[2] -= (double)n * (0.5 + kHalfLog2Pi) + sls;
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) s[k] = block_sum_256(s[k], sm);
+  grid_sum_ordered<5>(s, loss_sums, scratch, sm);
 }
 }  // namespace
 
@@ -305,6 +373,35 @@ extern "C" int a2c_gauss_nll_fwd_bwd(const float* heads, int64_t ld_heads, const
                      heads, (long)ld_heads, vals, (long)val_stride, actions, (long)ld_act, advs, returns, adv_sums,
                      (long)n_local, (long)n_global, n, pi_coef, val_coef, entr_coef, dheads, (long)ldd, dvals,
                      (long)dval_stride, loss_sums, scratch);
+  A2C_CHECK_LAUNCH();
+  return A2C_OK;
+}
+
+extern "C" int a2c_gauss_ppo_fwd_bwd(const float* heads, int64_t ld_heads, const float* vals, int64_t val_stride,
+                                     const float* actions, int64_t ld_act, const float* advs, const float* returns,
+                                     const double* adv_sums, int64_t n_local, int64_t n_global, int n, float pi_coef,
+                                     float val_coef, float entr_coef, float clip, int record, double* logp_old, float* dheads,
+                                     int64_t ldd, float* dvals, int64_t dval_stride, double* loss_sums, double* scratch,
+                                     a2c_stream_t stream) {
+  if (n_local < 0 || n_global < n_local || n_global < 1 || n < 1 || n > A2C_GAUSS_MAX_N || !loss_sums || !scratch)
+    return A2C_ERR_ARG;
+  if (adv_sums && n_global < 2) return A2C_ERR_ARG;
+  if (!(clip > 0.f) || clip == INFINITY || (record != 0 && record != 1) || !logp_old) return A2C_ERR_ARG;
+  if (n_local == 0) {
+    a2c_zero_async(loss_sums, 5 * sizeof(double), a2c_s(stream));
+    return A2C_OK;
+  }
+  if (!heads || !vals || !actions || !advs || !returns || !dheads || !dvals || ld_heads < 2 * n || ld_act < n || ldd < 2 * n)
+    return A2C_ERR_ARG;
+  const dim3 grid(a2c_grid_1d(n_local, 256, A2C_PPO_MAX_BLOCKS));
+  if (record)
+    hipLaunchKernelGGL(gauss_ppo_kernel<true>, grid, dim3(256), 0, a2c_s(stream), heads, (long)ld_heads, vals, (long)val_stride,
+                       actions, (long)ld_act, advs, returns, adv_sums, (long)n_local, (long)n_global, n, pi_coef, val_coef,
+                       entr_coef, clip, logp_old, dheads, (long)ldd, dvals, (long)dval_stride, loss_sums, scratch);
+  else
+    hipLaunchKernelGGL(gauss_ppo_kernel<false>, grid, dim3(256), 0, a2c_s(stream), heads, (long)ld_heads, vals, (long)val_stride,
+                       actions, (long)ld_act, advs, returns, adv_sums, (long)n_local, (long)n_global, n, pi_coef, val_coef,
+                       entr_coef, clip, logp_old, dheads, (long)ldd, dvals, (long)dval_stride, loss_sums, scratch);
   A2C_CHECK_LAUNCH();
   return A2C_OK;
 }

@@ -26,7 +26,12 @@
   * ``--bootstrap-truncated``: the leg of hyps ``bootstrap_truncated`` and nothing else: ms per epoch of
     FCModel on the "device_graph" path with the key off and on, the samples of the two alternating (the key adds one N-row
     forward and three small launches to the update, and two stores per lane to the world step); with ``--learn N`` the
-    learning record with the key on (``--gauss-loss`` and ``--norm`` as given).  ``--out profiles/pendulum_trunc_bench.json``.
+    learning record with the key on (``--gauss-loss`` and ``--norm`` as given).  ``--out profiles/pendulum_trunc_bench.json``;
+  * ``--ppo-epochs K [--ppo-clip E]``: the leg of hyps ``ppo_epochs`` / ``ppo_clip`` and nothing else: ms
+    per epoch of FCModel on the "device_graph" path with the keys absent and with ``ppo_epochs = K``, the samples of the two
+    alternating (every further epoch of the update adds one forward, one loss launch, one backward and one optimiser step);
+    with ``--learn N`` the learning record with the keys (``--gauss-loss``, ``--norm`` and ``--bootstrap-truncated`` as given;
+    a Gaussian net needs ``--gauss-loss exact``).  ``--out profiles/ppo_bench.json``.
 
 Method: ONE PROCESS PER SAMPLE.  ``--sample WHAT`` runs one sample in this process (a warm-up that allocates, tunes and
 captures; then ``--epochs`` epochs, or the graph replays, between two HIP events) and prints one JSON line; without it the
@@ -74,8 +79,13 @@ def event_ms(fn, n):
 NORM_KEYS = dict(norm_obs=True, norm_rewards=True)
 
 
-def hyps_for(n_envs, T, path, norm=False, gauss_loss="reference", trunc=False):
-    return dict(NORM_KEYS if norm else {}, **(dict(bootstrap_truncated=True) if trunc else {}), gauss_loss=gauss_loss, gamma=.99, lambda_=.98, n_tsteps=T, n_rollouts=n_envs, n_envs=n_envs, n_frame_stack=4, action_shift=0,
+def ppo_keys(ppo):
+    """ppo: (epochs, clip) or None (the keys absent)"""
+    return dict(ppo_epochs=int(ppo[0]), ppo_clip=float(ppo[1])) if ppo else {}
+
+
+def hyps_for(n_envs, T, path, norm=False, gauss_loss="reference", trunc=False, ppo=None):
+    return dict(NORM_KEYS if norm else {}, **(dict(bootstrap_truncated=True) if trunc else {}), **ppo_keys(ppo), gauss_loss=gauss_loss, gamma=.99, lambda_=.98, n_tsteps=T, n_rollouts=n_envs, n_envs=n_envs, n_frame_stack=4, action_shift=0,
                 render=False, env_type="Pendulum-device" if path.startswith("device") else "Pendulum-host", use_bptt=False,
                 use_nstep_rets=False, norm_advs=True, entr_coef=.005, pi_coef=1.0, val_coef=.5, max_norm=.5, lr=1e-4,
                 optim_type="RMSprop", is_discrete=False, h_size=256, seed=0, rollout_graphs=path != "device_eager")
@@ -106,14 +116,14 @@ def sample_vecnorm(B=256, L=4, C=4, T=16, launches=200, replays=50, rounds=3):
     return dict(vecnorm_step=statistics.median(us))
 
 
-def sample_epoch(model, path, n_envs, T, epochs, norm=False, gauss_loss="reference", trunc=False):
+def sample_epoch(model, path, n_envs, T, epochs, norm=False, gauss_loss="reference", trunc=False, ppo=None):
     import torch
     import a2c_amd
     from a2c_amd import preprocessing
     from a2c_amd.pendulum import DevicePendulumPool, PendulumEnv, PendulumFactory
     from a2c_amd.runner import HostEnvPool, Runner, SequentialEnvironment
     from a2c_amd.updater import Updater
-    hyps = hyps_for(n_envs, T, path, norm, gauss_loss, trunc)
+    hyps = hyps_for(n_envs, T, path, norm, gauss_loss, trunc, ppo)
     torch.manual_seed(0)
     net = getattr(a2c_amd.models, model)([4, 4], 1, h_size=256, is_discrete=False)
     N = n_envs * T
@@ -193,7 +203,7 @@ def sample_kernel(B, steps=200, C=4, replays=50, rounds=3):
     return out
 
 
-def sample_learn(epochs, norm=False, gauss_loss="reference", trunc=False):
+def sample_learn(epochs, norm=False, gauss_loss="reference", trunc=False, ppo=None):
     """one train() run -> the evaluation return per epoch, and the untrained net's on worlds of the same kind (norm: with
     norm_obs and norm_rewards; the untrained net is then evaluated as every later epoch is, through a frozen block -- a fresh
     one, count 1e-4, mean 0, var 1, which is where train()'s own block starts)"""
@@ -204,7 +214,7 @@ def sample_learn(epochs, norm=False, gauss_loss="reference", trunc=False):
     from a2c_amd.runner import DeviceStatsRunner
     from a2c_amd.training import DEFAULTS, train
     folder = tempfile.mkdtemp(prefix="pendulum_learn_")
-    keys = dict(NORM_KEYS if norm else {}, **(dict(bootstrap_truncated=True) if trunc else {}), gauss_loss=gauss_loss)
+    keys = dict(NORM_KEYS if norm else {}, **(dict(bootstrap_truncated=True) if trunc else {}), **ppo_keys(ppo), gauss_loss=gauss_loss)
     hyps = dict(LEARN, exp_name="pendulum_learn", main_path=folder, **keys)
     # the untrained net: train()'s own construction (same seed, same defaults), evaluated as train() evaluates
     full = dict(DEFAULTS, **hyps, is_discrete=False, action_shift=0, state_shape=[hyps["n_frame_stack"], 4], action_size=1)
@@ -249,10 +259,12 @@ def spread(xs, nd=3):
     return dict(median=round(statistics.median(xs), nd), min=round(min(xs), nd), max=round(max(xs), nd), samples=[round(x, nd) for x in xs])
 
 
-def child(args, what, gauss_loss=None):
+def child(args, what, gauss_loss=None, ppo=False):
     cmd = [sys.executable, os.path.abspath(__file__), "--sample", what, "--epochs", str(args.epochs), "--host-epochs",
            str(args.host_epochs), "--n-envs", str(args.n_envs), "--n-tsteps", str(args.n_tsteps), "--gauss-loss",
            gauss_loss or args.gauss_loss]
+    if ppo:
+        cmd += ["--ppo-epochs", str(args.ppo_epochs), "--ppo-clip", str(args.ppo_clip)]
     out = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=args.sample_timeout).stdout
     return json.loads(out.strip().splitlines()[-1])
 
@@ -354,6 +366,43 @@ def trunc_leg(args):
     print(json.dumps(res))
 
 
+def ppo_leg(args):
+    """hyps ppo_epochs / ppo_clip absent / given, alternating samples of FCModel on the device_graph path; optionally the
+    learning record with the keys, each kept under a name that carries K beside what the file already holds"""
+    import torch
+    res = {}
+    if args.out and os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    res.update(device=torch.cuda.get_device_name(0), world=WORLD)
+
+    def save():
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+    tag = (":norm" if args.norm else "") + (":trunc" if args.bootstrap_truncated else "")
+    K = args.ppo_epochs
+    if args.repeats > 0:            # (--repeats 0 --learn N: the learning record alone)
+        res.update(repeats=args.repeats, n_envs=args.n_envs, n_tsteps=args.n_tsteps, epochs=args.epochs, optim="RMSprop",
+                   path="device_graph", gauss_loss=args.gauss_loss, norm=bool(args.norm), trunc=bool(args.bootstrap_truncated),
+                   ppo_clip=args.ppo_clip)
+        rows = {f"keys_absent_beside_{K}": [], f"ppo_epochs_{K}": []}
+        for _ in range(args.repeats):
+            rows[f"keys_absent_beside_{K}"].append(child(args, f"epoch:FCModel:device_graph{tag}")["ms_per_epoch"])
+            rows[f"ppo_epochs_{K}"].append(child(args, f"epoch:FCModel:device_graph{tag}", ppo=True)["ms_per_epoch"])
+        res.setdefault("ms_per_epoch", {}).setdefault("FCModel", {}).update({k: spread(v) for k, v in rows.items()})
+        print(f"# FCModel: { {k: res['ms_per_epoch']['FCModel'][k] for k in rows} }", file=sys.stderr, flush=True)
+        save()
+    if args.learn > 0:
+        name = ("learning" + ("_exact" if args.gauss_loss == "exact" else "") + ("_norm" if args.norm else "")
+                + ("_trunc" if args.bootstrap_truncated else "") + f"_ppo{K}")
+        L = res[name] = child(args, f"learn:{args.learn}{tag}", ppo=True)
+        print(f"# {name}, {L['epochs']} epochs in {L['seconds']} s: untrained {L['untrained']}, first tenth "
+              f"{L['first_tenth_mean']}, last tenth {L['last_tenth_mean']}, best {L['best']}", file=sys.stderr, flush=True)
+    save()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5, help="samples per figure: one process each")
@@ -369,6 +418,9 @@ def main():
     ap.add_argument("--exact", action="store_true", help="the gauss_loss leg only (see the module docstring)")
     ap.add_argument("--bootstrap-truncated", action="store_true",
                     help="the bootstrap_truncated leg only (see the module docstring)")
+    ap.add_argument("--ppo-epochs", type=int, default=0,
+                    help="hyps['ppo_epochs'] (0: the keys absent); without --sample: the ppo leg only (see the module docstring)")
+    ap.add_argument("--ppo-clip", type=float, default=0.2, help="hyps['ppo_clip'] beside --ppo-epochs")
     ap.add_argument("--sample", default=None, help="run ONE sample in this process: kernel:B, vecnorm, "
                                                    "epoch:MODEL:PATH[:norm][:trunc] or learn:N[:norm][:trunc]")
     ap.add_argument("--sample-timeout", type=float, default=600.0)
@@ -376,6 +428,7 @@ def main():
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "pendulum_bench needs the MI355X"
+    ppo = (args.ppo_epochs, args.ppo_clip) if args.ppo_epochs else None
     if args.sample:
         kind, *rest = args.sample.split(":")
         if kind == "kernel":
@@ -383,13 +436,16 @@ def main():
         elif kind == "vecnorm":
             res = sample_vecnorm()
         elif kind == "learn":
-            res = sample_learn(int(rest[0]), norm="norm" in rest[1:], gauss_loss=args.gauss_loss, trunc="trunc" in rest[1:])
+            res = sample_learn(int(rest[0]), norm="norm" in rest[1:], gauss_loss=args.gauss_loss, trunc="trunc" in rest[1:],
+                               ppo=ppo)
         else:
             model, path = rest[:2]
             res = sample_epoch(model, path, args.n_envs, args.n_tsteps, args.epochs if path.startswith("device") else args.host_epochs,
-                               norm="norm" in rest[2:], gauss_loss=args.gauss_loss, trunc="trunc" in rest[2:])
+                               norm="norm" in rest[2:], gauss_loss=args.gauss_loss, trunc="trunc" in rest[2:], ppo=ppo)
         print(json.dumps(res))
         return
+    if ppo:
+        return ppo_leg(args)
     if args.bootstrap_truncated:
         return trunc_leg(args)
     if args.exact:
