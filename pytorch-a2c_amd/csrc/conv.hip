@@ -4072,10 +4072,11 @@ static bool band_setup(const a2c_conv_desc* d, const float* dout, const float* w
   q.mgroups = 1; q.mt_total = ceil_div(d->Cin, 16);
   q.st.src = dout; q.st.bstride = (long)d->Cout * d->OH * d->OW; q.st.Cp = d->Cout; q.st.IH = d->OH; q.st.IW = d->OW;
   q.st.TIH = TIH; q.st.WP = WPo; q.st.PLANE = PLANEo; q.st.sx0 = ox_lo; q.st.fast = 0;
-  // one band = the whole sample (TY == H): dOut is staged and dX flushed as contiguous float4 runs (bwd_band_kernel)
+  q.st.vec = stage_vec(dout, q.st.bstride, d->OH, d->OW);
+  // one band = the whole sample (TY == H): dOut is staged and dX flushed as contiguous float4 runs (bwd_band_kernel);
+  // rows that stage_vec already moves as float4 (vec == 4) keep the row-wise staging
   q.st.flat = (TY == d->H && q.st.vec != 4 && ((long)d->Cout * d->OH * d->OW) % 4 == 0 && ((long)d->Cin * d->H * d->W) % 4 == 0 &&
                ((uintptr_t)dout % 16 == 0)) ? 1 : 0;
-  q.st.vec = stage_vec(dout, q.st.bstride, d->OH, d->OW);
   for (int cls = 0; cls < S * S; ++cls) {
     const int ry = cls / S, rx = cls % S;
     BandClass& k = q.cls[cls];
